@@ -86,7 +86,15 @@ def parse_args():
     ap.add_argument("--no-extras", action="store_true", help="skip the C2 / C5 child runs that the default N=1 run appends as `extras`")
     ap.add_argument("--e2e-only", default="", help="run only the file-based end-to-end extra on this configuration (C2 / C3) and print its object")
     ap.add_argument("--dump-contigs", default="", help="rank 0 writes the gathered contigs (sorted) of the last step to this JSON file")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed (picks and contig digests of every gap, the contigs and bases of a seeded "
+                         "sample of gaps) to DIR/<name>.npy in float64 / float32, at most 64 MB in all (one rank only)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.gpus != 1:
+        ap.error("--dump-outputs needs --gpus 1 (a rank holds the results of its own gaps only)")
+    return args
 
 
 def launch_ranks(args):
@@ -125,13 +133,14 @@ def main():
         import gc
         gc.collect()
         torch.cuda.empty_cache()
-        out["extras"] = {"C2": child_run(["--config", "C2", "--steps", "20", "--warmup", "2"]),
-                         # stress workload: C2's draft with planted repeats (reads that hit 50 gaps, pools of thousands of reads)
-                         "C2_with_planted_repeats": child_run(["--config", "C2R", "--steps", "5", "--warmup", "1"]),
-                         "C5_mate_pair_multi_k": child_run(["--config", "C5", "--steps", "3", "--warmup", "1"]),
-                         # SURVEY.md §8d's own figure for the mate-pair library (100 M records = 4.8x): recorded as it is — at KMC's
-                         # min-count 2 that depth leaves holes in every 2-kb gap, so (nearly) nothing closes; see MATE_PAIRS
-                         "C5_survey_sized_100M_mate_pairs": child_run(["--config", "C5", "--mp-reads", "100000000", "--steps", "2", "--warmup", "1"])}
+        extra_argv = {"C2": ["--config", "C2", "--steps", "20", "--warmup", "2"],
+                      # stress workload: C2's draft with planted repeats (reads that hit 50 gaps, pools of thousands of reads)
+                      "C2_with_planted_repeats": ["--config", "C2R", "--steps", "5", "--warmup", "1"],
+                      "C5_mate_pair_multi_k": ["--config", "C5", "--steps", "3", "--warmup", "1"],
+                      # SURVEY.md §8d's own figure for the mate-pair library (100 M records = 4.8x): recorded as it is — at KMC's
+                      # min-count 2 that depth leaves holes in every 2-kb gap, so (nearly) nothing closes; see MATE_PAIRS
+                      "C5_survey_sized_100M_mate_pairs": ["--config", "C5", "--mp-reads", "100000000", "--steps", "2", "--warmup", "1"]}
+        out["extras"] = {name: child_run(argv) for name, argv in extra_argv.items()}
         # the product path on files: the CLI on a C3-sized BAM + FASTQ pair, wall time split by stage
         out["extras"]["e2e_files_C3"] = e2e_files("C3")
         # the second half of BASELINE.json's metric: 2-kb gaps cannot close from a 300-bp library alone (C4: 0 by construction of the
@@ -142,6 +151,9 @@ def main():
                                                         "gaps_closed": c5.get("counts", {}).get("gaps_closed"),
                                                         "gaps_closed_correct": c5.get("counts", {}).get("gaps_closed_correct"),
                                                         "correct_per_s": c5.get("gaps_closed_correct_per_s"), "ms_per_step": c5["ms_per_step"]}
+        # the result line stays one short line: each child run keeps its headline figures and the arguments that print its full line
+        for name, argv in extra_argv.items():
+            out["extras"][name] = extra_headline(out["extras"][name], argv)
     if rank == 0:
         print(json.dumps(out), flush=True)
     import torch.distributed as dist
@@ -341,6 +353,8 @@ def run(args):
     astat = (d_astat.cpu().numpy().astype(np.float64) / max(1, args.steps))      # per step (this rank's gaps)
     gf.set_option("asm_stats_ptr", 0)
     res = pipe.fetch()          # synchronises; raises on any capacity / overflow flag of the step
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, res, n_gaps)
     n_ctg, n_seq, n_closed_local = res.n_contigs, res.n_seq, res.n_closed
     asm_off_t, asm_pool_t, asm_rows_total = res.asm_off_t, res.asm_pool_t, res.asm_rows_total
     d_seq, d_best = pipe.d_seq, pipe.d_best
@@ -538,6 +552,74 @@ def run(args):
     return (out if rank == 0 else None), rank, world
 
 
+DUMP_SAMPLE_GAPS = 256
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, res, n_gaps, seed=20261015):
+    """--dump-outputs: what the last timed step handed its caller (Pipeline.fetch: the contig records, their bases and every gap's pick
+    word) as .npy files two builds can be compared by, file for file.  The device lists contigs in no fixed order, so contigs are
+    ordered by (gap, k, kv, length, CRC-32 of the bases, n_nodes, cov_sum) and the picked contig is named by its rank in its gap.
+      picks.npy            float64 [gap] x (closed, anchor length, picked length, reverse, contig k, kv, length, rank in the gap; -1 when open)
+      gap_contigs.npy      float64 [gap] x (contigs, contig bases, cov_sum total, sum of the contigs' CRC-32 mod 2^32)
+      totals.npy           float64 (contigs, contig bases, gaps closed)
+      sample_gaps.npy      float64 the seeded sample of gaps whose contigs follow in full (first, last and random gaps)
+      sample_contigs.npy   float64 [contig] x (gap, k, kv, n_nodes, cov_sum, length, offset into sample_bases)
+      sample_bases.npy     float32 the sample's contig bases (ASCII codes), back to back
+    The sample is cut from its end until everything fits in DUMP_MAX_BYTES."""
+    import zlib
+    ctg, seq, best = res.contigs, res.seq, res.best
+    n = len(ctg)
+    gap, off, ln = ctg["gap"].astype(np.int64), ctg["seq_off"].astype(np.int64), ctg["length"].astype(np.int64)
+    mv = memoryview(seq)
+    crc = np.fromiter((zlib.crc32(mv[o:o + l]) for o, l in zip(off.tolist(), ln.tolist())), dtype=np.int64, count=n)
+    order = np.lexsort((ctg["cov_sum"], ctg["n_nodes"], crc, ln, ctg["kv"], ctg["k"], gap))
+    pos = np.empty(n, dtype=np.int64)
+    pos[order] = np.arange(n)
+    first = np.searchsorted(gap[order], np.arange(n_gaps))
+
+    picks = np.full((n_gaps, 8), -1.0)
+    picks[:, 0] = best != 0
+    closed = np.nonzero(best)[0]
+    b = best[closed]
+    ci = (0x7FFFFFFF - ((b >> np.uint64(1)) & np.uint64(0x7FFFFFFF))).astype(np.int64)
+    picks[closed, 1] = (b >> np.uint64(56)).astype(np.float64)
+    picks[closed, 2] = ((b >> np.uint64(32)) & np.uint64(0xFFFFFF)).astype(np.float64)
+    picks[closed, 3] = (b & np.uint64(1)).astype(np.float64)
+    picks[closed, 4] = ctg["k"][ci]
+    picks[closed, 5] = ctg["kv"][ci]
+    picks[closed, 6] = ln[ci]
+    picks[closed, 7] = pos[ci] - first[closed]
+
+    per_gap = np.zeros((n_gaps, 4))
+    per_gap[:, 0] = np.bincount(gap, minlength=n_gaps)
+    per_gap[:, 1] = np.bincount(gap, weights=ln, minlength=n_gaps)
+    per_gap[:, 2] = np.bincount(gap, weights=ctg["cov_sum"].astype(np.float64), minlength=n_gaps)
+    crc_sum = np.zeros(n_gaps, dtype=np.int64)
+    np.add.at(crc_sum, gap, crc)
+    per_gap[:, 3] = crc_sum % (1 << 32)
+    totals = np.array([n, len(seq), len(closed)], dtype=np.float64)
+
+    rng = np.random.RandomState(seed)
+    sample = np.unique(np.concatenate([[0, n_gaps - 1], rng.choice(n_gaps, min(n_gaps, DUMP_SAMPLE_GAPS), replace=False)]))
+    fixed = picks.nbytes + per_gap.nbytes + totals.nbytes + 6 * 128        # (128: an .npy header)
+    cost = per_gap[sample, 0] * 7 * 8 + per_gap[sample, 1] * 4 + 8       # a sampled gap: its contig records, bases and gap number
+    sample = sample[:int(np.searchsorted(np.cumsum(cost), DUMP_MAX_BYTES - fixed, side="right"))]
+    rows = order[np.isin(gap[order], sample)]
+    s_ctg = np.zeros((len(rows), 7))
+    for j, f in enumerate(("gap", "k", "kv", "n_nodes", "cov_sum", "length")):
+        s_ctg[:, j] = ctg[f][rows]
+    s_ctg[:, 6] = np.concatenate([[0], np.cumsum(ln[rows])[:-1]]) if len(rows) else []
+    bases = np.frombuffer(b"".join(mv[o:o + l] for o, l in zip(off[rows].tolist(), ln[rows].tolist())), dtype=np.uint8).astype(np.float32)
+
+    os.makedirs(path, exist_ok=True)
+    arrays = {"picks": picks, "gap_contigs": per_gap, "totals": totals, "sample_gaps": sample.astype(np.float64),
+              "sample_contigs": s_ctg, "sample_bases": bases}
+    assert sum(a.nbytes + 128 for a in arrays.values()) <= DUMP_MAX_BYTES
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def truth_check(cfg, gaps, flanks, ctg, seq, best, GapFill):
     """Every closed gap of this rank: the sequence the picker writes for the winning contig (gappadder_amd/pick_contigs.py on that one
     contig: same contig, strand and span as the device word, asserted) against the TRUE bases behind the planted gap
@@ -689,6 +771,17 @@ def child_run(argv):
                {"workload": d["config"]["workload"], "roofline_frac": d["roofline"]["frac"], "filter_ms": d["roofline"]["avg_launch_ms"]}
     except Exception as e:      # the headline line must not depend on an extra
         return {"error": repr(e)[:300], "stderr_tail": (r.stderr.decode()[-400:] if r is not None else "")}
+
+
+def extra_headline(d, argv):
+    """A child run's object cut to its headline figures for the result line; `python bench.py --no-extras --no-cpu <argv>` prints it whole."""
+    if "error" in d:
+        return dict(d, argv=argv)
+    counts = d.get("counts", {})
+    return {key: d[key] for key in ("value", "ms_per_step", "steps", "warmup", "gaps_per_s", "gaps_closed_per_s", "gaps_closed_correct_per_s",
+                                    "roofline_frac", "filter_ms") if key in d} | \
+           {"gaps_closed": counts.get("gaps_closed"), "gaps_closed_correct": counts.get("gaps_closed_correct"), "contigs": counts.get("contigs"),
+            "argv": argv}
 
 
 def pmc_traffic(config, reads_per_launch, L, k, launch_ms, launched):

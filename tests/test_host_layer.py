@@ -425,6 +425,55 @@ def test_roofline_traffic_is_quoted_only_from_a_profile_of_the_running_build(tmp
     assert bench.pmc_traffic("C4", 900_000_000, 150, 51, 15.2, launched) == 7.4e10
 
 
+def test_dumped_outputs_do_not_depend_on_the_device_order_of_the_contigs(tmp_path, monkeypatch):
+    """bench.py::dump_outputs (--dump-outputs): the same contigs listed in another order, with the pick words pointing at the same
+    contigs, give the same files; the picked contig is named by its content and its rank in the gap; the sample is cut to the byte budget."""
+    import types
+    import numpy as np
+    import bench
+    from gappadder_amd import _lib as B
+    rng = np.random.RandomState(5)
+    n_gaps, n = 300, 6000
+    ctg = np.zeros(n, dtype=B.CONTIG)
+    ctg["gap"] = rng.randint(0, n_gaps - 2, n)                    # the last two gaps have no contigs
+    ctg["k"] = rng.choice([31, 41], n)
+    ctg["kv"] = ctg["k"] - 2
+    ctg["length"] = rng.randint(40, 300, n)
+    ctg["n_nodes"] = rng.randint(1, 9, n)
+    ctg["cov_sum"] = rng.randint(0, 999, n)
+    ctg["seq_off"] = np.concatenate([[0], np.cumsum(ctg["length"])[:-1]])
+    seq = bytes(rng.choice(np.frombuffer(b"ACGT", np.uint8), int(ctg["length"].sum())))
+    picked = {g: int(np.nonzero(ctg["gap"] == g)[0][-1]) for g in range(0, n_gaps - 2, 3)}
+
+    def dump(perm, d):
+        inv = np.empty(n, dtype=np.int64)
+        inv[perm] = np.arange(n)
+        best = np.zeros(n_gaps, dtype=np.uint64)
+        for g, ci in picked.items():
+            best[g] = (30 << 56) | (777 << 32) | ((0x7FFFFFFF - int(inv[ci])) << 1) | (g & 1)
+        bench.dump_outputs(str(d), types.SimpleNamespace(contigs=ctg[perm], seq=seq, best=best), n_gaps)
+        return {f: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))}
+
+    a = dump(np.arange(n), tmp_path / "a")
+    b = dump(rng.permutation(n), tmp_path / "b")
+    assert sorted(a) == ["gap_contigs.npy", "picks.npy", "sample_bases.npy", "sample_contigs.npy", "sample_gaps.npy", "totals.npy"]
+    assert all(a[f].dtype in (np.float32, np.float64) and np.array_equal(a[f], b[f]) for f in a)
+    p = a["picks.npy"]
+    assert p[:, 0].sum() == len(picked) and (p[p[:, 0] == 0, 7] == -1).all()
+    g = 3
+    ci = picked[g]
+    assert list(p[g, :7]) == [1, 30, 777, 1, ctg["k"][ci], ctg["kv"][ci], ctg["length"][ci]]
+    sc, sb = a["sample_contigs.npy"], a["sample_bases.npy"]
+    for r in sc[:50]:
+        text = bytes(sb[int(r[6]):int(r[6] + r[5])].astype(np.uint8))
+        assert any(int(c["gap"]) == r[0] and seq[int(c["seq_off"]):int(c["seq_off"]) + int(c["length"])] == text for c in ctg[ctg["gap"] == r[0]])
+    assert list(a["totals.npy"]) == [n, len(seq), len(picked)]
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 1 << 20)
+    c = dump(np.arange(n), tmp_path / "c")
+    assert 0 < len(c["sample_gaps.npy"]) < len(a["sample_gaps.npy"])
+    assert sum(os.path.getsize(str(tmp_path / "c" / f)) for f in c) <= 1 << 20
+
+
 def test_a_read_that_fits_at_a_second_occurrence_of_its_seed_is_no_bridge(tmp_path):
     """A contig with an internal repeat: a read that lies wholly inside the SECOND copy shares its seeds with the first copy
     too, where its extension runs off or mismatches — bwa reports the end-to-end alignment, so the read is not clipped at that contig."""
