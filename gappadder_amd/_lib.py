@@ -20,6 +20,7 @@ SYNTH_CFG = np.dtype([("seed", "<u8"), ("scaffold_len", "<u8"), ("n_scaffolds", 
                       ("gap_len", "<u4"), ("read_len", "<u4"), ("insert_mean", "<u4"), ("insert_sd", "<u4"),
                       ("err_q16", "<u4"), ("mapq0_q16", "<u4"), ("chimeric_q16", "<u4"), ("flank_len", "<u4"),
                       ("library", "<u4"), ("repeats", "<u4")])
+CTG_PICK = np.dtype([("lp", "<u4"), ("rp", "<u4"), ("lm", "<u2"), ("rm", "<u2"), ("reverse", "u1"), ("threshold", "u1"), ("reserved", "<u2")])
 QCPAIR = np.dtype([("set", "<u4"), ("i", "<u4"), ("j", "<u4")])
 OVL_PARAMS = np.dtype([("mismatch", "<f8"), ("indel", "<f8"), ("max_clip", "<f8"), ("frac_min_overlap", "<f8"), ("frac_loss", "<f8"),
                        ("min_overlap", "<f8"), ("min_overlap_scaffold", "<f8"), ("relax", "<f8")])
@@ -123,6 +124,8 @@ def lib():
         "gf_pick_anchored_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp]),
         "gf_pick_anchored2_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, vp, vp]),
         "gf_pick_anchored2_from_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, vp, vp, vp]),
+        "gf_pick_aligned_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, vp, vp, vp, vp]),
+        "gf_pick_aligned_from_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, vp, vp, vp, vp, vp]),
         "gf_bridging_reads": (i32, [vp, C.c_char_p, vp, vp, C.c_char_p, vp, vp, sz, i32, i32, vp]),
         "gf_merge_open_gaps_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, i32, i32, vp, vp, i32, vp]),
         "gf_count_kmers": (i32, [vp, vp, vp, sz, i32, i32, i32, vp, vp, sz, szp]),

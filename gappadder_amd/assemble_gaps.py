@@ -277,9 +277,11 @@ def bridging_reads_batch(items, seed_len=30, budget=2):
 
 
 class GapAssembler:
-    def __init__(self, sf_fai, sf_pos, n_jobs, working_space, kmer_list=None, gf=None, bam_list=None, samtools_path=None):
+    def __init__(self, sf_fai, sf_pos, n_jobs, working_space, kmer_list=None, gf=None, bam_list=None, samtools_path=None, flank_anchor="exact"):
+        """flank_anchor: how every ContigsSelection round anchors the flanks on the contigs, "exact" or "align" (pick_contigs.py)."""
         global kmer_len_list, working_folder, _gf
         self.bam_list = list(bam_list or [])
+        self.flank_anchor = flank_anchor
         self.samtools_path = samtools_path
         if kmer_list is not None:
             kmer_len_list = list(kmer_list)
@@ -371,7 +373,7 @@ class GapAssembler:
         self.assembly(fa_list)
         merged = sum(1 for v in self.run_contigs_merge(fa_list).values() if v)
         sf_picked = working_folder + "../picked_seqs.fa"
-        cs = ContigsSelection(working_folder)
+        cs = ContigsSelection(working_folder, self.flank_anchor)
         closed = cs.pick_full_constructed_contigs(30, fa_list, sf_picked)
         remain = self.pick_already_constructed(cs, fa_list, sf_picked)
         recruited = 0

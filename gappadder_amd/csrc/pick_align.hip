@@ -1,0 +1,337 @@
+// pick_align.hip — flank anchoring by ungapped seed-and-extend of the WHOLE flanks (the "align" mode of the picker): the stand-in
+// for `bwa mem -T {score} -a` that aligns through a draft base that differs from the reads near a flank's gap-side end, where the
+// exact anchors of pick.hip lose the gap.  Definition (bwa mem's defaults as constants, written out): the docstring of
+// gappadder_amd/pick_contigs.py, host twin align_hits; the selection after the hits is select_full (pick_contigs.py:97-321), as in
+// pick.hip.  Entry points: gf_pick_aligned_dev / gf_pick_aligned_from_dev (include/gapfill_hip.h).
+//
+// One one-wave workgroup per contig.  The four queries of the contig's gap (left, revcomp(left), right, revcomp(right); codes 0-3,
+// 4 = non-ACGT) and a sorted table of their 19-mers are built once per gf_set_gaps.  Seeds: every lane rolls the 19-mers of a
+// stretch of the contig and looks each one up in the table (binary search); a (query, position) hit is a seed when it STARTS a run
+// of identical ACGT bases (the bases before it differ), so every maximal run of >= 19 identical bases on a diagonal is found
+// exactly once.  The seeds (<= SEED_MAX per contig) are ranked in LDS by (query, diagonal, query start) — the production order of
+// the definition —, extended one per lane, and lane 0 walks them in that order: the skip rule (a seed inside an alignment already
+// produced on its diagonal), the cap per (query), the per-(side, clip type) best hit of select_full and its seven pairs.
+#include <algorithm>
+#include <cstring>
+
+#include "gf_internal.hpp"
+
+namespace gf {
+
+constexpr int AL_SEED = 19, AL_MATCH = 1, AL_MISMATCH = -4, AL_NSCORE = -1, AL_ZDROP = 100, AL_CLIP = 5;
+constexpr int AL_FLANK_MAX = 1024, AL_SEED_MAX = 1024, AL_CAP = 64;
+constexpr int AL_TAB_META = -1, AL_TAB_KMERS = -2;      // keys of ctx->anchor_tabs (dropped with the exact anchors by gf_set_gaps)
+constexpr int CT_LEFT = 0, CT_RIGHT = 1, CT_NONE = 2;    // clip types the selection keeps (BOTH is never used, pick_contigs.py:104)
+
+struct AlignMeta {
+    uint32_t kbeg, kn;     // the gap's 19-mer entries: kmer << 12 | query << 10 | query position, ascending
+    uint32_t qoff;         // the gap's query bytes: left, revcomp(left), right, revcomp(right) back to back
+    uint16_t nl, nr;
+};
+static_assert(sizeof(AlignMeta) == 16, "AlignMeta");
+
+struct AlignParams {
+    const gf_contig* contigs;
+    const uint32_t* n_contigs;
+    uint32_t contig_cap;
+    const char* seq;
+    const AlignMeta* meta;
+    const uint8_t* qbytes;
+    const unsigned long long* kmers;
+    uint32_t n_gaps, t_long, t_short;
+    unsigned long long* gap_best;
+    uint32_t* n_closed;
+    gf_ctg_pick* ctg_pick;
+    uint32_t* stats;           // [0] alignments beyond the cap, [1] contigs with more than AL_SEED_MAX seeds
+    const uint32_t* first;     // or null
+};
+
+struct AlHit {
+    uint32_t m, score, rev, pos;   // m == 0: none
+};
+
+__device__ __forceinline__ uint32_t al_code(char c) {
+    return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
+}
+
+__device__ __forceinline__ int al_score(uint32_t a, uint32_t b) {
+    return (a > 3 || b > 3) ? AL_NSCORE : a == b ? AL_MATCH : AL_MISMATCH;
+}
+
+// one seed -> score << 33 | seed end << 22 | query begin << 11 | query end (pick_contigs.py::_extend)
+__device__ uint64_t al_extend(const uint8_t* Q, int n, const char* s, int m, int d, int qs) {
+    int se = qs;
+    while (se < n && se + d < m && Q[se] < 4 && Q[se] == al_code(s[se + d])) ++se;
+    int run = se - qs, best = run, qb = qs, i = qs - 1;
+    bool stopped = false;
+    for (; i >= 0 && i + d >= 0; --i) {
+        run += al_score(Q[i], al_code(s[i + d]));
+        if (run > best) { best = run; qb = i; }
+        else if (best - run > AL_ZDROP) { stopped = true; break; }
+    }
+    int score = best;
+    if (!stopped && i < 0 && run > 0 && run > best - AL_CLIP) { qb = 0; score = run; }
+    run = best = score;
+    int qe = se, j = se;
+    stopped = false;
+    for (; j < n && j + d < m; ++j) {
+        run += al_score(Q[j], al_code(s[j + d]));
+        if (run > best) { best = run; qe = j + 1; }
+        else if (best - run > AL_ZDROP) { stopped = true; break; }
+    }
+    score = best;
+    if (!stopped && j == n && run > 0 && run > best - AL_CLIP) { qe = n; score = run; }
+    return ((uint64_t)(uint32_t)score << 33) | ((uint64_t)se << 22) | ((uint64_t)qb << 11) | (uint64_t)qe;
+}
+
+// the selection of one threshold (pick_contigs.py::select_per_contig): false when no same-strand pair with a span >= 0
+__device__ bool al_select(const AlHit* left, const AlHit* right, uint32_t* lp, uint32_t* rp, uint32_t* lm, uint32_t* rm, uint32_t* rc,
+                          int* span) {
+    const int pairs[7][2] = {{CT_NONE, CT_NONE}, {CT_NONE, CT_LEFT}, {CT_NONE, CT_RIGHT}, {CT_LEFT, CT_NONE},
+                             {CT_LEFT, CT_RIGHT}, {CT_RIGHT, CT_NONE}, {CT_RIGHT, CT_LEFT}};
+    int top = -1;
+    bool any = false;
+    *rc = 0;
+#pragma unroll
+    for (int p = 0; p < 7; ++p) {
+        const AlHit l = left[pairs[p][0]], r = right[pairs[p][1]];
+        if (!l.m || !r.m || l.rev != r.rev || !(top < (int)(l.m + r.m))) continue;
+        top = (int)(l.m + r.m);
+        *lp = l.pos; *rp = r.pos; *lm = l.m; *rm = r.m;
+        *rc |= l.rev;                       // (:176-177: set by any winning reverse pair, never cleared)
+        any = true;
+    }
+    if (!any) return false;
+    *span = *rc ? (int)*lp - (int)(*rp + *rm) : (int)*rp - (int)(*lp + *lm);
+    return *span >= 0;
+}
+
+__global__ __launch_bounds__(64) void pick_align_kernel(AlignParams P) {
+    __shared__ unsigned long long keys[AL_SEED_MAX];   // seeds as found, then the extension results in rank order
+    __shared__ unsigned long long srt[AL_SEED_MAX];    // seeds in (query, diagonal, query start) order
+    __shared__ uint32_t cnt;
+    __shared__ AlHit tab[2][2][3];                     // [threshold][side][clip type] (lane 0)
+    const uint32_t n_ctg = *P.n_contigs < P.contig_cap ? *P.n_contigs : P.contig_cap;
+    const int lane = threadIdx.x;
+    for (uint32_t ci = (P.first ? *P.first : 0u) + blockIdx.x; ci < n_ctg; ci += gridDim.x) {
+        const gf_contig c = P.contigs[ci];
+        if (c.gap >= P.n_gaps || c.length < (uint32_t)AL_SEED) continue;        // (uniform over the workgroup)
+        const AlignMeta M = P.meta[c.gap];
+        if (!M.kn) continue;
+        const char* s = P.seq + c.seq_off;
+        const int m = (int)c.length, nl = M.nl, nr = M.nr;
+        const uint8_t* qb0 = P.qbytes + M.qoff;
+        const unsigned long long* km = P.kmers + M.kbeg;
+        if (lane == 0) cnt = 0;
+        __syncthreads();
+        // ---- seeds: run starts among the 19-mer hits
+        const int npos = m - AL_SEED + 1, chunk = (npos + 63) / 64;
+        const int p0 = lane * chunk, p1 = min(npos, p0 + chunk);
+        if (p0 < p1) {
+            uint64_t kmer = 0;
+            int run = 0;
+            for (int j = p0; j < p1 + AL_SEED - 1; ++j) {
+                const uint32_t b = al_code(s[j]);
+                if (b < 4) { kmer = ((kmer << 2) | b) & ((1ull << (2 * AL_SEED)) - 1); ++run; } else run = 0;
+                if (j < p0 + AL_SEED - 1 || run < AL_SEED) continue;
+                const int p = j - AL_SEED + 1;
+                const unsigned long long lo = (unsigned long long)kmer << 12;
+                uint32_t a = 0, z = M.kn;                  // first entry >= lo
+                while (a < z) {
+                    const uint32_t h = (a + z) >> 1;
+                    if (km[h] < lo) a = h + 1; else z = h;
+                }
+                const uint32_t prev = p > 0 ? al_code(s[p - 1]) : 4u;
+                for (; a < M.kn && (km[a] >> 12) == kmer; ++a) {
+                    const uint32_t qi = (uint32_t)(km[a] >> 10) & 3u, q = (uint32_t)km[a] & 1023u;
+                    const uint8_t* Q = qb0 + (qi == 0 ? 0 : qi == 1 ? nl : qi == 2 ? 2 * nl : 2 * nl + nr);
+                    if (p > 0 && q > 0 && Q[q - 1] < 4 && Q[q - 1] == prev) continue;     // not the start of its run
+                    const uint32_t at = atomicAdd(&cnt, 1u);
+                    if (at < (uint32_t)AL_SEED_MAX)
+                        keys[at] = ((unsigned long long)qi << 62) | ((unsigned long long)(p - (int)q + AL_FLANK_MAX) << 11) | q;
+                }
+            }
+        }
+        __syncthreads();
+        const uint32_t n = cnt;
+        if (n > (uint32_t)AL_SEED_MAX) {
+            if (lane == 0) atomicAdd(P.stats + 1, 1u);
+            __syncthreads();
+            continue;
+        }
+        // ---- rank sort (keys are distinct)
+        for (uint32_t i = lane; i < n; i += 64) {
+            const unsigned long long k = keys[i];
+            uint32_t r = 0;
+            for (uint32_t j = 0; j < n; ++j) r += keys[j] < k;
+            srt[r] = k;
+        }
+        __syncthreads();
+        // ---- extension, one seed per lane
+        for (uint32_t i = lane; i < n; i += 64) {
+            const unsigned long long k = srt[i];
+            const uint32_t qi = (uint32_t)(k >> 62), q = (uint32_t)k & 2047u;
+            const int d = (int)((k >> 11) & ((1ull << 51) - 1)) - AL_FLANK_MAX;
+            const uint8_t* Q = qb0 + (qi == 0 ? 0 : qi == 1 ? nl : qi == 2 ? 2 * nl : 2 * nl + nr);
+            keys[i] = al_extend(Q, qi < 2 ? nl : nr, s, m, d, (int)q);
+        }
+        __syncthreads();
+        if (lane == 0) {
+            for (int t = 0; t < 2; ++t)
+                for (int sd = 0; sd < 2; ++sd)
+                    for (int ct = 0; ct < 3; ++ct) tab[t][sd][ct] = AlHit{0, 0, 0, 0};
+            uint32_t produced[4] = {0, 0, 0, 0}, drops = 0;
+            unsigned long long last = ~0ull;
+            int max_qe = -1;
+            for (uint32_t i = 0; i < n; ++i) {
+                const unsigned long long k = srt[i], r = keys[i];
+                const uint32_t qi = (uint32_t)(k >> 62);
+                if ((k >> 11) != last) { last = k >> 11; max_qe = -1; }
+                const int se = (int)((r >> 22) & 2047u), qb = (int)((r >> 11) & 2047u), qe = (int)(r & 2047u);
+                const uint32_t score = (uint32_t)(r >> 33);
+                if (se <= max_qe) continue;                         // inside an alignment already produced on this diagonal
+                max_qe = qe > max_qe ? qe : max_qe;
+                const uint32_t np = qi == 0 ? ++produced[0] : qi == 1 ? ++produced[1] : qi == 2 ? ++produced[2] : ++produced[3];
+                if (np > (uint32_t)AL_CAP) { ++drops; continue; }
+                const int nq = qi < 2 ? nl : nr;
+                const bool cl = qb > 0, cr = qe < nq;
+                if (cl && cr) continue;                             // BOTH: never selected
+                const int ct = cl ? CT_LEFT : cr ? CT_RIGHT : CT_NONE;
+                const int d = (int)((k >> 11) & ((1ull << 51) - 1)) - AL_FLANK_MAX;
+                const AlHit h{(uint32_t)(qe - qb), score, qi & 1u, (uint32_t)(d + qb + 1)};
+                for (int t = 0; t < 2; ++t) {
+                    const uint32_t T = t == 0 ? P.t_long : P.t_short;
+                    if (!T || score < T) continue;
+                    AlHit& o = tab[t][qi >> 1][ct];
+                    // the hit with the longest match; equal matches: the first in align_hits' order (score desc, forward, pos asc)
+                    if (!o.m || h.m > o.m ||
+                        (h.m == o.m && (h.score > o.score || (h.score == o.score && (h.rev < o.rev || (h.rev == o.rev && h.pos < o.pos))))))
+                        o = h;
+                }
+            }
+            if (drops) atomicAdd(P.stats, drops);
+            uint32_t lp = 0, rp = 0, lm = 0, rm = 0, rc = 0, T = 0;
+            int span = -1;
+            if (al_select(tab[0][0], tab[0][1], &lp, &rp, &lm, &rm, &rc, &span)) T = P.t_long;
+            else if (P.t_short && al_select(tab[1][0], tab[1][1], &lp, &rp, &lm, &rm, &rc, &span)) T = P.t_short;
+            if (T) {
+                gf_ctg_pick* cp = P.ctg_pick + ci;
+                if (T > cp->threshold) {      // calls accumulate: the highest threshold a contig selects at stays
+                    gf_ctg_pick v;
+                    v.lp = lp; v.rp = rp; v.lm = (uint16_t)lm; v.rm = (uint16_t)rm; v.reverse = (uint8_t)rc; v.threshold = (uint8_t)T;
+                    v.reserved = 0;
+                    *cp = v;
+                }
+                unsigned long long sp = (unsigned long long)span + 1;
+                if (sp > 0xFFFFFFull) sp = 0xFFFFFFull;
+                const unsigned long long val = ((unsigned long long)T << 56) | (sp << 32) |
+                                               ((unsigned long long)(0x7FFFFFFFu - ci) << 1) | rc;
+                const unsigned long long old = atomicMax(P.gap_best + c.gap, val);
+                if (old == 0) atomicAdd(P.n_closed, 1u);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace gf
+
+using namespace gf;
+
+extern "C" {
+
+static int align_tables(gf_ctx* ctx, const AlignMeta** meta, const uint8_t** qbytes, const unsigned long long** kmers) {
+    const size_t ng = ctx->gaps.size();
+    DevBuf &tm = ctx->anchor_tabs[AL_TAB_META], &tk = ctx->anchor_tabs[AL_TAB_KMERS];
+    if (!tm.p || !tk.p) {   // built once per gf_set_gaps, which drops them
+        std::vector<AlignMeta> mt(ng);
+        std::vector<uint8_t> qb;
+        std::vector<unsigned long long> km;
+        auto code = [](char c) -> uint8_t { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; };
+        for (size_t g = 0; g < ng; ++g) {
+            const std::string &l = ctx->flank_left[g], &r = ctx->flank_right[g];
+            if ((int)l.size() > AL_FLANK_MAX || (int)r.size() > AL_FLANK_MAX) {
+                ctx->last_error = "gf_pick_aligned: gap " + std::to_string(g) + " has a flank longer than 1024 bases";
+                return GF_E_UNSUPPORTED;
+            }
+            AlignMeta& M = mt[g];
+            M.qoff = (uint32_t)qb.size();
+            M.nl = (uint16_t)l.size();
+            M.nr = (uint16_t)r.size();
+            M.kbeg = (uint32_t)km.size();
+            const std::string* fl[2] = {&l, &r};
+            for (int qi = 0; qi < 4; ++qi) {
+                const std::string& f = *fl[qi >> 1];
+                const size_t n = f.size(), q0 = qb.size();
+                for (size_t i = 0; i < n; ++i) {
+                    const uint8_t b = (qi & 1) ? code(f[n - 1 - i]) : code(f[i]);
+                    qb.push_back((qi & 1) && b < 4 ? (uint8_t)(3 - b) : b);
+                }
+                uint64_t kmer = 0;
+                int run = 0;
+                for (size_t i = 0; i < n; ++i) {
+                    const uint8_t b = qb[q0 + i];
+                    if (b < 4) { kmer = ((kmer << 2) | b) & ((1ull << (2 * AL_SEED)) - 1); ++run; } else run = 0;
+                    if (run >= AL_SEED) km.push_back(((unsigned long long)kmer << 12) | ((unsigned long long)qi << 10) | (i + 1 - AL_SEED));
+                }
+            }
+            M.kn = (uint32_t)(km.size() - M.kbeg);
+            std::sort(km.begin() + M.kbeg, km.end());
+        }
+        if (qb.size() > 0xFFFFFFFFull || km.size() > 0xFFFFFFFFull) return GF_E_UNSUPPORTED;
+        const size_t mbytes = ng * sizeof(AlignMeta), all = mbytes + qb.size();
+        int rc = ensure(ctx, tm, all + 64);
+        if (!rc) rc = ensure(ctx, tk, km.size() * 8 + 64);
+        if (rc) return rc;
+        GF_HIP(ctx, hipMemcpy(tm.p, mt.data(), mbytes, hipMemcpyHostToDevice));
+        if (!qb.empty()) GF_HIP(ctx, hipMemcpy((char*)tm.p + mbytes, qb.data(), qb.size(), hipMemcpyHostToDevice));
+        if (!km.empty()) GF_HIP(ctx, hipMemcpy(tk.p, km.data(), km.size() * 8, hipMemcpyHostToDevice));
+    }
+    *meta = (const AlignMeta*)tm.p;
+    *qbytes = (const uint8_t*)tm.p + ng * sizeof(AlignMeta);
+    *kmers = (const unsigned long long*)tk.p;
+    return GF_OK;
+}
+
+static int pick_aligned(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t_long,
+                        int t_short, const void* d_first, void* d_gap_best, void* d_n_closed, void* d_ctg_pick, void* d_stats) {
+    if (!ctx || !d_contigs || !d_n_contigs || !d_seq || !d_gap_best || !d_n_closed || !d_ctg_pick || !d_stats || t_long < 1 ||
+        t_long > 255 || contig_cap > 0x7FFFFFFFull || t_short < 0 || (t_short && t_short >= t_long))
+        return GF_E_INVAL;
+    const size_t ng = ctx->gaps.size();
+    if (ctx->flank_left.size() != ng || ctx->flank_right.size() != ng) return GF_E_STATE;
+    if (!ng) return GF_OK;
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    AlignParams P;
+    int rc = align_tables(ctx, &P.meta, &P.qbytes, &P.kmers);
+    if (rc) return rc;
+    P.contigs = (const gf_contig*)d_contigs;
+    P.n_contigs = (const uint32_t*)d_n_contigs;
+    P.contig_cap = (uint32_t)contig_cap;
+    P.seq = (const char*)d_seq;
+    P.n_gaps = (uint32_t)ng;
+    P.t_long = (uint32_t)t_long;
+    P.t_short = (uint32_t)t_short;
+    P.gap_best = (unsigned long long*)d_gap_best;
+    P.n_closed = (uint32_t*)d_n_closed;
+    P.ctg_pick = (gf_ctg_pick*)d_ctg_pick;
+    P.stats = (uint32_t*)d_stats;
+    P.first = (const uint32_t*)d_first;
+    LaunchTimer tm(ctx, GF_KERNEL_PICK);
+    hipLaunchKernelGGL(pick_align_kernel, dim3(ctx->n_cu * 16), dim3(64), 0, ctx->stream, P);
+    GF_HIP(ctx, hipGetLastError());
+    return GF_OK;
+}
+
+int gf_pick_aligned_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t_long,
+                        int t_short, void* d_gap_best, void* d_n_closed, void* d_ctg_pick, void* d_stats) {
+    return pick_aligned(ctx, d_contigs, d_n_contigs, contig_cap, d_seq, t_long, t_short, nullptr, d_gap_best, d_n_closed, d_ctg_pick, d_stats);
+}
+
+int gf_pick_aligned_from_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t_long,
+                             int t_short, const void* d_first, void* d_gap_best, void* d_n_closed, void* d_ctg_pick, void* d_stats) {
+    if (!d_first) return GF_E_INVAL;
+    return pick_aligned(ctx, d_contigs, d_n_contigs, contig_cap, d_seq, t_long, t_short, d_first, d_gap_best, d_n_closed, d_ctg_pick, d_stats);
+}
+
+}  // extern "C"

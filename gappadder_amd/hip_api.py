@@ -52,6 +52,7 @@ class GapFill:
             rc = self._L.gf_set_gaps(self._h, B._p(gaps), len(gaps), int(n_scaffolds), None, None)
         self._chk(rc, "gf_set_gaps")
         self.n_gaps = len(gaps)
+        self.flanks = [(l, r) for l, r in flanks] if flanks is not None else None    # (Pipeline.picked_sequences cuts exact-mode picks with them)
 
     @staticmethod
     def pack_reads(seqs, read_len, with_mask=False):

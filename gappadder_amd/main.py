@@ -40,6 +40,11 @@ def parse_configuration(path):
     cfg["wf"] = p.get("working_folder", "./GAPPadder_Output/")
     cfg["samtools"] = data.get("software_path", {}).get("samtools", "samtools")
     cfg["kmer_screen"] = int(p.get("kmer_screen", 0))   # extension: flank-k-mer recruitment from the FASTQ files (0 = off)
+    # extension: how the picker anchors the flanks on the contigs — "exact" anchors (default) or "align" (seed-and-extend of the whole
+    # flanks, closer to the reference's bwa mem; pick_contigs.py)
+    cfg["flank_anchor"] = str(p.get("flank_anchor", "exact"))
+    if cfg["flank_anchor"] not in ("exact", "align"):
+        raise SystemExit("parameters.flank_anchor must be 'exact' or 'align', not %r" % (cfg["flank_anchor"],))
     for path_, what in [(cfg["draft"], "draft genome")] + [(a[0], "bam") for a in cfg["alignments"]] + \
                        [(x, "raw reads") for pair in cfg["raw_reads"] for x in pair] + [(cfg["wf"], "working folder")]:
         if not os.path.exists(path_):
@@ -158,7 +163,8 @@ def main_func(command, sf_config):
         for s in SUB_MERGED:
             os.makedirs(wf + MERGE_FOLDER + s, exist_ok=True)
         ga = assemble_gaps.GapAssembler(sf_fai, sf_gap_pos, cfg["nthreads"], wf + MERGE_FOLDER, cfg["kmers"], gf,
-                                        bam_list=[bam for bam, _, _ in cfg["alignments"]], samtools_path=cfg["samtools"])
+                                        bam_list=[bam for bam, _, _ in cfg["alignments"]], samtools_path=cfg["samtools"],
+                                        flank_anchor=cfg["flank_anchor"])
         if first_round is not None:
             assemble_gaps.set_first_round(first_round)
         res = ga.assemble_pipeline()

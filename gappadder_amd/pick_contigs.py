@@ -7,7 +7,31 @@ the right flank (score = the reference's bwa_min_score: 30, later 15).  The sele
 including what its coordinates do on the reverse strand (the slice then keeps the last base of the LEFT anchor instead of the
 first base of the right one) — and is pinned on the reference's own answers (tests/golden/pick_kat.json.gz through
 oracle/gp_oracle.py).  The same rule runs on the device as gf_pick_anchored_dev (csrc/pick.hip).  A gap with a picked sequence
-is what this build reports as "closed"."""
+is what this build reports as "closed".
+
+A second, opt-in stand-in (`mode="align"`, `align_hits`) is closer to what bwa does: ungapped seed-and-extend of the WHOLE flanks.
+Exact anchors lose a gap to one draft base that differs from the reads within `score` bases of the flank's gap-side end; bwa aligns
+through such a base.  bwa is absent here, so this definition is this build's own, modelled on bwa mem's defaults and pinned on
+hand-derived answers (tests/test_pick_align_host.py), not on bwa's output.  For every contig, side and strand:
+  query      Q = the flank (forward strand) or revcomp(flank) (reverse strand), aligned to the FORWARD contig, so positions and clip
+             types come out in SAM's frame, as in the reference's flanks.sam;
+  seeds      on each diagonal d (contig index = query index + d) a seed is a maximal run of >= SEED_LEN (19, `-k`) consecutive
+             identical ACGT bases; diagonals ascending, seeds left to right; a seed that lies inside an alignment already produced on
+             its diagonal is skipped (every produced alignment counts, whatever its score);
+  extension  left first, then right, ungapped, from the seed's length as score: match +1, mismatch -4, a non-ACGT base on either
+             side -1; each side keeps the FIRST maximum of the running score and stops when the running score falls more than
+             ZDROP (100) below it;
+  end rule   when the contig reaches the query's end on that side and the extension got there without stopping, g = the running
+             score at that end: the alignment goes to the end when g > 0 and g > best - CLIP_PEN (5), else it is clipped at the
+             maximum (bwa's `gscore <= 0 || gscore <= score - pen_clip`);
+  hit        reported when its score >= T (the round's score, 30 or 15): pos = contig index of the first aligned query base + 1,
+             M = aligned length, clip type from (query start > 0, query end < |Q|): BOTH, LEFT, RIGHT or NONE;
+  cap        at most ALIGN_CAP (64) alignments per (contig, side, strand), in the order they were produced; later ones are dropped
+             and counted; a contig with more than SEED_MAX (1024) seeds over both flanks and strands gives no hits and is counted;
+  order      within a (contig, side) hits are ordered by score descending, forward before reverse, then pos ascending — so
+             select_full's "first on ties" and pick_extended_sequence's "first contig" mean something definite.
+Flanks are limited to FLANK_MAX (1 024) bases.  Indels between flank and contig are out of scope.  The device runs the same rule
+as gf_pick_aligned_dev (csrc/pick_align.hip)."""
 import os
 
 _COMP = str.maketrans("ACGTacgt", "TGCATGCA")            # gnrt_reverse_complementary, pick_contigs.py:19-33: upper-case output
@@ -84,11 +108,149 @@ def anchor_hits(contigs, left_flank, right_flank, score):
     return out
 
 
+SEED_LEN, MATCH, MISMATCH, N_SCORE, ZDROP, CLIP_PEN = 19, 1, -4, -1, 100, 5     # bwa mem: -k, -A, -B, N penalty, -d, -L
+ALIGN_CAP, SEED_MAX, FLANK_MAX = 64, 1024, 1024
+_CODE = {"A": 0, "C": 1, "G": 2, "T": 3}
+
+
+def _seeds(qs, c, index):
+    """Seeds of the four queries in one contig: [(query id, diagonal, query start)] (run starts of >= SEED_LEN identical ACGT bases)."""
+    out = []
+    for p in range(len(c) - SEED_LEN + 1):
+        for qi, q in index.get(c[p:p + SEED_LEN], ()):
+            Q = qs[qi]
+            if p == 0 or q == 0 or Q[q - 1] != c[p - 1] or Q[q - 1] not in _CODE:
+                out.append((qi, p - q, q))
+    return out
+
+
+def _sc(a, b):
+    if a not in _CODE or b not in _CODE:
+        return N_SCORE
+    return MATCH if a == b else MISMATCH
+
+
+def _extend(Q, c, d, qs):
+    """One seed -> (query begin, query end, score, seed end)."""
+    n, m = len(Q), len(c)
+    se = qs
+    while se < n and se + d < m and Q[se] == c[se + d] and Q[se] in _CODE:
+        se += 1
+    run = best = se - qs
+    qb, i, stopped = qs, qs - 1, False
+    while i >= 0 and i + d >= 0:
+        run += _sc(Q[i], c[i + d])
+        if run > best:
+            best, qb = run, i
+        elif best - run > ZDROP:
+            stopped = True
+            break
+        i -= 1
+    score = best
+    if not stopped and i < 0 and run > 0 and run > best - CLIP_PEN:
+        qb, score = 0, run
+    run = best = score
+    qe, j, stopped = se, se, False
+    while j < n and j + d < m:
+        run += _sc(Q[j], c[j + d])
+        if run > best:
+            best, qe = run, j + 1
+        elif best - run > ZDROP:
+            stopped = True
+            break
+        j += 1
+    score = best
+    if not stopped and j == n and run > 0 and run > best - CLIP_PEN:
+        qe, score = n, run
+    return qb, qe, score, se
+
+
+def _alignments(contig, queries, index, cap, stats):
+    """Per query id (0 left, 1 revcomp(left), 2 right, 3 revcomp(right)) the alignments that survive the cap, in production order:
+    [(diagonal, query begin, query end, score)]."""
+    seeds = _seeds(queries, contig, index)
+    out = [[], [], [], []]
+    if len(seeds) > SEED_MAX:
+        stats["seed_overflow"] = stats.get("seed_overflow", 0) + 1
+        return out
+    produced = [0, 0, 0, 0]
+    last, max_qe = None, -1
+    for qi, d, q in sorted(seeds):
+        if (qi, d) != last:
+            last, max_qe = (qi, d), -1
+        qb, qe, score, se = _extend(queries[qi], contig, d, q)
+        if se <= max_qe:                     # inside an alignment already produced on this diagonal
+            continue
+        max_qe = max(max_qe, qe)
+        produced[qi] += 1
+        if produced[qi] > cap:
+            stats["dropped"] = stats.get("dropped", 0) + 1
+            continue
+        out[qi].append((d, qb, qe, score))
+    return out
+
+
+def _queries(left_flank, right_flank):
+    if len(left_flank) > FLANK_MAX or len(right_flank) > FLANK_MAX:
+        raise ValueError("align mode: flanks are limited to %d bases" % FLANK_MAX)
+    strict = lambda f: "".join(x if x in _CODE else "N" for x in f)      # (a non-ACGT base stays one on the other strand)
+    qs = (left_flank, revcomp(strict(left_flank)), right_flank, revcomp(strict(right_flank)))
+    index = {}
+    for qi, Q in enumerate(qs):
+        for q in range(len(Q) - SEED_LEN + 1):
+            k = Q[q:q + SEED_LEN]
+            if all(x in _CODE for x in k):
+                index.setdefault(k, []).append((qi, q))
+    return qs, index
+
+
+def align_hits(contigs, left_flank, right_flank, score, cap=ALIGN_CAP, stats=None):
+    """The `align` stand-in for `bwa mem -T {score} -a` (the definition: this module's docstring): the same hit tuples as
+    anchor_hits, [(side, reverse?, contig index, 1-based position in the contig, clip type, matched bases)], per contig the left
+    hits, then the right hits, each in the documented order.  stats (a dict or None) counts "dropped" alignments beyond the cap and
+    contigs skipped for "seed_overflow"."""
+    stats = {} if stats is None else stats
+    qs, index = _queries(left_flank, right_flank)
+    out = []
+    for ci, (_, seq) in enumerate(contigs):
+        per_q = _alignments(seq, qs, index, int(cap), stats)
+        for side, q0 in (("left", 0), ("right", 2)):
+            hits = []
+            for rev in (False, True):
+                n = len(qs[q0 + rev])
+                for d, qb, qe, sc in per_q[q0 + rev]:
+                    if sc < score:
+                        continue
+                    ct = _BOTH if qb > 0 and qe < n else _LEFT if qb > 0 else _RIGHT if qe < n else _NONE
+                    hits.append((-sc, rev, d + qb + 1, ct, qe - qb))
+            hits.sort(key=lambda h: h[:3])
+            out += [(side, rev, ci, pos, ct, m) for _, rev, pos, ct, m in hits]
+    return out
+
+
+def stand_in_hits(mode, contigs, left_flank, right_flank, score):
+    if mode == "exact":
+        return anchor_hits(contigs, left_flank, right_flank, score)
+    if mode == "align":
+        return align_hits(contigs, left_flank, right_flank, score)
+    raise ValueError("flank anchor mode %r: 'exact' or 'align'" % (mode,))
+
+
 _PAIRS = ((_NONE, _NONE), (_NONE, _LEFT), (_NONE, _RIGHT), (_LEFT, _NONE), (_LEFT, _RIGHT), (_RIGHT, _NONE), (_RIGHT, _LEFT))
 
 
 def select_full(hits):
     """pick_contigs.py:97-321 on hit tuples: (contig index, left pos, right pos, left match, right match, reverse?) or None."""
+    best = None
+    for ci, (span, lp, rp, lm, rm, rc) in select_per_contig(hits).items():
+        if span > (-1 if best is None else best[0]):     # longest span, the earlier contig on ties (:313-321)
+            best = (span, ci, lp, rp, lm, rm, rc)
+    return None if best is None else best[1:]
+
+
+def select_per_contig(hits):
+    """pick_contigs.py:97-297 per contig: {contig index: (span, left pos, right pos, left match, right match, reverse?)}, in the
+    order the contigs first appear among the hits; only contigs with a same-strand pair."""
     table = {}                                           # contig -> side -> clip type -> (reverse?, match, pos)
     for side, rev, ci, pos, ct, m in hits:
         if ct == _BOTH:
@@ -96,7 +258,7 @@ def select_full(hits):
         slot = table.setdefault(ci, {}).setdefault(side, {})
         if ct not in slot or m > slot[ct][1]:
             slot[ct] = (rev, m, pos)
-    best = None
+    out = {}
     for ci, sides in table.items():
         if len(sides) != 2:
             continue
@@ -110,15 +272,14 @@ def select_full(hits):
         if sel is None:
             continue
         lp, rp, lm, rm = sel
-        span = (lp - (rp + rm)) if rc else (rp - (lp + lm))
-        if span > (-1 if best is None else best[0]):     # longest span, the earlier contig on ties (:313-321)
-            best = (span, ci, lp, rp, lm, rm, rc)
-    return None if best is None else best[1:]
+        out[ci] = ((lp - (rp + rm)) if rc else (rp - (lp + lm)), lp, rp, lm, rm, rc)
+    return out
 
 
-def pick_gap_sequence(contigs, left_flank, right_flank, anchor_len):
-    """contigs: [(name, seq)].  Returns (name, gap_seq, contig as written to picked_contigs.fa) or None (pick_contigs.py:331-358)."""
-    sel = select_full(anchor_hits(contigs, left_flank, right_flank, anchor_len))
+def pick_gap_sequence(contigs, left_flank, right_flank, anchor_len, mode="exact"):
+    """contigs: [(name, seq)].  Returns (name, gap_seq, contig as written to picked_contigs.fa) or None (pick_contigs.py:331-358).
+    mode: the stand-in for bwa's hits, "exact" (anchor_hits) or "align" (align_hits; anchor_len is then the score threshold)."""
+    sel = select_full(stand_in_hits(mode, contigs, left_flank, right_flank, anchor_len))
     if sel is None:
         return None
     ci, lp, rp, lm, rm, rc = sel
@@ -128,16 +289,17 @@ def pick_gap_sequence(contigs, left_flank, right_flank, anchor_len):
     return name, seq[lp + lm - 1:rp], seq
 
 
-def pick_extended_sequence(contigs, left_flank, right_flank, anchor_len):
+def pick_extended_sequence(contigs, left_flank, right_flank, anchor_len, mode="exact"):
     """The fallback of the last round (run_pick_extended_contig, pick_contigs.py:361-539): no contig carries both anchors in
     order, so the gap is filled from each side as far as a contig reaches and the parts are joined by 'NN' (:517-525).  Hit for
     hit the reference's rule on the stand-in's hits: clipped hits only (:388-389), per side the contig with the longest match —
     the anchors all match `anchor_len` bases and the reference's tie test is constant (int > str, :444, :457), so the FIRST contig
     with a hit; when both sides pick the same contig only the right side is used, and its slice then keeps the first anchor base
-    (:480-486 vs :509-512); reverse-strand slices keep one anchor base as well (:496, :474).  Returns (left_name, right_name,
-    sequence or None, picked_contigs text or None)."""
+    (:480-486 vs :509-512); reverse-strand slices keep one anchor base as well (:496, :474).  In "align" mode the hits carry real
+    match lengths, but the tie test stays constant, so it is still the first hit in align_hits' order.  Returns (left_name,
+    right_name, sequence or None, picked_contigs text or None)."""
     first = {"left": None, "right": None}
-    for side, rev, ci, pos, ct, m in anchor_hits(contigs, left_flank, right_flank, anchor_len):
+    for side, rev, ci, pos, ct, m in stand_in_hits(mode, contigs, left_flank, right_flank, anchor_len):
         want = (_RIGHT if rev else _LEFT) if side == "left" else (_LEFT if rev else _RIGHT)
         if ct == want and first[side] is None:
             first[side] = (ci, pos, m, rev)
@@ -167,8 +329,11 @@ def pick_extended_sequence(contigs, left_flank, right_flank, anchor_len):
 
 
 class ContigsSelection:
-    def __init__(self, working_space):
-        self.working_folder = working_space
+    def __init__(self, working_space, mode="exact"):
+        """mode: how the flanks are anchored on the contigs, "exact" (anchor_hits) or "align" (align_hits)."""
+        if mode not in ("exact", "align"):
+            raise ValueError("flank anchor mode %r: 'exact' or 'align'" % (mode,))
+        self.working_folder, self.mode = working_space, mode
 
     def _pick_one(self, gid, anchor_len):
         wf = self.working_folder
@@ -180,7 +345,7 @@ class ContigsSelection:
         if not (os.path.exists(sf_flank) and os.path.exists(sf_contig)):
             return False
         fl = dict(read_fasta(sf_flank))
-        res = pick_gap_sequence(read_fasta(sf_contig), fl.get(gid + "_left", ""), fl.get(gid + "_right", ""), anchor_len)
+        res = pick_gap_sequence(read_fasta(sf_contig), fl.get(gid + "_left", ""), fl.get(gid + "_right", ""), anchor_len, self.mode)
         if res is None:
             return False
         name, gap_seq, oriented = res
@@ -214,7 +379,8 @@ class ContigsSelection:
             if not (os.path.exists(sf_flank) and os.path.exists(sf_contig)):
                 continue
             fl = dict(read_fasta(sf_flank))
-            res = pick_extended_sequence(read_fasta(sf_contig), fl.get(gid + "_left", ""), fl.get(gid + "_right", ""), int(bwa_score))
+            res = pick_extended_sequence(read_fasta(sf_contig), fl.get(gid + "_left", ""), fl.get(gid + "_right", ""), int(bwa_score),
+                                         self.mode)
             if res is None:
                 continue
             left_name, right_name, seq, contig_text = res

@@ -64,7 +64,7 @@ class Results:
 class Pipeline:
     def __init__(self, gf, n_gaps, read_len, k_pairs, device=None, world=1, rank=0, backend="nccl", force_exchange=False,
                  min_count=2, min_contig=40, anchors=(30, 15), clip_dist=250, anchor_mapq=30, k_screen=None, keep_read_ids=False,
-                 key_column=True, merge_in_step=False, merge_max_set=128):
+                 key_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact"):
         """gf: a GapFill whose gaps (and flanks, when a library is screened) are set.  k_pairs: [(k, k_velvet)] of
         assemble_gaps.py:87-122.  The screen runs at the SMALLEST k of the list: a read that shares a 51-mer with a flank shares
         its 31-mers too, so this is the superset every assembly k needs (the reference recruits once, then assembles at every k).
@@ -72,7 +72,13 @@ class Pipeline:
         clip_dist / anchor_mapq: main.py:215-216.  key_column: the libraries keep an 8-byte key per alignment record beside the records
         ({pos, scaffold | MAPQ-0 bit}, built once when a library is added: 7.2 GB for C4's 900 M records) and the tagger streams THAT —
         a record far from every gap, 99 % of a BAM, is decided by (scaffold, position) alone (the reference's `focal_region.has_key(POS)`,
-        collect_reads_for_gaps.py:104) — fetching the 32-byte record only of what passes its bin maps."""
+        collect_reads_for_gaps.py:104) — fetching the 32-byte record only of what passes its bin maps.
+        anchor_mode: how every pick of the step anchors the flanks on the contigs — "exact" anchors (gf_pick_anchored2_dev) or "align",
+        seed-and-extend of the whole flanks (gf_pick_aligned_dev; `anchors` are then the score thresholds); with "align" the Results
+        carry `ctg_pick` (gf_ctg_pick per contig) and `align_dropped` / `align_seed_overflow` (gf_pick_aligned_dev's d_stats)."""
+        if anchor_mode not in ("exact", "align"):
+            raise ValueError("anchor_mode %r: 'exact' or 'align'" % (anchor_mode,))
+        self.anchor_mode = anchor_mode
         self.gf, self.lib, self.h = gf, B.lib(), gf.handle
         self.n_gaps, self.L, self.kk = int(n_gaps), int(read_len), [(int(a), int(b)) for a, b in k_pairs]
         self.rb = self.lib.gf_packed_read_bytes(self.L)
@@ -387,6 +393,9 @@ class Pipeline:
         self.d_acnt = torch.zeros(8, dtype=torch.int32, device=dev)
         self.ap = self.d_acnt.data_ptr()
         self.d_mstats = torch.zeros(B.MG_WORDS, dtype=torch.int32, device=dev)      # statistics of the merge round (gf_merge_open_gaps_dev)
+        if self.anchor_mode == "align":        # per contig the selection of the align-mode pick, and its two statistics words
+            self.d_ctg_pick = self._u8(self.contig_cap * B.CTG_PICK.itemsize)
+            self.d_pstats = torch.zeros(2, dtype=torch.int32, device=dev)
         pr = np.zeros(1, dtype=B.OVL_PARAMS)
         pr[0] = tuple(self.gf.MERGER_PARAMS)[:7] + (0.0,)       # ContigsMerger's options as GAPPadder sets them (MergeContigs.py:75)
         self.merge_params = pr
@@ -422,6 +431,9 @@ class Pipeline:
         # (zeroed through the library = on its stream; a torch op here would run on torch's stream)
         self._chk(lib.gf_memset_dev(h, self.d_xerr.data_ptr(), 0, 16) or lib.gf_memset_dev(h, self.d_best.data_ptr(), 0, 8 * max(1, n_gaps))
                   or lib.gf_memset_dev(h, self.ap + 16, 0, 16), "gf_memset_dev")
+        if self.anchor_mode == "align":
+            self._chk(lib.gf_memset_dev(h, self.d_ctg_pick.data_ptr(), 0, self.contig_cap * B.CTG_PICK.itemsize)
+                      or lib.gf_memset_dev(h, self.d_pstats.data_ptr(), 0, 8), "gf_memset_dev")
         if not self.need_merge:
             self.asm_ptr, self.asm_off, self.asm_rows = self.pool_ptr[0], self.libs[0].d_pool_off.data_ptr(), self.lib_cap
         elif not self.multi:
@@ -471,16 +483,25 @@ class Pipeline:
                                             self.d_seq.data_ptr(), self.seq_cap, self.ap + 8, self.d_gap_err.data_ptr()), "gf_assemble_multi_dev")
         # which gaps are closed: both flanks anchored on one contig (pick_contigs.py:64-358; scores 30 then 15, assemble_gaps.py:336, 365)
         a0, a1 = self.anchors[0], (self.anchors[1] if len(self.anchors) > 1 else 0)
-        self._chk(lib.gf_pick_anchored2_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), a0, a1,
-                                            self.d_best.data_ptr(), self.ap + 16), "gf_pick_anchored2_dev")
+        if self.anchor_mode == "align":
+            self._chk(lib.gf_pick_aligned_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), a0, a1, self.d_best.data_ptr(),
+                                              self.ap + 16, self.d_ctg_pick.data_ptr(), self.d_pstats.data_ptr()), "gf_pick_aligned_dev")
+        else:
+            self._chk(lib.gf_pick_anchored2_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), a0, a1,
+                                                self.d_best.data_ptr(), self.ap + 16), "gf_pick_anchored2_dev")
         if self.merge_in_step:
             # the open gaps' contigs through the contig merger, merged contigs appended (k = kv = 0), second pick over THEM only
             self._chk(lib.gf_merge_open_gaps_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), self.ap + 8, self.seq_cap,
                                                  self.d_best.data_ptr(), self.n_gaps, B._p(self.merge_params), 10, self.merge_max_set,
                                                  self.k_arr, self.kv_arr, min(16, len(self.kk)), self.d_mstats.data_ptr()), "gf_merge_open_gaps_dev")
-            self._chk(lib.gf_pick_anchored2_from_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), a0, a1,
-                                                     self.d_mstats.data_ptr() + 4 * B.MG_N0, self.d_best.data_ptr(), self.ap + 16),
-                      "gf_pick_anchored2_from_dev")
+            if self.anchor_mode == "align":
+                self._chk(lib.gf_pick_aligned_from_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), a0, a1,
+                                                       self.d_mstats.data_ptr() + 4 * B.MG_N0, self.d_best.data_ptr(), self.ap + 16,
+                                                       self.d_ctg_pick.data_ptr(), self.d_pstats.data_ptr()), "gf_pick_aligned_from_dev")
+            else:
+                self._chk(lib.gf_pick_anchored2_from_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), a0, a1,
+                                                         self.d_mstats.data_ptr() + 4 * B.MG_N0, self.d_best.data_ptr(), self.ap + 16),
+                          "gf_pick_anchored2_from_dev")
 
     def step(self, n=1):
         assert self.prepared, "Pipeline.prepare() first"
@@ -540,6 +561,10 @@ class Pipeline:
         r.contigs = np.frombuffer(self.d_ctg[:r.n_contigs * 32].cpu().numpy().tobytes(), dtype=B.CONTIG)
         r.seq = self.d_seq[:r.n_seq].cpu().numpy().tobytes()
         r.best = self.d_best[:self.n_gaps].cpu().numpy().view(np.uint64)
+        r.anchor_mode, r.ctg_pick, r.align_dropped, r.align_seed_overflow = self.anchor_mode, None, 0, 0
+        if self.anchor_mode == "align":
+            r.ctg_pick = np.frombuffer(self.d_ctg_pick[:r.n_contigs * B.CTG_PICK.itemsize].cpu().numpy().tobytes(), dtype=B.CTG_PICK)
+            r.align_dropped, r.align_seed_overflow = (int(x) for x in self.d_pstats.cpu().numpy())
         if r.merge is not None:      # gaps whose winning contig is a merged one
             idx = 0x7FFFFFFF - ((r.best >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64)
             r.merge["gaps_closed_by_merging"] = int(((r.best != 0) & (idx >= r.merge["contigs_before"])).sum())
@@ -594,12 +619,49 @@ class Pipeline:
         d_n2 = torch.tensor([len(new), 0, 0, 0], dtype=torch.int32, device=self.dev)
         torch.cuda.synchronize()
         a0, a1 = self.anchors[0], (self.anchors[1] if len(self.anchors) > 1 else 0)
-        self._chk(self.lib.gf_pick_anchored2_dev(self.h, d_c2.data_ptr(), d_n2.data_ptr(), len(new), d_s2.data_ptr(), a0, a1, d_b2.data_ptr(),
-                                                 d_n2.data_ptr() + 8), "gf_pick_anchored2_dev")
+        if self.anchor_mode == "align":
+            d_p2 = torch.zeros(len(new) * B.CTG_PICK.itemsize, dtype=torch.uint8, device=self.dev)
+            d_st2 = torch.zeros(2, dtype=torch.int32, device=self.dev)
+            torch.cuda.synchronize()
+            self._chk(self.lib.gf_pick_aligned_dev(self.h, d_c2.data_ptr(), d_n2.data_ptr(), len(new), d_s2.data_ptr(), a0, a1, d_b2.data_ptr(),
+                                                   d_n2.data_ptr() + 8, d_p2.data_ptr(), d_st2.data_ptr()), "gf_pick_aligned_dev")
+        else:
+            self._chk(self.lib.gf_pick_anchored2_dev(self.h, d_c2.data_ptr(), d_n2.data_ptr(), len(new), d_s2.data_ptr(), a0, a1, d_b2.data_ptr(),
+                                                     d_n2.data_ptr() + 8), "gf_pick_anchored2_dev")
         self.gf.sync()
         b2 = d_b2[:self.n_gaps].cpu().numpy().view(np.uint64)
         out["closed"] = {int(g): decode_best(b2[g]) for g in np.nonzero(b2)[0]}
+        if self.anchor_mode == "align":       # (the selections of the merged contigs, indexed like "contigs")
+            out["ctg_pick"] = np.frombuffer(d_p2.cpu().numpy().tobytes(), dtype=B.CTG_PICK)
+            out["align_dropped"], out["align_seed_overflow"] = (int(x) for x in d_st2.cpu().numpy())
         out["arrays"] = (c2, "".join(s for _, s in new).encode(), b2)       # the second pick's contig table, bases and pick words
+        return out
+
+    def picked_sequences(self, res):
+        """The gap sequence of every gap the step closed, cut from its winning contig as ContigsSelection writes it to picked_seqs.fa
+        (pick_contigs.py:341-349): {gap: (contig index, gap sequence, reverse?)}.  "align": from the contig's selection in
+        res.ctg_pick; "exact": the host picker (pick_contigs.pick_gap_sequence) on the winning contig alone, at the word's anchor
+        length, with the flanks given to gf_set_gaps."""
+        from .pick_contigs import pick_gap_sequence, revcomp
+        out = {}
+        for g in np.nonzero(res.best)[0]:
+            a_len, span1, ci, rev = decode_best(res.best[g])
+            c = res.contigs[ci]
+            seq = res.seq[int(c["seq_off"]):int(c["seq_off"]) + int(c["length"])].decode()
+            if res.anchor_mode == "align":
+                p = res.ctg_pick[ci]
+                lp, rp, lm, rm = int(p["lp"]), int(p["rp"]), int(p["lm"]), int(p["rm"])
+                assert int(p["threshold"]) == a_len and int(p["reverse"]) == rev, (int(g), p, a_len, rev)
+                body = revcomp(seq[rp + rm - 1:lp]) if rev else seq[lp + lm - 1:rp]
+            else:
+                if self.gf.flanks is None:
+                    raise ValueError("picked_sequences in exact mode needs the flanks given to gf_set_gaps")
+                l, r = self.gf.flanks[g]
+                picked = pick_gap_sequence([("c", seq)], l, r, a_len)
+                if picked is None:
+                    raise RuntimeError("gap %d: the host picker does not confirm the device's pick" % g)
+                body = picked[1]
+            out[int(g)] = (int(ci), body, bool(rev))
         return out
 
     def fixed_ms(self, steps):

@@ -461,6 +461,39 @@ int gf_pick_anchored_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_con
 int gf_pick_anchored2_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
                           int anchor_len, int anchor_len_short, void* d_gap_best, void* d_n_closed);
 
+/* ---- flank anchoring in "align" mode: ungapped seed-and-extend of the WHOLE flanks instead of exact anchors (the stand-in for
+ * `bwa mem -T {T} -a` that aligns through a draft base differing from the reads near a flank's gap-side end).  The definition, with
+ * bwa mem's default parameters as constants, for every contig, side and strand: query Q = the flank, or revcomp(flank) on the
+ * reverse strand, aligned to the forward contig (SAM's frame); seeds = maximal runs of >= 19 identical ACGT bases on one diagonal,
+ * diagonals ascending, seeds left to right, a seed inside an alignment already produced on its diagonal skipped; extension left,
+ * then right, ungapped, from the seed length as score: match +1, mismatch -4, non-ACGT on either side -1, the first maximum kept,
+ * stop when the running score falls more than 100 below it; at a query end the contig reaches, the score g of extending to the end
+ * wins when g > 0 and g > best - 5 (else the end is clipped); reported when score >= T: pos = contig index of the first aligned
+ * query base + 1, M = aligned length, clip type from (query start > 0, query end < |Q|); at most 64 alignments per (contig, side,
+ * strand) in production order (the rest are dropped and counted in d_stats[0]); a contig with more than 1 024 seeds over both
+ * flanks and strands gives no hits (counted in d_stats[1]).  Per (side, clip type) the hit with the longest M, ties to the higher
+ * score, the forward strand, the lower pos; then the reference's seven pairs (pick_contigs.py:149-297, the reverse flag never
+ * cleared, :176-177) and the span as for gf_pick_anchored_dev.  Host twin: gappadder_amd/pick_contigs.py::align_hits.
+ * t_long (1..255) and t_short (< t_long; 0 = one round) are the two score thresholds of the pipeline (30 and 15).
+ * d_gap_best (u64 per gap, caller zeroes, atomicMax) = T << 56 | (span + 1) << 32 | (0x7FFFFFFF - contig index) << 1 | reverse,
+ * T = the threshold the contig selects at (the higher one when both): decode exactly as gf_pick_anchored_dev's words, a pick at
+ * t_long outranks any at t_short; *d_n_closed (u32, caller zeroes) counts gaps that became non-zero.
+ * d_ctg_pick: gf_ctg_pick per contig index (contig_cap entries, caller zeroes): the contig's selection at the highest threshold it
+ * selects at, over this and earlier calls (an entry is replaced only by one of a higher threshold); threshold 0 = none.
+ * d_stats: 2 x u32 (caller zeroes; calls accumulate).  Flanks of more than 1 024 bases: GF_E_UNSUPPORTED (nothing is truncated). */
+typedef struct {
+    uint32_t lp, rp;      /* 1-based contig positions of the left and right flank alignments */
+    uint16_t lm, rm;      /* their aligned lengths */
+    uint8_t reverse;      /* the pair is on the reverse strand (the contig is written reverse-complemented) */
+    uint8_t threshold;    /* the score threshold it was selected at; 0 = no selection */
+    uint16_t reserved;
+} gf_ctg_pick;
+int gf_pick_aligned_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t_long,
+                        int t_short, void* d_gap_best, void* d_n_closed, void* d_ctg_pick, void* d_stats);
+/* gf_pick_aligned_dev over the contigs from *d_first (u32, device) on: the second pick after gf_merge_open_gaps_dev */
+int gf_pick_aligned_from_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t_long,
+                             int t_short, const void* d_first, void* d_gap_best, void* d_n_closed, void* d_ctg_pick, void* d_stats);
+
 /* ---- §8f-3, first piece: the all-pairs k-mer prefilter of the reference's ContigsMerger (QuickCheckerContigsMatch,
  * ContigsCompactor.cpp:1982-2095, applied by CompactVer3 :836-853 / threadQuickCheck :1073-1098).  A contig SET (one per gap: its
  * contigs.fa) becomes the node list [c0, revcomp(c0), c1, revcomp(c1), ...]; pair (i, j), i <= j, is feasible iff some k-mer of
