@@ -38,6 +38,10 @@ MG_N_PRE, MG_N_SETS, MG_SKIPPED, MG_N_PAIRS, MG_QC_FLAGS, MG_N_JOBS, MG_ERR, MG_
 MG_SKIPPED_GRAPH = 16
 MG_WORDS = 32
 
+# words of the second round's statistics (round2.hip, u32[16])
+R2_KMERS, R2_TAB_FULL, R2_HITS, R2_UNIQUE, R2_TRIED, R2_WITH, R2_ROWS, R2_FIRST, R2_APPEND_ERR, R2_N2, R2_POOL_OVF = 0, 1, 2, 3, 4, 5, 6, 8, 9, 10, 11
+R2_WORDS, R2_MAX_LIBS = 16, 16
+
 _lib = None
 
 
@@ -128,6 +132,12 @@ def lib():
         "gf_pick_aligned_from_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, vp, vp, vp, vp, vp]),
         "gf_bridging_reads": (i32, [vp, C.c_char_p, vp, vp, C.c_char_p, vp, vp, sz, i32, i32, vp]),
         "gf_merge_open_gaps_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, i32, i32, vp, vp, i32, vp]),
+        "gf_both_unmapped_reads_dev": (i32, [vp, vp, sz, sz, vp, vp, sz, vp]),
+        "gf_contig_kmer_table_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, i32, vp, i32, vp]),
+        "gf_recruit_by_contigs_dev": (i32, [vp, vp, vp, sz, i32, vp, vp, sz, i32, i32, vp, i32, vp, sz, vp]),
+        "gf_round2_work_words": (sz, [sz, sz]),
+        "gf_round2_pools_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, vp, vp, vp, sz, vp, vp, vp, sz, vp]),
+        "gf_contigs_append_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp]),
         "gf_count_kmers": (i32, [vp, vp, vp, sz, i32, i32, i32, vp, vp, sz, szp]),
         "gf_pool_keys_reset": (i32, [vp, vp]),
         "gf_pool_keys_from_screen_dev": (i32, [vp, vp, vp, sz, i32, vp, sz, vp]),

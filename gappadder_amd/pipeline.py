@@ -16,6 +16,9 @@ What the reference does with files between processes —
     gf_assemble_multi_dev                                      every (k, kv) pair (a-6)
     gf_pick_anchored2_dev                                      closed gaps (f-1)
     gf_merge_open_gaps_dev + gf_pick_anchored2_from_dev        contig merger for the gaps still open, second pick (f-3; merge_in_step)
+    gf_contig_kmer_table_dev + gf_recruit_by_contigs_dev       second assembly round for the gaps still open (second_round):
+      + gf_round2_pools_dev + gf_assemble_multi_dev            both-unmapped pairs recruited by the round-1 contigs' k-mers, pools
+      + gf_contigs_append_dev + gf_pick_*_from_dev             = round-1 rows + recruits, assembled and picked again
 
 `Pipeline` owns the sizing pass (capacities follow what the libraries actually recruit), every intermediate buffer, the stream
 wiring and — in a multi-rank run — the one exchange step.  Two callers: bench.py (libraries synthesised on the
@@ -64,7 +67,7 @@ class Results:
 class Pipeline:
     def __init__(self, gf, n_gaps, read_len, k_pairs, device=None, world=1, rank=0, backend="nccl", force_exchange=False,
                  min_count=2, min_contig=40, anchors=(30, 15), clip_dist=250, anchor_mapq=30, k_screen=None, keep_read_ids=False,
-                 key_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact"):
+                 key_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False):
         """gf: a GapFill whose gaps (and flanks, when a library is screened) are set.  k_pairs: [(k, k_velvet)] of
         assemble_gaps.py:87-122.  The screen runs at the SMALLEST k of the list: a read that shares a 51-mer with a flank shares
         its 31-mers too, so this is the superset every assembly k needs (the reference recruits once, then assembles at every k).
@@ -75,9 +78,25 @@ class Pipeline:
         collect_reads_for_gaps.py:104) — fetching the 32-byte record only of what passes its bin maps.
         anchor_mode: how every pick of the step anchors the flanks on the contigs — "exact" anchors (gf_pick_anchored2_dev) or "align",
         seed-and-extend of the whole flanks (gf_pick_aligned_dev; `anchors` are then the score thresholds); with "align" the Results
-        carry `ctg_pick` (gf_ctg_pick per contig) and `align_dropped` / `align_seed_overflow` (gf_pick_aligned_dev's d_stats)."""
+        carry `ctg_pick` (gf_ctg_pick per contig) and `align_dropped` / `align_seed_overflow` (gf_pick_aligned_dev's d_stats).
+        second_round: the reference's second assembly round (assemble_gaps.py:344-351) inside the step for the gaps the first pick
+        leaves open: the pairs with both mates unmapped (FLAG & 12 == 12) that share a canonical k-mer (the smallest k of k_pairs in
+        16..64) with a gap's round-1 contigs are appended to its pool, the gap is assembled again at every (k, kv) and picked over the
+        round-2 contigs only (appended after round 1's; Results.round2 / round2_first).  Single rank, without merge_in_step.
+        The candidate pairs are listed from the libraries' alignment records once, in prepare(): like the key column, they assume the
+        records do not change after prepare() (a caller that rewrites d_recs prepares a new Pipeline)."""
         if anchor_mode not in ("exact", "align"):
             raise ValueError("anchor_mode %r: 'exact' or 'align'" % (anchor_mode,))
+        self.second_round = bool(second_round)
+        if self.second_round:
+            if int(world) > 1 or force_exchange:
+                raise ValueError("second_round runs on a single rank")
+            if merge_in_step:
+                raise ValueError("second_round with merge_in_step: the order of the merge and the second round is not settled")
+            ks = [int(a) for a, _ in k_pairs if 16 <= int(a) <= 64]
+            if not ks:
+                raise ValueError("second_round needs a k in 16..64 among k_pairs")
+            self.k_round2 = min(ks)
         self.anchor_mode = anchor_mode
         self.gf, self.lib, self.h = gf, B.lib(), gf.handle
         self.n_gaps, self.L, self.kk = int(n_gaps), int(read_len), [(int(a), int(b)) for a, b in k_pairs]
@@ -402,11 +421,137 @@ class Pipeline:
         self.k_arr = (C.c_int * nk)(*[a for a, _ in self.kk])
         self.kv_arr = (C.c_int * nk)(*[b for _, b in self.kk])
         torch.cuda.synchronize()
+        if self.second_round:
+            self._prepare_round2()
         if self.tag_ahead:          # the first step's tagger pass (untimed, like a warm-up step's)
             assert all(lb.second_stream for lb in self.libs), "tag_ahead needs DeviceLibrary(tag_ctx=...)"
             self._on_stream(lambda: [self.tagger(lb) for lb in self.libs])
             self.sync()
         self.prepared = True
+
+    # ---- second assembly round: sizing (untimed) ---------------------------------------------------------------------------
+    def _r2_caps(self, rows):
+        nk = max(1, len(self.kk))
+        return (64 * self.n_gaps + 4096 + rows // 4) * nk, (24576 * self.n_gaps + (1 << 20) + 32 * rows) * nk
+
+    def _r2_alloc(self):
+        dev = self.dev
+        self.d_r2tab = self._u8(24 << self.r2_log2)
+        self.d_r2keys = torch.empty(self.r2_key_cap, dtype=torch.int64, device=dev)
+        self.d_r2sorted = torch.empty(self.r2_key_cap, dtype=torch.int64, device=dev)
+        self.d_r2work = torch.empty(int(self.lib.gf_round2_work_words(self.r2_key_cap, self.n_gaps)), dtype=torch.int32, device=dev)
+        self.d_r2pool = self._u8(self.r2_pool_cap * self.rb + 64)
+        self.d_ctg2 = self._u8(self.r2_ctg_cap * 32)
+        self.d_seq2 = self._u8(self.r2_seq_cap)
+
+    def _prepare_round2(self):
+        """Candidates of every library (they depend on the records alone: listed once, like the key column — the records must not change
+        after prepare()), then the step with the round
+        run again and again, every buffer grown to the exact count the run before reported, until nothing is beyond a capacity."""
+        lib, h, dev = self.lib, self.h, self.dev
+        if len(self.libs) > B.R2_MAX_LIBS:
+            raise ValueError("second_round: at most %d libraries" % B.R2_MAX_LIBS)
+        if not self.kk or not self.assemble_in_step:
+            raise ValueError("second_round runs inside the step's assembly (k_pairs and assemble_in_step)")
+        for lb in self.libs:
+            lb.d_r2bits = self._u8(((lb.n_reads // 2 + 31) // 32) * 4)
+            lb.d_r2n = torch.zeros(4, dtype=torch.int32, device=dev)
+            lb.r2_cap, lb.d_r2pairs = 0, torch.empty(1, dtype=torch.int32, device=dev)
+            for _ in range(2):
+                torch.cuda.synchronize()
+                self._chk(lib.gf_both_unmapped_reads_dev(h, lb.d_recs.data_ptr(), lb.n_recs, lb.n_reads, lb.d_r2bits.data_ptr(), lb.d_r2pairs.data_ptr(),
+                                                         lb.r2_cap, lb.d_r2n.data_ptr()), "gf_both_unmapped_reads_dev")
+                self.gf.sync()
+                n = int(lb.d_r2n[0])
+                if n <= lb.r2_cap:
+                    break
+                lb.r2_cap, lb.d_r2pairs = n, torch.empty(n + 1, dtype=torch.int32, device=dev)
+        self.r2_lib_ptrs = (C.c_void_p * len(self.libs))(*[lb.d_reads.data_ptr() for lb in self.libs])
+        self.d_r2st = torch.zeros(B.R2_WORDS, dtype=torch.int32, device=dev)
+        self.d_acnt2 = torch.zeros(8, dtype=torch.int32, device=dev)
+        self.d_gap_err2 = torch.zeros(max(1, self.n_gaps), dtype=torch.int32, device=dev)
+        # round-2 rows per gap, then their offsets (the pool_off of the round-2 assembly)
+        self.d_r2rows_all = torch.zeros(2 * (self.n_gaps + 1), dtype=torch.int64, device=dev)
+        self.d_r2rows, self.d_r2off = self.d_r2rows_all[:self.n_gaps + 1], self.d_r2rows_all[self.n_gaps + 1:]
+        self.r2_log2, self.r2_key_cap, self.r2_pool_cap = 12, 4096, 4096
+        self.r2_ctg_cap, self.r2_seq_cap = self._r2_caps(0)
+        self._r2_alloc()
+        big = int(self.max_pool_rows)
+        for attempt in range(8):
+            torch.cuda.synchronize()
+            self._on_stream(lambda: self._step(recruited=True))
+            self.sync()
+            torch.cuda.synchronize()
+            st = self.d_r2st.cpu().numpy().view(np.uint32)
+            a1, a2 = self.d_acnt.cpu().numpy(), self.d_acnt2.cpu().numpy()
+            n2, s2 = int(a2[0]), int(a2[2:4].view(np.uint64)[0])
+            rows = int(st[B.R2_ROWS:B.R2_ROWS + 2].view(np.uint64)[0])
+            grown = False
+            need_log2 = max(12, int(2 * int(st[B.R2_KMERS]) + 16).bit_length())
+            if need_log2 > self.r2_log2 or int(st[B.R2_TAB_FULL]):
+                self.r2_log2, grown = max(need_log2, self.r2_log2 + 1), True
+            if int(st[B.R2_HITS]) > self.r2_key_cap:
+                self.r2_key_cap, grown = int(1.25 * int(st[B.R2_HITS])) + 4096, True
+            if rows > self.r2_pool_cap:
+                self.r2_pool_cap, grown = int(1.25 * rows) + 4096, True
+            if n2 > self.r2_ctg_cap or s2 > self.r2_seq_cap:
+                c2, q2 = self._r2_caps(rows)
+                self.r2_ctg_cap, self.r2_seq_cap, grown = max(c2, int(1.25 * n2)), max(q2, int(1.25 * s2)), True
+            # the step's list holds both rounds' contigs
+            n1, q1 = int(st[B.R2_FIRST]), int(a1[2:4].view(np.uint64)[0]) - (0 if int(st[B.R2_APPEND_ERR]) else s2)
+            if n1 + n2 > self.contig_cap or q1 + s2 > self.seq_cap:
+                self.contig_cap, self.seq_cap = max(self.contig_cap, int(1.25 * (n1 + n2)) + 4096), max(self.seq_cap, int(1.25 * (q1 + s2)) + (1 << 20))
+                self.d_ctg, self.d_seq = self._u8(self.contig_cap * 32), self._u8(self.seq_cap)
+                if self.anchor_mode == "align":
+                    self.d_ctg_pick = self._u8(self.contig_cap * B.CTG_PICK.itemsize)
+                grown = True
+            # the assembly's workspace bounds cover the round-2 pools too (a pool beyond asm_big_pool_reads would set its gap error)
+            sizes = self.d_r2rows[:self.n_gaps].cpu().numpy()
+            deep = int(sizes.max()) if len(sizes) else 0
+            if deep > big:
+                big = deep
+                bound = big if big <= 4096 else max(4096, self.asm_bound, int(np.percentile(sizes[sizes > 0], 99)))
+                self.gf.set_option("asm_max_pool_reads", max(1, bound))
+                self.gf.set_option("asm_big_pool_reads", max(1, min(0x1FFFFF, big)))
+                grown = True
+            if not grown:
+                break
+            self._r2_alloc()
+        else:
+            raise RuntimeError("second round: the buffers keep growing")
+        torch.cuda.synchronize()
+
+    def _round2(self):
+        """Enqueued right after the first pick: recruitment, round-2 pools, assembly, append, pick over the round-2 contigs."""
+        lib, h, n_gaps, k = self.lib, self.h, self.n_gaps, self.k_round2
+        st = self.d_r2st.data_ptr()
+        self._chk(lib.gf_memset_dev(h, st, 0, 4 * B.R2_WORDS) or lib.gf_memset_dev(h, self.d_r2keys.data_ptr(), 0xFF, 8 * self.r2_key_cap),
+                  "gf_memset_dev")
+        self._chk(lib.gf_contig_kmer_table_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), self.d_best.data_ptr(), n_gaps,
+                                               k, self.d_r2tab.data_ptr(), self.r2_log2, st), "gf_contig_kmer_table_dev")
+        for l, lb in enumerate(self.libs):
+            self._chk(lib.gf_recruit_by_contigs_dev(h, lb.d_reads.data_ptr(), lb.d_nmask.data_ptr() if lb.d_nmask is not None else None, lb.n_reads,
+                                                    self.L, lb.d_r2pairs.data_ptr(), lb.d_r2n.data_ptr(), lb.r2_cap, l, k, self.d_r2tab.data_ptr(),
+                                                    self.r2_log2, self.d_r2keys.data_ptr(), self.r2_key_cap, st), "gf_recruit_by_contigs_dev")
+        self._chk(lib.gf_round2_pools_dev(h, self.d_r2keys.data_ptr(), self.d_r2sorted.data_ptr(), self.r2_key_cap, self.r2_lib_ptrs, len(self.libs), self.L,
+                                          self.asm_ptr, self.asm_off, self.d_best.data_ptr(), n_gaps, self.d_r2work.data_ptr(),
+                                          self.d_r2rows_all.data_ptr(), self.d_r2pool.data_ptr(), self.r2_pool_cap, st), "gf_round2_pools_dev")
+        ap2 = self.d_acnt2.data_ptr()
+        self._chk(lib.gf_assemble_multi_dev(h, self.d_r2pool.data_ptr(), None, self.d_r2off.data_ptr(), n_gaps, self.r2_pool_cap, self.L, self.k_arr,
+                                            self.kv_arr, len(self.kk), self.min_count, self.min_contig, self.d_ctg2.data_ptr(), self.r2_ctg_cap, ap2,
+                                            self.d_seq2.data_ptr(), self.r2_seq_cap, ap2 + 8, self.d_gap_err2.data_ptr()), "gf_assemble_multi_dev (round 2)")
+        self._chk(lib.gf_contigs_append_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), self.ap + 8, self.seq_cap,
+                                            self.d_ctg2.data_ptr(), ap2, self.r2_ctg_cap, self.d_seq2.data_ptr(), ap2 + 8, self.r2_seq_cap, st),
+                  "gf_contigs_append_dev")
+        first = st + 4 * B.R2_FIRST
+        a0, a1 = self.anchors[0], (self.anchors[1] if len(self.anchors) > 1 else 0)
+        if self.anchor_mode == "align":
+            self._chk(lib.gf_pick_aligned_from_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), a0, a1, first,
+                                                   self.d_best.data_ptr(), self.ap + 16, self.d_ctg_pick.data_ptr(), self.d_pstats.data_ptr()),
+                      "gf_pick_aligned_from_dev")
+        else:
+            self._chk(lib.gf_pick_anchored2_from_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), a0, a1, first,
+                                                     self.d_best.data_ptr(), self.ap + 16), "gf_pick_anchored2_from_dev")
 
     def _check_cap(self, n, cap, what, lb):
         if n > cap:
@@ -502,6 +647,8 @@ class Pipeline:
                 self._chk(lib.gf_pick_anchored2_from_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), a0, a1,
                                                          self.d_mstats.data_ptr() + 4 * B.MG_N0, self.d_best.data_ptr(), self.ap + 16),
                           "gf_pick_anchored2_from_dev")
+        if self.second_round:
+            self._round2()
 
     def step(self, n=1):
         assert self.prepared, "Pipeline.prepare() first"
@@ -568,10 +715,42 @@ class Pipeline:
         if r.merge is not None:      # gaps whose winning contig is a merged one
             idx = 0x7FFFFFFF - ((r.best >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64)
             r.merge["gaps_closed_by_merging"] = int(((r.best != 0) & (idx >= r.merge["contigs_before"])).sum())
+        r.round2, r.round2_first, r.round2_reads = None, None, None
+        if self.second_round and self.kk:
+            self._fetch_round2(r)
         if pools:
             r.pool_off = r.asm_off_t.cpu().numpy().astype(np.int64)
             r.pool_rows = r.asm_pool_t[:r.asm_rows_total * self.rb].cpu().numpy().reshape(-1, self.rb)
         return r
+
+    def _fetch_round2(self, r):
+        st = self.d_r2st.cpu().numpy().view(np.uint32)
+        a2 = self.d_acnt2.cpu().numpy()
+        n2, s2 = int(a2[0]), int(a2[2:4].view(np.uint64)[0])
+        n_err = int(self.d_gap_err2.sum())
+        if n_err or int(st[B.R2_APPEND_ERR]) or n2 > self.r2_ctg_cap or s2 > self.r2_seq_cap:
+            raise RuntimeError("second round overflow: %d gap errors, append flag %d, %d contigs (cap %d), %d contig bases (cap %d)"
+                               % (n_err, int(st[B.R2_APPEND_ERR]), n2, self.r2_ctg_cap, s2, self.r2_seq_cap))
+        first = int(st[B.R2_FIRST])
+        n_keys = min(int(st[B.R2_HITS]), self.r2_key_cap)
+        cand = [int(lb.d_r2n[0]) for lb in self.libs]
+        # recruits the round could not take: table entries without room, keys beyond their buffer, candidates beyond theirs, pools beyond theirs
+        dropped = (int(st[B.R2_TAB_FULL]) + max(0, int(st[B.R2_HITS]) - self.r2_key_cap) + sum(max(0, c - lb.r2_cap) for c, lb in zip(cand, self.libs))
+                   + (2 * int(st[B.R2_UNIQUE]) if int(st[B.R2_POOL_OVF]) else 0))
+        idx = 0x7FFFFFFF - ((r.best >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64)
+        r.round2_first = first
+        r.round2 = {"gaps_tried": int(st[B.R2_TRIED]), "gaps_with_recruits": int(st[B.R2_WITH]), "reads_recruited": 2 * int(st[B.R2_UNIQUE]),
+                    "contigs": int(st[B.R2_N2]), "gaps_closed": int(((r.best != 0) & (idx >= first)).sum()), "dropped": int(dropped),
+                    "candidates": 2 * sum(cand)}
+        if self.keep_read_ids:      # per gap with recruits: [(library, read id)] in round-2 pool order
+            keys = np.unique(self.d_r2sorted[:n_keys].cpu().numpy().view(np.uint64))
+            keys = keys[keys != np.uint64(0xFFFFFFFFFFFFFFFF)]
+            gap, libi, pair = (keys >> np.uint64(40)).astype(np.int64), ((keys >> np.uint64(36)) & np.uint64(15)).astype(np.int64), \
+                (keys & np.uint64((1 << 36) - 1)).astype(np.int64)
+            out = {}
+            for g, l, p in zip(gap.tolist(), libi.tolist(), pair.tolist()):
+                out.setdefault(g, []).extend([(l, 2 * p), (l, 2 * p + 1)])
+            r.round2_reads = out
 
     def merge_open_gaps(self, res, max_set=128):
         """The reference merges a gap's contigs BEFORE it picks (assemble_gaps.py:301-306, 335-339: run_contigs_merge, then

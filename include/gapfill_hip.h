@@ -565,6 +565,41 @@ int gf_merge_open_gaps_dev(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size
 int gf_pick_anchored2_from_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
                                int anchor_len, int anchor_len_short, const void* d_first, void* d_gap_best, void* d_n_closed);
 
+/* ---- the second assembly round inside the step (assemble_gaps.py:328-368 with collect_both_unmapped_reads.py's recruitment; DESIGN.md
+ * "Second round").  Predicate (the CLI's kmer_recruit_unmapped): a both-unmapped pair is recruited for an open gap when one of its reads shares
+ * a canonical k-mer with one of the gap's round-1 contigs; k-mers touching a non-ACGT contig base or an N-masked read base do not count.
+ * Every count below is exact whatever the capacities: a caller sizes from them and runs again (Pipeline.prepare). */
+#define GF_R2_MAX_LIBS 16
+/* candidate pairs of one library: every pair one of whose records has FLAG & 12 == 12 (`samtools view -f 12`), listed once (u32 pair ids,
+ * unordered); d_pair_bits: (n_reads / 2 + 31) / 32 u32 words of scratch; *d_n_pairs (u32) = candidates found (beyond cap: not stored). */
+int gf_both_unmapped_reads_dev(gf_ctx* ctx, const void* d_recs, size_t n_recs, size_t n_reads, void* d_pair_bits, void* d_pairs, size_t cap,
+                               void* d_n_pairs);
+/* the (canonical k-mer, gap) table of the contigs [0, *d_n_contigs) whose gap has d_gap_best == 0: 24-byte slots, 2^log2_slots of them
+ * (cleared by the call).  d_stats: u32[16] (zeroed by the caller before the round): [0] k-mer positions (size the table at least twice
+ * that), [1] entries without room. */
+int gf_contig_kmer_table_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, const void* d_gap_best,
+                             size_t n_gaps, int k, void* d_table, int log2_slots, void* d_stats);
+/* both reads of every candidate pair against the table: keys gap << 40 | lib << 36 | pair appended to d_keys (fill it with 0xFF before the
+ * round; the same (gap, pair) may appear more than once); d_stats[2] = keys emitted. */
+int gf_recruit_by_contigs_dev(gf_ctx* ctx, const void* d_reads, const void* d_nmask_or_null, size_t n_reads, int read_len, const void* d_pairs,
+                              const void* d_n_pairs, size_t pair_cap, int lib, int k, const void* d_table, int log2_slots, void* d_keys,
+                              size_t key_cap, void* d_stats);
+/* u32 words of gf_round2_pools_dev's d_work */
+size_t gf_round2_work_words(size_t key_cap, size_t n_gaps);
+/* the round-2 pools: per gap with recruits its round-1 rows (d_asm_pool / d_asm_off, as they went to the assembly) followed by the recruited
+ * pairs' reads in (library, read id) order, each pair once; other gaps get empty pools.  d_lib_reads: n_lib device pointers (host array).
+ * d_rows: u64[2 * (n_gaps + 1)], the pool offsets in its second half (the d_pool_off of gf_assemble_multi_dev).  d_stats: [3] distinct
+ * recruited pairs, [4] gaps with d_gap_best == 0, [5] gaps with recruits, [6-7] u64 rows, [11] 1 when the rows exceed pool_cap (every pool
+ * is then left empty). */
+int gf_round2_pools_dev(gf_ctx* ctx, void* d_keys, void* d_keys_sorted, size_t key_cap, const void* const* d_lib_reads, int n_lib, int read_len,
+                        const void* d_asm_pool, const void* d_asm_off, const void* d_gap_best, size_t n_gaps, void* d_work, void* d_rows,
+                        void* d_pool, size_t pool_cap, void* d_stats);
+/* the contigs of a second list appended to the first (seq_off moved); d_stats[8] = the first appended index, [10] contigs appended, [9] = 1
+ * when they do not fit (nothing appended).  Follow with gf_pick_*_from_dev(d_first = d_stats + 8). */
+int gf_contigs_append_dev(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t contig_cap, void* d_seq, void* d_seq_len, size_t seq_cap,
+                          const void* d_src_contigs, const void* d_src_n, size_t src_cap, const void* d_src_seq, const void* d_src_seq_len,
+                          size_t src_seq_cap, void* d_stats);
+
 /* ---- the reference's rescue round (assemble_gaps.py:166-217 run_collect_high_quality_unmap_to_contig_reads: `bwa mem` of a gap's high-quality
  * reads against its merged contigs, reads that align CLIPPED to at least two contigs are bridges), for ALL gaps of a round in one host call (no GPU
  * work; ctx may be NULL).  Contigs of gap g = texts [ctg_set_off[g], ctg_set_off[g+1]) of ctg_text (text c at ctg_off[c] .. ctg_off[c+1]), reads
