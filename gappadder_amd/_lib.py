@@ -22,11 +22,15 @@ SYNTH_CFG = np.dtype([("seed", "<u8"), ("scaffold_len", "<u8"), ("n_scaffolds", 
                       ("library", "<u4"), ("repeats", "<u4")])
 CTG_PICK = np.dtype([("lp", "<u4"), ("rp", "<u4"), ("lm", "<u2"), ("rm", "<u2"), ("reverse", "u1"), ("threshold", "u1"), ("reserved", "<u2")])
 QCPAIR = np.dtype([("set", "<u4"), ("i", "<u4"), ("j", "<u4")])
+# the extended fill's record per gap (gf_ext_pick): contig per side (EXT_NONE: none), the slices of the two parts, the fill's place
+EXT_PICK = np.dtype([("left", "<u4"), ("right", "<u4"), ("l_beg", "<u4"), ("l_len", "<u4"), ("r_beg", "<u4"), ("r_len", "<u4"), ("off", "<u8"),
+                     ("len", "<u4"), ("l_rev", "u1"), ("r_rev", "u1"), ("reserved", "<u2")])
+EXT_NONE = 0xFFFFFFFF
 OVL_PARAMS = np.dtype([("mismatch", "<f8"), ("indel", "<f8"), ("max_clip", "<f8"), ("frac_min_overlap", "<f8"), ("frac_loss", "<f8"),
                        ("min_overlap", "<f8"), ("min_overlap_scaffold", "<f8"), ("relax", "<f8")])
 OVL_RESULT = np.dtype([(n, "<i4") for n in ("res", "row_end", "col_end", "nclip", "score", "contained", "merged_len", "overlap",
                                             "containment", "first_goes_first")])
-assert CONTIG.itemsize == 32 and GAP.itemsize == 16 and ALNREC.itemsize == 32 and TAGHIT.itemsize == 12 and DPOS.itemsize == 16 and HIT.itemsize == 8
+assert CONTIG.itemsize == 32 and EXT_PICK.itemsize == 40 and GAP.itemsize == 16 and ALNREC.itemsize == 32 and TAGHIT.itemsize == 12 and DPOS.itemsize == 16 and HIT.itemsize == 8
 
 GF_OK, GF_E_INVAL, GF_E_NODEV, GF_E_NOMEM, GF_E_NOSPACE, GF_E_STATE, GF_E_UNSUPPORTED, GF_E_FORMAT = 0, -1, -2, -3, -4, -5, -6, -7
 KIND_CLIP, KIND_DISCORDANT, KIND_UNMAP, KIND_LOWMAPQ = 0, 1, 2, 3
@@ -41,6 +45,10 @@ MG_WORDS = 32
 # words of the second round's statistics (round2.hip, u32[16])
 R2_KMERS, R2_TAB_FULL, R2_HITS, R2_UNIQUE, R2_TRIED, R2_WITH, R2_ROWS, R2_FIRST, R2_APPEND_ERR, R2_N2, R2_POOL_OVF = 0, 1, 2, 3, 4, 5, 6, 8, 9, 10, 11
 R2_WORDS, R2_MAX_LIBS = 16, 16
+
+# words of the extended fill's statistics (gf_pick_extended_dev, u32[12]): fills (left only, right only, both sides), u64 bases, overflow flag
+EXT_EXTENDED, EXT_LEFT_ONLY, EXT_RIGHT_ONLY, EXT_BOTH, EXT_BASES, EXT_OVERFLOW, EXT_ALIGN_DROPPED, EXT_ALIGN_SEED_OVERFLOW = 0, 1, 2, 3, 4, 6, 8, 9
+EXT_WORDS, EXT_MAX_PAIRS = 12, 32
 
 _lib = None
 
@@ -137,6 +145,8 @@ def lib():
         "gf_recruit_by_contigs_dev": (i32, [vp, vp, vp, sz, i32, vp, vp, sz, i32, i32, vp, i32, vp, sz, vp]),
         "gf_round2_work_words": (sz, [sz, sz]),
         "gf_round2_pools_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, vp, vp, vp, sz, vp, vp, vp, sz, vp]),
+        "gf_pick_extended_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
+        "gf_pick_extended_aligned_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_contigs_append_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp]),
         "gf_count_kmers": (i32, [vp, vp, vp, sz, i32, i32, i32, vp, vp, sz, szp]),
         "gf_pool_keys_reset": (i32, [vp, vp]),

@@ -61,6 +61,17 @@ struct DevBuf {
     size_t bytes = 0;
 };
 
+// the extended fill (pick_ext.hip): per contig of an open gap its wanted hit on each side (pos 1-based, m bases, strand) and the link to the
+// next contig of the gap with a hit on that side (lists headed per gap and side, EMPTY32 ends them)
+struct ExtHit {
+    uint32_t pos[2];
+    uint32_t next[2];
+    uint16_t m[2];     // 0: no hit on that side
+    uint8_t rev[2];
+    uint16_t pad;
+};
+static_assert(sizeof(ExtHit) == 24, "ExtHit");
+
 struct TimedLaunch {
     hipEvent_t a, b;
     int which;
@@ -133,7 +144,7 @@ struct gf_ctx {
     size_t low_b1 = 0, low_b2 = 0;
 
     // scratch
-    gf::DevBuf cand, cand2, part_ws, tag_stage, verify_stage, bam_stream, bam_recs, asm_table, asm_surv, asm_nodes, asm_jump, asm_big, rowgap, pool_ws, xchg_ws, xchg_ws2, merge_ws, counters, stage_in, stage_out, stage_aux, table, r2_tmp;
+    gf::DevBuf cand, cand2, part_ws, tag_stage, verify_stage, bam_stream, bam_recs, asm_table, asm_surv, asm_nodes, asm_jump, asm_big, rowgap, pool_ws, xchg_ws, xchg_ws2, merge_ws, counters, stage_in, stage_out, stage_aux, table, r2_tmp, ext_ws;
     size_t bam_n_recs = 0;       // alignment records gf_bam_pack left in bam_recs (for gf_tag_*_bam)
     size_t bam_stream_len = 0;   // inflated BAM bytes gf_bgzf_inflate left in bam_stream
     // timing
@@ -181,6 +192,11 @@ struct ZeroList {
     uint32_t n[4];   // 32-bit words
 };
 void zero_regions(gf_ctx* ctx, const ZeroList& z);
+
+// pick.hip: the exact anchors of one length (built once per gf_set_gaps); pick_align.hip: the align-mode hits of the extended fill
+int anchor_table_for(gf_ctx* ctx, int anchor_len, const uint8_t** out);
+int launch_align_ext(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t, const void* d_first,
+                     const void* d_gap_best, ExtHit* hits, uint32_t* heads, uint32_t* stats);
 
 // index.cpp
 int build_flank_index(gf_ctx* ctx, int k, FlankIndex** out);

@@ -224,3 +224,11 @@ int gf_pick_anchored_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_con
 }
 
 }  // extern "C"
+
+namespace gf {
+
+int anchor_table_for(gf_ctx* ctx, int anchor_len, const uint8_t** out) {   // (pick_ext.hip)
+    return anchor_table(ctx, anchor_len, out);
+}
+
+}  // namespace gf

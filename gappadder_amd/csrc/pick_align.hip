@@ -44,6 +44,8 @@ struct AlignParams {
     gf_ctg_pick* ctg_pick;
     uint32_t* stats;           // [0] alignments beyond the cap, [1] contigs with more than AL_SEED_MAX seeds
     const uint32_t* first;     // or null
+    ExtHit* ext_hits;          // the extended fill (pick_ext.hip): per contig its wanted hit per side, pushed on ...
+    uint32_t* ext_heads;       // ... the lists of its gap (t_long = the threshold; gap_best is read, not written)
 };
 
 struct AlHit {
@@ -106,7 +108,11 @@ __device__ bool al_select(const AlHit* left, const AlHit* right, uint32_t* lp, u
     return *span >= 0;
 }
 
-__global__ __launch_bounds__(64) void pick_align_kernel(AlignParams P) {
+// EXT: the hits of the extended fill instead of the pick: per contig of an open gap and side the FIRST hit in align_hits' order (score
+// descending, forward before reverse, pos ascending; production order on full ties) whose clip type is the wanted one — the flank clipped
+// on its far side: LEFT for the left flank forward and rc(right flank), RIGHT for rc(left flank) and the right flank forward
+template <bool EXT>
+__device__ __forceinline__ void pick_align_body(const AlignParams& P) {
     __shared__ unsigned long long keys[AL_SEED_MAX];   // seeds as found, then the extension results in rank order
     __shared__ unsigned long long srt[AL_SEED_MAX];    // seeds in (query, diagonal, query start) order
     __shared__ uint32_t cnt;
@@ -116,6 +122,7 @@ __global__ __launch_bounds__(64) void pick_align_kernel(AlignParams P) {
     for (uint32_t ci = (P.first ? *P.first : 0u) + blockIdx.x; ci < n_ctg; ci += gridDim.x) {
         const gf_contig c = P.contigs[ci];
         if (c.gap >= P.n_gaps || c.length < (uint32_t)AL_SEED) continue;        // (uniform over the workgroup)
+        if (EXT && P.gap_best[c.gap]) continue;
         const AlignMeta M = P.meta[c.gap];
         if (!M.kn) continue;
         const char* s = P.seq + c.seq_off;
@@ -177,9 +184,11 @@ __global__ __launch_bounds__(64) void pick_align_kernel(AlignParams P) {
         }
         __syncthreads();
         if (lane == 0) {
-            for (int t = 0; t < 2; ++t)
-                for (int sd = 0; sd < 2; ++sd)
-                    for (int ct = 0; ct < 3; ++ct) tab[t][sd][ct] = AlHit{0, 0, 0, 0};
+            AlHit fh_l{0, 0, 0, 0}, fh_r{0, 0, 0, 0};                        // (EXT: two register sets, not an indexed array: no scratch)
+            if (!EXT)
+                for (int t = 0; t < 2; ++t)
+                    for (int sd = 0; sd < 2; ++sd)
+                        for (int ct = 0; ct < 3; ++ct) tab[t][sd][ct] = AlHit{0, 0, 0, 0};
             uint32_t produced[4] = {0, 0, 0, 0}, drops = 0;
             unsigned long long last = ~0ull;
             int max_qe = -1;
@@ -199,6 +208,15 @@ __global__ __launch_bounds__(64) void pick_align_kernel(AlignParams P) {
                 const int ct = cl ? CT_LEFT : cr ? CT_RIGHT : CT_NONE;
                 const int d = (int)((k >> 11) & ((1ull << 51) - 1)) - AL_FLANK_MAX;
                 const AlHit h{(uint32_t)(qe - qb), score, qi & 1u, (uint32_t)(d + qb + 1)};
+                if (EXT) {
+                    if (score < P.t_long || ct != ((qi == 0 || qi == 3) ? CT_LEFT : CT_RIGHT)) continue;
+                    auto first = [&h](const AlHit& o) {
+                        return !o.m || h.score > o.score || (h.score == o.score && (h.rev < o.rev || (h.rev == o.rev && h.pos < o.pos)));
+                    };
+                    if (qi >> 1) { if (first(fh_r)) fh_r = h; }
+                    else if (first(fh_l)) fh_l = h;
+                    continue;
+                }
                 for (int t = 0; t < 2; ++t) {
                     const uint32_t T = t == 0 ? P.t_long : P.t_short;
                     if (!T || score < T) continue;
@@ -210,9 +228,25 @@ __global__ __launch_bounds__(64) void pick_align_kernel(AlignParams P) {
                 }
             }
             if (drops) atomicAdd(P.stats, drops);
+            if (EXT) {
+                if (fh_l.m || fh_r.m) {
+                    ExtHit eh;
+                    eh.pad = 0;
+#pragma unroll
+                    for (int sd = 0; sd < 2; ++sd) {
+                        const AlHit o = sd ? fh_r : fh_l;
+                        eh.m[sd] = (uint16_t)o.m;
+                        eh.rev[sd] = (uint8_t)o.rev;
+                        eh.pos[sd] = o.pos;
+                        eh.next[sd] = o.m ? atomicExch(P.ext_heads + 2 * c.gap + sd, ci) : EMPTY32;
+                    }
+                    P.ext_hits[ci] = eh;
+                }
+            }
             uint32_t lp = 0, rp = 0, lm = 0, rm = 0, rc = 0, T = 0;
             int span = -1;
-            if (al_select(tab[0][0], tab[0][1], &lp, &rp, &lm, &rm, &rc, &span)) T = P.t_long;
+            if (EXT) T = 0;
+            else if (al_select(tab[0][0], tab[0][1], &lp, &rp, &lm, &rm, &rc, &span)) T = P.t_long;
             else if (P.t_short && al_select(tab[1][0], tab[1][1], &lp, &rp, &lm, &rm, &rc, &span)) T = P.t_short;
             if (T) {
                 gf_ctg_pick* cp = P.ctg_pick + ci;
@@ -233,6 +267,10 @@ __global__ __launch_bounds__(64) void pick_align_kernel(AlignParams P) {
         __syncthreads();
     }
 }
+
+__global__ __launch_bounds__(64) void pick_align_kernel(AlignParams P) { pick_align_body<false>(P); }
+
+__global__ __launch_bounds__(64) void pick_align_ext_kernel(AlignParams P) { pick_align_body<true>(P); }
 
 }  // namespace gf
 
@@ -317,6 +355,8 @@ static int pick_aligned(gf_ctx* ctx, const void* d_contigs, const void* d_n_cont
     P.ctg_pick = (gf_ctg_pick*)d_ctg_pick;
     P.stats = (uint32_t*)d_stats;
     P.first = (const uint32_t*)d_first;
+    P.ext_hits = nullptr;
+    P.ext_heads = nullptr;
     LaunchTimer tm(ctx, GF_KERNEL_PICK);
     hipLaunchKernelGGL(pick_align_kernel, dim3(ctx->n_cu * 16), dim3(64), 0, ctx->stream, P);
     GF_HIP(ctx, hipGetLastError());
@@ -335,3 +375,29 @@ int gf_pick_aligned_from_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n
 }
 
 }  // extern "C"
+
+namespace gf {
+
+int launch_align_ext(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t, const void* d_first,
+                     const void* d_gap_best, ExtHit* hits, uint32_t* heads, uint32_t* stats) {   // (pick_ext.hip; the caller checked the arguments)
+    AlignParams P;
+    memset(&P, 0, sizeof(P));
+    int rc = align_tables(ctx, &P.meta, &P.qbytes, &P.kmers);
+    if (rc) return rc;
+    P.contigs = (const gf_contig*)d_contigs;
+    P.n_contigs = (const uint32_t*)d_n_contigs;
+    P.contig_cap = (uint32_t)contig_cap;
+    P.seq = (const char*)d_seq;
+    P.n_gaps = (uint32_t)ctx->gaps.size();
+    P.t_long = (uint32_t)t;
+    P.gap_best = (unsigned long long*)d_gap_best;
+    P.stats = stats;
+    P.first = (const uint32_t*)d_first;
+    P.ext_hits = hits;
+    P.ext_heads = heads;
+    hipLaunchKernelGGL(pick_align_ext_kernel, dim3(ctx->n_cu * 16), dim3(64), 0, ctx->stream, P);
+    GF_HIP(ctx, hipGetLastError());
+    return GF_OK;
+}
+
+}  // namespace gf

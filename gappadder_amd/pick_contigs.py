@@ -328,6 +328,40 @@ def pick_extended_sequence(contigs, left_flank, right_flank, anchor_len, mode="e
     return names[0], names[1], (out if out != "NN" else None), (text if text not in ("", "NN") else None)
 
 
+def extension_order(contigs, k_pairs):
+    """The contig order of the device step's extended fill (gf_pick_extended_dev): pick_extended_sequence takes the FIRST contig with
+    a hit per side, and the device lists a gap's contigs in no fixed order.  contigs: [(k, kv, bases)]; k_pairs: the pipeline's
+    [(k, kv)].  Returns the contig indices sorted by (position of (k, kv) in k_pairs — the merged contigs' (0, 0) and any pair not in
+    the list after every pair, as contigs.fa concatenates the per-pair files —, length descending, bases ascending, index)."""
+    rank = {}
+    for i, (k, kv) in enumerate(k_pairs):
+        rank.setdefault((int(k), int(kv)), i)
+    n = len(k_pairs)
+    return sorted(range(len(contigs)), key=lambda i: (rank.get((int(contigs[i][0]), int(contigs[i][1])), n), -len(contigs[i][2]),
+                                                      contigs[i][2], i))
+
+
+def decode_extended(rec, contig_seq):
+    """One gf_ext_pick record (fields left, right, l_beg, l_len, l_rev, r_beg, r_len, r_rev; 0xFFFFFFFF = no contig) -> the fields of
+    pick_extended_sequence with contig indices for names: (left contig or -1, right contig or -1, fill or None, picked_contigs text or
+    None), or None when neither side has a contig.  contig_seq(i) = the bases of contig i."""
+    none = 0xFFFFFFFF
+    left, right = int(rec["left"]), int(rec["right"])
+    if left == none and right == none:
+        return None
+    parts = []
+    for ci, beg, n, rev in ((left, rec["l_beg"], rec["l_len"], rec["l_rev"]), (right, rec["r_beg"], rec["r_len"], rec["r_rev"])):
+        s = contig_seq(ci)[int(beg):int(beg) + int(n)] if int(n) else ""
+        parts.append(revcomp(s) if int(rev) else s)
+    fill = parts[0] + "NN" + parts[1]
+    if left != none and left == right:
+        text = contig_seq(right)
+    else:
+        text = (contig_seq(left) if left != none else "") + ("NN" + contig_seq(right) if right != none else "")
+    return (left if left != none else -1, right if right != none else -1, fill if fill != "NN" else None,
+            text if text not in ("", "NN") else None)
+
+
 class ContigsSelection:
     def __init__(self, working_space, mode="exact"):
         """mode: how the flanks are anchored on the contigs, "exact" (anchor_hits) or "align" (align_hits)."""

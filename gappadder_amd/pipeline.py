@@ -19,6 +19,7 @@ What the reference does with files between processes —
     gf_contig_kmer_table_dev + gf_recruit_by_contigs_dev       second assembly round for the gaps still open (second_round):
       + gf_round2_pools_dev + gf_assemble_multi_dev            both-unmapped pairs recruited by the round-1 contigs' k-mers, pools
       + gf_contigs_append_dev + gf_pick_*_from_dev             = round-1 rows + recruits, assembled and picked again
+    gf_pick_extended[_aligned]_dev                             partial fills of the gaps every pick left open (extended_fill)
 
 `Pipeline` owns the sizing pass (capacities follow what the libraries actually recruit), every intermediate buffer, the stream
 wiring and — in a multi-rank run — the one exchange step.  Two callers: bench.py (libraries synthesised on the
@@ -67,7 +68,8 @@ class Results:
 class Pipeline:
     def __init__(self, gf, n_gaps, read_len, k_pairs, device=None, world=1, rank=0, backend="nccl", force_exchange=False,
                  min_count=2, min_contig=40, anchors=(30, 15), clip_dist=250, anchor_mapq=30, k_screen=None, keep_read_ids=False,
-                 key_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False):
+                 key_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False,
+                 extended_fill=False, ext_base_cap=None):
         """gf: a GapFill whose gaps (and flanks, when a library is screened) are set.  k_pairs: [(k, k_velvet)] of
         assemble_gaps.py:87-122.  The screen runs at the SMALLEST k of the list: a read that shares a 51-mer with a flank shares
         its 31-mers too, so this is the superset every assembly k needs (the reference recruits once, then assembles at every k).
@@ -84,7 +86,13 @@ class Pipeline:
         16..64) with a gap's round-1 contigs are appended to its pool, the gap is assembled again at every (k, kv) and picked over the
         round-2 contigs only (appended after round 1's; Results.round2 / round2_first).  Single rank, without merge_in_step.
         The candidate pairs are listed from the libraries' alignment records once, in prepare(): like the key column, they assume the
-        records do not change after prepare() (a caller that rewrites d_recs prepares a new Pipeline)."""
+        records do not change after prepare() (a caller that rewrites d_recs prepares a new Pipeline).
+        extended_fill: the reference's last stage (pick_extended_contigs, assemble_gaps.py:367-368) after the last pick of the step: every
+        gap still open is filled from each side as far as a contig reaches, the parts joined by "NN" (gf_pick_extended_dev; the shorter
+        anchor, anchors[-1], in anchor_mode; over the round-2 contigs with second_round, else over all of the step's contigs).  Results.ext
+        (gf_ext_pick per gap), .ext_bases and .extended (counts); Pipeline.extended_sequences decodes them.  Single rank.  ext_base_cap:
+        bytes of the fill buffer (default: the contig bases' capacity + 2 per gap, which no fill set can exceed); fetch() raises when
+        the fills do not fit."""
         if anchor_mode not in ("exact", "align"):
             raise ValueError("anchor_mode %r: 'exact' or 'align'" % (anchor_mode,))
         self.second_round = bool(second_round)
@@ -98,6 +106,13 @@ class Pipeline:
                 raise ValueError("second_round needs a k in 16..64 among k_pairs")
             self.k_round2 = min(ks)
         self.anchor_mode = anchor_mode
+        self.extended_fill = bool(extended_fill)
+        if self.extended_fill:
+            if int(world) > 1 or force_exchange:
+                raise ValueError("extended_fill runs on a single rank")
+            if len(k_pairs) > B.EXT_MAX_PAIRS:
+                raise ValueError("extended_fill: at most %d (k, kv) pairs" % B.EXT_MAX_PAIRS)
+        self.ext_base_cap_arg = int(ext_base_cap) if ext_base_cap is not None else None
         self.gf, self.lib, self.h = gf, B.lib(), gf.handle
         self.n_gaps, self.L, self.kk = int(n_gaps), int(read_len), [(int(a), int(b)) for a, b in k_pairs]
         self.rb = self.lib.gf_packed_read_bytes(self.L)
@@ -420,14 +435,36 @@ class Pipeline:
         self.merge_params = pr
         self.k_arr = (C.c_int * nk)(*[a for a, _ in self.kk])
         self.kv_arr = (C.c_int * nk)(*[b for _, b in self.kk])
+        if self.extended_fill:
+            self._ext_alloc()
         torch.cuda.synchronize()
         if self.second_round:
             self._prepare_round2()
+            if self.extended_fill:
+                self._ext_alloc()       # (the round may have grown the contig buffers)
         if self.tag_ahead:          # the first step's tagger pass (untimed, like a warm-up step's)
             assert all(lb.second_stream for lb in self.libs), "tag_ahead needs DeviceLibrary(tag_ctx=...)"
             self._on_stream(lambda: [self.tagger(lb) for lb in self.libs])
             self.sync()
         self.prepared = True
+
+    def _ext_alloc(self):
+        cap = self.ext_base_cap_arg if self.ext_base_cap_arg is not None else self.seq_cap + 2 * self.n_gaps
+        if getattr(self, "ext_base_cap", None) == cap:
+            return
+        self.ext_base_cap = cap
+        self.d_ext = self._u8(self.n_gaps * B.EXT_PICK.itemsize)
+        self.d_ext_bases = self._u8(cap)
+        self.d_ext_stats = torch.zeros(B.EXT_WORDS, dtype=torch.int32, device=self.dev)
+
+    def _extend(self):
+        """Enqueued after the last pick of the step: the partial fills of the gaps d_best leaves open."""
+        first = self.d_r2st.data_ptr() + 4 * B.R2_FIRST if self.second_round else None
+        fn, what = ((self.lib.gf_pick_extended_aligned_dev, "gf_pick_extended_aligned_dev") if self.anchor_mode == "align"
+                    else (self.lib.gf_pick_extended_dev, "gf_pick_extended_dev"))
+        self._chk(fn(self.h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), self.anchors[-1], self.k_arr, self.kv_arr,
+                     len(self.kk), first, self.d_best.data_ptr(), self.d_ext.data_ptr(), self.d_ext_bases.data_ptr(), self.ext_base_cap,
+                     self.d_ext_stats.data_ptr()), what)
 
     # ---- second assembly round: sizing (untimed) ---------------------------------------------------------------------------
     def _r2_caps(self, rows):
@@ -649,6 +686,8 @@ class Pipeline:
                           "gf_pick_anchored2_from_dev")
         if self.second_round:
             self._round2()
+        if self.extended_fill:
+            self._extend()
 
     def step(self, n=1):
         assert self.prepared, "Pipeline.prepare() first"
@@ -718,6 +757,9 @@ class Pipeline:
         r.round2, r.round2_first, r.round2_reads = None, None, None
         if self.second_round and self.kk:
             self._fetch_round2(r)
+        r.extended, r.ext, r.ext_bases = None, None, None
+        if self.extended_fill and self.kk:
+            self._fetch_extended(r)
         if pools:
             r.pool_off = r.asm_off_t.cpu().numpy().astype(np.int64)
             r.pool_rows = r.asm_pool_t[:r.asm_rows_total * self.rb].cpu().numpy().reshape(-1, self.rb)
@@ -751,6 +793,40 @@ class Pipeline:
             for g, l, p in zip(gap.tolist(), libi.tolist(), pair.tolist()):
                 out.setdefault(g, []).extend([(l, 2 * p), (l, 2 * p + 1)])
             r.round2_reads = out
+
+    def _fetch_extended(self, r):
+        st = self.d_ext_stats.cpu().numpy().view(np.uint32)
+        total = int(st[B.EXT_BASES]) | (int(st[B.EXT_BASES + 1]) << 32)
+        if int(st[B.EXT_OVERFLOW]) or total > self.ext_base_cap:
+            raise RuntimeError("extended fill overflow: %d fill bases, buffer of %d (Pipeline(ext_base_cap=...))" % (total, self.ext_base_cap))
+        r.extended = {"gaps_extended": int(st[B.EXT_EXTENDED]), "left_only": int(st[B.EXT_LEFT_ONLY]), "right_only": int(st[B.EXT_RIGHT_ONLY]),
+                      "both_sides": int(st[B.EXT_BOTH]), "bases": total}
+        if self.anchor_mode == "align":
+            r.extended["align_dropped"], r.extended["align_seed_overflow"] = int(st[B.EXT_ALIGN_DROPPED]), int(st[B.EXT_ALIGN_SEED_OVERFLOW])
+        r.ext = np.frombuffer(self.d_ext[:self.n_gaps * B.EXT_PICK.itemsize].cpu().numpy().tobytes(), dtype=B.EXT_PICK)
+        r.ext_bases = self.d_ext_bases[:total].cpu().numpy().tobytes()
+
+    def extended_sequences(self, res):
+        """The partial fills of the last step (extended_fill): {gap: (left contig index or -1, right contig index or -1, fill or None,
+        picked_contigs text or None)} for every gap with a contig on either side — pick_extended_sequence's fields with contig indices for
+        names (pick_contigs.decode_extended); the fill is the device's, checked against its record's slices."""
+        from .pick_contigs import decode_extended
+        if res.ext is None:
+            raise ValueError("extended_sequences needs the Results of a Pipeline(extended_fill=True) step")
+        ctg, seq = res.contigs, res.seq
+
+        def contig_seq(i):
+            c = ctg[i]
+            return seq[int(c["seq_off"]):int(c["seq_off"]) + int(c["length"])].decode()
+        out = {}
+        for g in np.nonzero((res.ext["left"] != B.EXT_NONE) | (res.ext["right"] != B.EXT_NONE))[0]:
+            rec = res.ext[g]
+            d = decode_extended(rec, contig_seq)
+            dev = res.ext_bases[int(rec["off"]):int(rec["off"]) + int(rec["len"])].decode() if int(rec["len"]) else None
+            if dev != d[2]:
+                raise RuntimeError("gap %d: the device's fill does not match its record" % g)
+            out[int(g)] = d
+        return out
 
     def merge_open_gaps(self, res, max_set=128):
         """The reference merges a gap's contigs BEFORE it picks (assemble_gaps.py:301-306, 335-339: run_contigs_merge, then

@@ -565,6 +565,46 @@ int gf_merge_open_gaps_dev(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size
 int gf_pick_anchored2_from_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
                                int anchor_len, int anchor_len_short, const void* d_first, void* d_gap_best, void* d_n_closed);
 
+/* ---- partial fills of the gaps no pick closed (run_pick_extended_contig, pick_contigs.py:361-539, called at assemble_gaps.py:367-368
+ * with score 15; DESIGN.md "Extended fill").  Host twin: gappadder_amd/pick_contigs.py::pick_extended_sequence applied to a gap's
+ * contigs in the order of pick_contigs.extension_order.  For every gap with d_gap_best == 0, over its contigs from *d_first on
+ * (d_first NULL: from 0): per side the FIRST contig with a wanted (clipped) hit in the order (rank of the contig's (k, kv) among
+ * k_list / kv_list, a pair not in the list — the merged contigs' k = kv = 0 — after every pair; length descending; bases ascending;
+ * contig index), the same contig on both sides used on the right only, the parts sliced and oriented as the twin does and joined
+ * by "NN".  Exact mode: the hits of anchor_hits (the anchor_len-base anchors of gf_pick_anchored_dev, any contig of >= anchor_len
+ * bases); align mode: the first hit of align_hits' order with the wanted clip type (the hits of gf_pick_aligned_dev at threshold t).
+ * d_ext: n_gaps gf_ext_pick (written for every gap); d_bases: the fills back to back in gap order (capacity base_cap); d_stats:
+ * GF_EXT_WORDS u32, zeroed by the call.  Fills beyond base_cap are not written and set GF_EXT_OVERFLOW: the caller raises.  n_k <= 32.
+ * Align mode: flanks of more than 1 024 bases give GF_E_UNSUPPORTED (as gf_pick_aligned_dev). */
+#define GF_EXT_NONE 0xFFFFFFFFu
+#define GF_EXT_MAX_PAIRS 32
+typedef struct {
+    uint32_t left, right;    /* contig of each side (before the same-contig rule), GF_EXT_NONE: none */
+    uint32_t l_beg, l_len;   /* the left part: contig bases [l_beg, l_beg + l_len), reverse-complemented when l_rev */
+    uint32_t r_beg, r_len;   /* the right part, likewise */
+    uint64_t off;            /* the fill (left part + "NN" + right part) at d_bases + off ... */
+    uint32_t len;            /* ... of len bases; 0 = no fill (no hit, or nothing but "NN") */
+    uint8_t l_rev, r_rev;
+    uint16_t reserved;
+} gf_ext_pick;
+/* words of d_stats: gaps with a fill; of them: left side only, right side only, both sides; u64 fill bases (words 4-5); overflow flag;
+ * align mode: alignments beyond the cap and contigs beyond the seed limit (as gf_pick_aligned_dev's d_stats) */
+#define GF_EXT_EXTENDED 0
+#define GF_EXT_LEFT_ONLY 1
+#define GF_EXT_RIGHT_ONLY 2
+#define GF_EXT_BOTH 3
+#define GF_EXT_BASES 4
+#define GF_EXT_OVERFLOW 6
+#define GF_EXT_ALIGN_DROPPED 8
+#define GF_EXT_ALIGN_SEED_OVERFLOW 9
+#define GF_EXT_WORDS 12
+int gf_pick_extended_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int anchor_len,
+                         const int* k_list, const int* kv_list, int n_k, const void* d_first, const void* d_gap_best, void* d_ext,
+                         void* d_bases, size_t base_cap, void* d_stats);
+int gf_pick_extended_aligned_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t,
+                                 const int* k_list, const int* kv_list, int n_k, const void* d_first, const void* d_gap_best, void* d_ext,
+                                 void* d_bases, size_t base_cap, void* d_stats);
+
 /* ---- the second assembly round inside the step (assemble_gaps.py:328-368 with collect_both_unmapped_reads.py's recruitment; DESIGN.md
  * "Second round").  Predicate (the CLI's kmer_recruit_unmapped): a both-unmapped pair is recruited for an open gap when one of its reads shares
  * a canonical k-mer with one of the gap's round-1 contigs; k-mers touching a non-ACGT contig base or an N-masked read base do not count.
