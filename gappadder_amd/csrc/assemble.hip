@@ -1735,6 +1735,9 @@ __device__ __forceinline__ void assemble_body(const AsmParams& P, AsmShared<NT>&
                     ct.length = rec[4 * q + 1] + PKV - 1; ct.cov_sum = cacc_lds ? cacc[q] : __hip_atomic_load(&rec[4 * q + 3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // from L2, where the atomics landed
                     ct.reserved = 0;
                     ct.seq_off = s_seq[1] + rec[4 * q + 2];
+                    // bases beyond seq_cap were not written: a tombstone (length 0, seq_off 0) that every consumer skips, as the merge
+                    // round's; the counters still count the contig and its bases, so the host sees the overflow
+                    if (ct.seq_off + ct.length > P.seq_cap) { ct.length = 0; ct.seq_off = 0; }
                     P.contigs[ci] = ct;
                 }
             }

@@ -449,11 +449,21 @@ __device__ __forceinline__ uint32_t mg_block_scan_excl(uint32_t v, uint32_t* s_w
     return base + x - v;
 }
 
+// a list that overflowed before the round (the assembly's counters beyond the capacities): the round is a no-op that keeps the overflow
+// visible — no gap is counted, so no set takes part, stats[MG_ERR] says why, and *n_contigs / *seq_len stay beyond the caps
+__device__ __forceinline__ bool mg_list_overflowed(const MgParams& P) { return *P.n_contigs > P.contig_cap || *P.seq_len > P.seq_cap; }
+
+// tombstones (length 0: a record whose bases did not fit the buffer) take no part; mg_fill_kernel skips the same records
+__device__ __forceinline__ bool mg_takes_part(const MgParams& P, const gf_contig& c) {
+    return c.gap < P.n_gaps && c.length != 0 && P.gap_best[c.gap] == 0;
+}
+
 __global__ __launch_bounds__(256) void mg_count_kernel(MgParams P) {
+    if (mg_list_overflowed(P)) return;
     const uint32_t n = *P.n_contigs < P.contig_cap ? *P.n_contigs : P.contig_cap;
     for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n; c += gridDim.x * blockDim.x) {
-        const uint32_t g = P.contigs[c].gap;
-        if (g < P.n_gaps && P.gap_best[g] == 0) atomicAdd(&P.cnt[g], 1u);
+        const gf_contig ct = P.contigs[c];
+        if (mg_takes_part(P, ct)) atomicAdd(&P.cnt[ct.gap], 1u);
     }
 }
 
@@ -482,14 +492,17 @@ __global__ __launch_bounds__(1024) void mg_scan_gaps_kernel(MgParams P) {
         P.pre_off[carry_set] = carry_off;
         P.stats[MG_N_PRE] = carry_set;
         P.stats[MG_N0] = *P.n_contigs < P.contig_cap ? *P.n_contigs : P.contig_cap;
+        if (*P.n_contigs > P.contig_cap) atomicOr(&P.stats[MG_ERR], MG_E_CONTIGS);
+        if (*P.seq_len > P.seq_cap) atomicOr(&P.stats[MG_ERR], MG_E_OUTSEQ);
     }
 }
 
 __global__ __launch_bounds__(256) void mg_fill_kernel(MgParams P) {
     const uint32_t n = P.stats[MG_N0];
     for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n; c += gridDim.x * blockDim.x) {
-        const uint32_t g = P.contigs[c].gap;
-        if (g >= P.n_gaps) continue;
+        const gf_contig ct = P.contigs[c];
+        if (!mg_takes_part(P, ct)) continue;
+        const uint32_t g = ct.gap;
         const uint32_t pre = P.pre_of_gap[g];
         if (pre == EMPTY32) continue;
         P.ids[P.pre_off[pre] + atomicAdd(&P.cnt[g], 1u)] = c;
@@ -1016,7 +1029,7 @@ __global__ __launch_bounds__(1024) void mg_scan_jobs_kernel(MgParams P) {
         carry += tot;
         __syncthreads();
     }
-    if (threadIdx.x == 0) {
+    if (threadIdx.x == 0 && !mg_list_overflowed(P)) {     // (an overflow on entry: no sets, and the counter stays beyond the cap)
         if ((unsigned long long)n0 + carry > P.contig_cap) atomicOr(&P.stats[MG_ERR], MG_E_CONTIGS);
         *P.n_contigs = n0 + carry;       // (beyond the capacity: the caller's overflow test sees it; the records beyond are not written)
     }

@@ -316,7 +316,10 @@ int gf_assemble_dev(gf_ctx* ctx, const void* d_pool_packed, const void* d_pool_n
                     void* d_contigs, size_t contig_cap, void* d_n_contigs, void* d_seq, size_t seq_cap, void* d_seq_len,
                     void* d_gap_error);
 /* every (k_list[i], kv_list[i]) pair of run_assembly's loop (assemble_gaps.py:87-122) in one call: one launch per pair, all
- * appending to the same contig list (gf_contig.k / .kv tell the pairs apart); counters and error flags as gf_assemble_dev. */
+ * appending to the same contig list (gf_contig.k / .kv tell the pairs apart); counters and error flags as gf_assemble_dev.
+ * Capacities (this call and gf_assemble_dev): the counters count every contig and base, also those beyond contig_cap / seq_cap; every
+ * record below min(*d_n_contigs, contig_cap) is written, and one whose bases do not fit seq_cap is a TOMBSTONE {length = 0, seq_off = 0}
+ * (the contig list's consumers skip it); nothing is written beyond either capacity. */
 int gf_assemble_multi_dev(gf_ctx* ctx, const void* d_pool_packed, const void* d_pool_n_mask_or_null, const void* d_pool_off,
                           size_t n_pools, size_t total_reads, int read_len, const int* k_list, const int* kv_list, int n_k,
                           int min_count, int min_contig, void* d_contigs, size_t contig_cap, void* d_n_contigs, void* d_seq,
@@ -550,7 +553,9 @@ int gf_overlap_evaluate_dev(gf_ctx* ctx, const void* d_seq, const void* d_contig
  * (the 21 longest paths per root), removal of reverse-complement twin paths, and FormMergedSeqFromPath per path with Evaluate in its
  * relaxed mode (GraphUtils.cpp:625-859, 1028-1178, 1258-1344, 1422-1454; ContigsCompactor.cpp:773-983, 1456-1520).  The merged strings are
  * APPENDED to the contig list as records {gap, k = 0, kv = 0, n_nodes = nodes of the path, length, seq_off} in (gap, sorted path) order
- * (NEW_CONTIG_MERGE_1, _2, ... of each gap); *d_n_contigs and *d_seq_len grow.  Everything is enqueued on the context's stream, no host
+ * (NEW_CONTIG_MERGE_1, _2, ... of each gap); *d_n_contigs and *d_seq_len grow.  Tombstones (length 0) take no part.  A list handed over
+ * beyond its capacities (*d_n_contigs > contig_cap or *d_seq_len > seq_cap) is left as it is, counters included, and flags 32 / 64 are
+ * set: the round is a no-op that keeps the overflow visible.  Everything is enqueued on the context's stream, no host
  * synchronisation.  A gap's contigs are taken in the order of its contigs.fa: the (k_list[i], kv_list[i]) pairs in list order, inside a pair
  * by (length descending, sequence) — n_k <= 16; n_k == 0: record order.
  * d_stats: u32[32] — [0] open gaps with 2 .. 1 024 contigs, [1] gaps that went through the merger, [2] gaps left alone for their size
