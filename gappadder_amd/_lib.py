@@ -46,6 +46,11 @@ MG_WORDS = 32
 R2_KMERS, R2_TAB_FULL, R2_HITS, R2_UNIQUE, R2_TRIED, R2_WITH, R2_ROWS, R2_FIRST, R2_APPEND_ERR, R2_N2, R2_POOL_OVF = 0, 1, 2, 3, 4, 5, 6, 8, 9, 10, 11
 R2_WORDS, R2_MAX_LIBS = 16, 16
 
+# the rescue round (rescue.hip, u32[16] statistics): marker of the bridge records (k = kv = RESCUE_MARK), the words of the statistics
+RESCUE_MARK = 0xFFFF
+RS_TRIED, RS_HQ_KEYS, RS_HQ, RS_WINDOWS, RS_TAB_FULL, RS_SEEDS, RS_PLACE_OVF, RS_GAPS_BRIDGED, RS_BRIDGES, RS_FIRST, RS_APPEND_ERR, RS_LONG = range(12)
+RS_WORDS = 16
+
 # words of the extended fill's statistics (gf_pick_extended_dev, u32[12]): fills (left only, right only, both sides), u64 bases, overflow flag
 EXT_EXTENDED, EXT_LEFT_ONLY, EXT_RIGHT_ONLY, EXT_BOTH, EXT_BASES, EXT_OVERFLOW, EXT_ALIGN_DROPPED, EXT_ALIGN_SEED_OVERFLOW = 0, 1, 2, 3, 4, 6, 8, 9
 EXT_WORDS, EXT_MAX_PAIRS = 12, 32
@@ -148,6 +153,12 @@ def lib():
         "gf_pick_extended_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_pick_extended_aligned_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_contigs_append_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp]),
+        "gf_rescue_work_bytes": (sz, [sz, sz, sz, i32]),
+        "gf_rescue_reset_dev": (i32, [vp, vp, sz, sz, sz, i32, vp]),
+        "gf_rescue_hq_keys_dev": (i32, [vp, vp, vp, sz, vp, sz, i32, sz, vp, sz, sz, i32, vp]),
+        "gf_rescue_bridges_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, vp, i32, i32, vp, sz, sz, i32, vp, vp]),
+        "gf_rescue_gap_bridges": (vp, [vp, sz, sz, sz, i32]),
+        "gf_merge_rescue_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, i32, i32, vp, vp, i32, vp, vp, vp, vp]),
         "gf_count_kmers": (i32, [vp, vp, vp, sz, i32, i32, i32, vp, vp, sz, szp]),
         "gf_pool_keys_reset": (i32, [vp, vp]),
         "gf_pool_keys_from_screen_dev": (i32, [vp, vp, vp, sz, i32, vp, sz, vp]),

@@ -72,6 +72,24 @@ struct ExtHit {
 };
 static_assert(sizeof(ExtHit) == 24, "ExtHit");
 
+// merge.hip's kernels in the rescue round (rescue.hip).  MG_MODE_ROUND: the merge round of the step (gf_merge_open_gaps_dev);
+// MG_MODE_RESCUE: the rescue's merge (gf_merge_rescue_dev); MG_MODE_SETS: the rescue's alignment sets — the open gaps' records, own and
+// merged, through the exact-containment dedup alone, in record order
+enum : uint32_t { MG_MODE_ROUND = 0, MG_MODE_RESCUE = 1, MG_MODE_SETS = 2 };
+struct MgSetsView {          // where MG_MODE_SETS leaves the sets (the merge workspace, until the next merge call on the stream)
+    const uint32_t* pre_of_gap;   // [n_gaps] set of a gap or EMPTY32 (fewer than 2 or more than 1024 contigs)
+    const uint32_t* pre_off;      // [sets + 1] first entry of a set in ids
+    const uint32_t* kept_n;       // [sets] contigs the dedup kept: ids[pre_off[s] .. + kept_n[s]), ascending record index
+    const uint32_t* ids;
+};
+struct MgRescueArgs {
+    uint32_t mode;
+    const uint32_t* gap_bridges;
+    const uint32_t* merge_n0;
+    const uint32_t* rescue_first;
+    MgSetsView* view;
+};
+
 struct TimedLaunch {
     hipEvent_t a, b;
     int which;
@@ -144,7 +162,7 @@ struct gf_ctx {
     size_t low_b1 = 0, low_b2 = 0;
 
     // scratch
-    gf::DevBuf cand, cand2, part_ws, tag_stage, verify_stage, bam_stream, bam_recs, asm_table, asm_surv, asm_nodes, asm_jump, asm_big, rowgap, pool_ws, xchg_ws, xchg_ws2, merge_ws, counters, stage_in, stage_out, stage_aux, table, r2_tmp, ext_ws;
+    gf::DevBuf cand, cand2, part_ws, tag_stage, verify_stage, bam_stream, bam_recs, asm_table, asm_surv, asm_nodes, asm_jump, asm_big, rowgap, pool_ws, xchg_ws, xchg_ws2, merge_ws, counters, stage_in, stage_out, stage_aux, table, r2_tmp, ext_ws, rs_tmp;
     size_t bam_n_recs = 0;       // alignment records gf_bam_pack left in bam_recs (for gf_tag_*_bam)
     size_t bam_stream_len = 0;   // inflated BAM bytes gf_bgzf_inflate left in bam_stream
     // timing
@@ -197,6 +215,10 @@ void zero_regions(gf_ctx* ctx, const ZeroList& z);
 int anchor_table_for(gf_ctx* ctx, int anchor_len, const uint8_t** out);
 int launch_align_ext(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t, const void* d_first,
                      const void* d_gap_best, ExtHit* hits, uint32_t* heads, uint32_t* stats);
+
+// merge.hip: MG_MODE_SETS (d_stats: u32[GF_MG_WORDS] of its own)
+int launch_merge_sets(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t contig_cap, void* d_seq, void* d_seq_len, size_t seq_cap,
+                      const void* d_gap_best, size_t n_gaps, const gf_ovl_params* params, void* d_stats, MgSetsView* view);
 
 // index.cpp
 int build_flank_index(gf_ctx* ctx, int k, FlankIndex** out);

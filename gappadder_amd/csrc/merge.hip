@@ -381,6 +381,7 @@ enum { MG_N_PRE = 0, MG_N_SETS = 1, MG_SKIPPED = 2, MG_N_PAIRS = 3, MG_QC_FLAGS 
 // MG_MAX_EDGES edges, MG_MAX_PATHS paths or MG_PATH_BYTES path nodes (the contig graph of a repeat-bearing gap has thousands of paths) —
 // is left alone and counted in stats[MG_SKIPPED_GRAPH], like the sets of more than max_set contigs in stats[MG_SKIPPED]
 constexpr uint32_t MG_E_SEQ = 1, MG_E_PAIRS = 2, MG_E_CONTIGS = 32, MG_E_OUTSEQ = 64;
+constexpr uint32_t MG_SETS_NO_MAX_SET = 0;   // max_set of MG_MODE_SETS: the dedup alone, no set limit applies
 
 struct MgJob { uint32_t set, off, len; };   // path = job_nodes[off .. off + len)
 
@@ -431,6 +432,12 @@ struct MgParams {
     // (length descending, sequence) — n_k > 0; n_k == 0: record order (contig index)
     uint32_t n_k;
     uint16_t k_list[16], kv_list[16];
+    // the rescue round's two uses of these kernels (gf_merge_rescue_dev, gf_rescue_bridges_dev; MG_MODE_*): which records take part,
+    // and where the rescue set's marker records (k = kv = GF_RESCUE_MARK, the bridges) stand in a gap's order
+    uint32_t mode;
+    const uint32_t* gap_bridges;      // [n_gaps] bridges per gap (MG_MODE_RESCUE: a gap without one takes no part)
+    const uint32_t* merge_n0;         // the first merge round's first record (its stats[MG_N0]) ...
+    const uint32_t* rescue_first;     // ... and the first bridge: [*merge_n0, *rescue_first) = the first merge's records, no part of the rescue set
 };
 
 __device__ __forceinline__ uint32_t mg_block_scan_excl(uint32_t v, uint32_t* s_w, uint32_t* total) {   // blockDim.x a multiple of 64, <= 1024
@@ -453,9 +460,12 @@ __device__ __forceinline__ uint32_t mg_block_scan_excl(uint32_t v, uint32_t* s_w
 // visible — no gap is counted, so no set takes part, stats[MG_ERR] says why, and *n_contigs / *seq_len stay beyond the caps
 __device__ __forceinline__ bool mg_list_overflowed(const MgParams& P) { return *P.n_contigs > P.contig_cap || *P.seq_len > P.seq_cap; }
 
-// tombstones (length 0: a record whose bases did not fit the buffer) take no part; mg_fill_kernel skips the same records
-__device__ __forceinline__ bool mg_takes_part(const MgParams& P, const gf_contig& c) {
-    return c.gap < P.n_gaps && c.length != 0 && P.gap_best[c.gap] == 0;
+// tombstones (length 0: a record whose bases did not fit the buffer) take no part; mg_fill_kernel skips the same records.  The rescue
+// merge (MG_MODE_RESCUE) takes the gap's own contigs and its bridges, not the first merge's records, and only gaps with a bridge
+__device__ __forceinline__ bool mg_takes_part(const MgParams& P, const gf_contig& c, uint32_t idx) {
+    if (!(c.gap < P.n_gaps && c.length != 0 && P.gap_best[c.gap] == 0)) return false;
+    if (P.mode != MG_MODE_RESCUE) return true;
+    return (idx < *P.merge_n0 || idx >= *P.rescue_first) && P.gap_bridges[c.gap] != 0;
 }
 
 __global__ __launch_bounds__(256) void mg_count_kernel(MgParams P) {
@@ -463,7 +473,7 @@ __global__ __launch_bounds__(256) void mg_count_kernel(MgParams P) {
     const uint32_t n = *P.n_contigs < P.contig_cap ? *P.n_contigs : P.contig_cap;
     for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n; c += gridDim.x * blockDim.x) {
         const gf_contig ct = P.contigs[c];
-        if (mg_takes_part(P, ct)) atomicAdd(&P.cnt[ct.gap], 1u);
+        if (mg_takes_part(P, ct, c)) atomicAdd(&P.cnt[ct.gap], 1u);
     }
 }
 
@@ -501,7 +511,7 @@ __global__ __launch_bounds__(256) void mg_fill_kernel(MgParams P) {
     const uint32_t n = P.stats[MG_N0];
     for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n; c += gridDim.x * blockDim.x) {
         const gf_contig ct = P.contigs[c];
-        if (!mg_takes_part(P, ct)) continue;
+        if (!mg_takes_part(P, ct, c)) continue;
         const uint32_t g = ct.gap;
         const uint32_t pre = P.pre_of_gap[g];
         if (pre == EMPTY32) continue;
@@ -537,6 +547,8 @@ __global__ __launch_bounds__(1024) void mg_dedup_kernel(MgParams P) {
                 uint32_t pi = 0xFFFFu;
                 for (uint32_t q = 0; q < P.n_k; ++q) if (P.k_list[q] == c.k && P.kv_list[q] == c.kv) { pi = q; break; }
                 key = P.n_k ? ((unsigned long long)pi << 32) | (0xFFFFFFFFu - c.length) : (unsigned long long)s_id[tid];
+                if (P.mode == MG_MODE_RESCUE && c.k == GF_RESCUE_MARK && c.kv == GF_RESCUE_MARK)      // bridges: after every pair, in record order
+                    key = (0x10000ull << 32) | s_id[tid];
             }
             s_key[tid] = key;
         }
@@ -1124,7 +1136,7 @@ static inline size_t mg_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int launch_merge_round(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t contig_cap, void* d_seq, void* d_seq_len, size_t seq_cap,
                        const void* d_gap_best, size_t n_gaps, const gf_ovl_params* params, int kq, int max_set, const int* k_list, const int* kv_list,
-                       int n_k, void* d_stats) {
+                       int n_k, void* d_stats, const MgRescueArgs* rs = nullptr) {
     const unsigned grid = (unsigned)ctx->n_cu;
     const size_t ng = n_gaps;
     const size_t node_cap = contig_cap;
@@ -1163,6 +1175,15 @@ int launch_merge_round(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t c
     P.pr.relax = 0.0;
     P.n_k = (uint32_t)n_k;
     for (int q = 0; q < n_k; ++q) { P.k_list[q] = (uint16_t)k_list[q]; P.kv_list[q] = (uint16_t)kv_list[q]; }
+    if (rs) {
+        if (rs->mode == MG_MODE_SETS && (max_set != (int)MG_SETS_NO_MAX_SET || !rs->view)) return GF_E_INVAL;   // (see launch_merge_sets)
+        P.mode = rs->mode;
+        P.gap_bridges = rs->gap_bridges; P.merge_n0 = rs->merge_n0; P.rescue_first = rs->rescue_first;
+        if (rs->mode == MG_MODE_SETS) {
+            P.n_k = 0;
+            rs->view->pre_of_gap = P.pre_of_gap; rs->view->pre_off = P.pre_off; rs->view->kept_n = P.kept_n; rs->view->ids = P.ids;
+        }
+    }
     LaunchTimer tm(ctx, GF_KERNEL_MERGE);
     GF_HIP(ctx, hipMemsetAsync(d_stats, 0, MG_WORDS * 4, ctx->stream));
     GF_HIP(ctx, hipMemsetAsync(P.cnt, 0, ng * 4, ctx->stream));
@@ -1175,6 +1196,10 @@ int launch_merge_round(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t c
     hipLaunchKernelGGL(mg_scan_gaps_kernel, dim3(1), dim3(1024), 0, ctx->stream, P);
     hipLaunchKernelGGL(mg_fill_kernel, dim3(cgrid), dim3(256), 0, ctx->stream, P);
     hipLaunchKernelGGL(mg_dedup_kernel, dim3(grid), dim3(1024), 0, ctx->stream, P);
+    if (P.mode == MG_MODE_SETS) {       // (the sets stay in the workspace for the rescue kernels that follow on this stream)
+        GF_HIP(ctx, hipGetLastError());
+        return GF_OK;
+    }
     hipLaunchKernelGGL(mg_scan_sets_kernel, dim3(1), dim3(1024), 0, ctx->stream, P);
     hipLaunchKernelGGL(mg_copy_kernel, dim3(grid), dim3(256), 0, ctx->stream, P);
     {   // the merger's prefilter over the sets (their number is a device word)
@@ -1198,6 +1223,31 @@ int launch_merge_round(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t c
     hipLaunchKernelGGL(mg_strings_kernel, dim3(grid), dim3(OV_NT), OV_LDS_BYTES, ctx->stream, P);
     GF_HIP(ctx, hipGetLastError());
     return GF_OK;
+}
+
+static int merge_args_ok(gf_ctx* ctx, const char* who, void* d_contigs, void* d_n_contigs, size_t contig_cap, void* d_seq, void* d_seq_len,
+                         const void* d_gap_best, size_t n_gaps, const gf_ovl_params* params, int kmer_len_quick, int max_set, const int* k_list,
+                         const int* kv_list, int n_k, void* d_stats) {
+    if (n_k < 0 || n_k > 16 || (n_k && (!k_list || !kv_list))) return GF_E_INVAL;
+    if (!ctx || !d_contigs || !d_n_contigs || !d_seq || !d_seq_len || !d_gap_best || !params || !d_stats || contig_cap > 0x7FFFFFFFull ||
+        n_gaps > 0xFFFFFFF0ull || kmer_len_quick < 4 || kmer_len_quick > 16 || max_set < 2 || max_set > (int)(MG_MAX_NODES / 2))
+        return GF_E_INVAL;
+    if (params->indel != (double)(int)params->indel || params->max_clip < 0 || params->max_clip > 1e6) {
+        ctx->last_error = std::string(who) + ": the indel score must be integral";
+        return GF_E_UNSUPPORTED;
+    }
+    return GF_OK;
+}
+
+// the rescue's alignment sets (rescue.hip): mg_count .. mg_dedup over the open gaps' records, own and merged, in record order.  Those four
+// kernels read neither the merger's parameters, nor the prefilter's k, nor max_set (launch_merge_round stops after mg_dedup in this mode,
+// before mg_scan_sets applies max_set): the values below only fill the call.  A change that makes one of them read P.pr, P.max_set or the
+// k must give this mode real values — launch_merge_round refuses MG_MODE_SETS with a max_set other than MG_SETS_NO_MAX_SET.
+int launch_merge_sets(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t contig_cap, void* d_seq, void* d_seq_len, size_t seq_cap,
+                      const void* d_gap_best, size_t n_gaps, const gf_ovl_params* params, void* d_stats, MgSetsView* view) {
+    MgRescueArgs rs{MG_MODE_SETS, nullptr, nullptr, nullptr, view};
+    return launch_merge_round(ctx, d_contigs, d_n_contigs, contig_cap, d_seq, d_seq_len, seq_cap, d_gap_best, n_gaps, params, 8, MG_SETS_NO_MAX_SET,
+                              nullptr, nullptr, 0, d_stats, &rs);
 }
 
 }  // namespace gf
@@ -1381,6 +1431,20 @@ int gf_merge_open_gaps_dev(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size
     if (!n_gaps) { GF_HIP(ctx, hipMemsetAsync(d_stats, 0, MG_WORDS * 4, ctx->stream)); return GF_OK; }
     return launch_merge_round(ctx, d_contigs, d_n_contigs, contig_cap, d_seq, d_seq_len, seq_cap, d_gap_best, n_gaps, params, kmer_len_quick, max_set,
                               k_list, kv_list, n_k, d_stats);
+}
+
+int gf_merge_rescue_dev(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t contig_cap, void* d_seq, void* d_seq_len, size_t seq_cap,
+                        const void* d_gap_best, size_t n_gaps, const gf_ovl_params* params, int kmer_len_quick, int max_set, const int* k_list,
+                        const int* kv_list, int n_k, const void* d_merge_stats, const void* d_rescue_first, const void* d_gap_bridges, void* d_stats) {
+    int rc = merge_args_ok(ctx, "gf_merge_rescue_dev", d_contigs, d_n_contigs, contig_cap, d_seq, d_seq_len, d_gap_best, n_gaps, params, kmer_len_quick,
+                           max_set, k_list, kv_list, n_k, d_stats);
+    if (rc) return rc;
+    if (!d_merge_stats || !d_rescue_first || !d_gap_bridges) return GF_E_INVAL;
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    if (!n_gaps) { GF_HIP(ctx, hipMemsetAsync(d_stats, 0, MG_WORDS * 4, ctx->stream)); return GF_OK; }
+    MgRescueArgs rs{MG_MODE_RESCUE, (const uint32_t*)d_gap_bridges, (const uint32_t*)d_merge_stats + MG_N0, (const uint32_t*)d_rescue_first, nullptr};
+    return launch_merge_round(ctx, d_contigs, d_n_contigs, contig_cap, d_seq, d_seq_len, seq_cap, d_gap_best, n_gaps, params, kmer_len_quick, max_set,
+                              k_list, kv_list, n_k, d_stats, &rs);
 }
 
 }  // extern "C"

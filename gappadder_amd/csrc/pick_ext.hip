@@ -117,6 +117,7 @@ __global__ __launch_bounds__(256) void ext_anchor_kernel(ExtParams P, const uint
 __device__ __forceinline__ uint32_t ext_rank(const ExtParams& P, const gf_contig& c) {
     for (uint32_t i = 0; i < P.n_k; ++i)
         if (c.k == P.k[i] && c.kv == P.kv[i]) return i;
+    if (c.k == GF_RESCUE_MARK && c.kv == GF_RESCUE_MARK) return P.n_k + 1;     // the rescue's bridges: after the merged contigs
     return P.n_k;                          // merged contigs (k = kv = 0) and any pair not in the list: after every pair
 }
 

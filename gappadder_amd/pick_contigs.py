@@ -332,8 +332,10 @@ def extension_order(contigs, k_pairs):
     """The contig order of the device step's extended fill (gf_pick_extended_dev): pick_extended_sequence takes the FIRST contig with
     a hit per side, and the device lists a gap's contigs in no fixed order.  contigs: [(k, kv, bases)]; k_pairs: the pipeline's
     [(k, kv)].  Returns the contig indices sorted by (position of (k, kv) in k_pairs — the merged contigs' (0, 0) and any pair not in
-    the list after every pair, as contigs.fa concatenates the per-pair files —, length descending, bases ascending, index)."""
-    rank = {}
+    the list after every pair, as contigs.fa concatenates the per-pair files, and the rescue round's bridges (RESCUE_MARK, RESCUE_MARK)
+    after those —, length descending, bases ascending, index)."""
+    from ._lib import RESCUE_MARK
+    rank = {(RESCUE_MARK, RESCUE_MARK): len(k_pairs) + 1}
     for i, (k, kv) in enumerate(k_pairs):
         rank.setdefault((int(k), int(kv)), i)
     n = len(k_pairs)

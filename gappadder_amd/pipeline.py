@@ -19,6 +19,8 @@ What the reference does with files between processes —
     gf_contig_kmer_table_dev + gf_recruit_by_contigs_dev       second assembly round for the gaps still open (second_round):
       + gf_round2_pools_dev + gf_assemble_multi_dev            both-unmapped pairs recruited by the round-1 contigs' k-mers, pools
       + gf_contigs_append_dev + gf_pick_*_from_dev             = round-1 rows + recruits, assembled and picked again
+    gf_rescue_hq_keys_dev + gf_rescue_bridges_dev              rescue round for the gaps still open after the merge pick (rescue_round):
+      + gf_merge_rescue_dev + gf_pick_*_from_dev               high-quality reads clipped at two contigs join the own contigs, merge, pick at 15
     gf_pick_extended[_aligned]_dev                             partial fills of the gaps every pick left open (extended_fill)
 
 `Pipeline` owns the sizing pass (capacities follow what the libraries actually recruit), every intermediate buffer, the stream
@@ -69,7 +71,7 @@ class Pipeline:
     def __init__(self, gf, n_gaps, read_len, k_pairs, device=None, world=1, rank=0, backend="nccl", force_exchange=False,
                  min_count=2, min_contig=40, anchors=(30, 15), clip_dist=250, anchor_mapq=30, k_screen=None, keep_read_ids=False,
                  key_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False,
-                 extended_fill=False, ext_base_cap=None):
+                 extended_fill=False, ext_base_cap=None, rescue_round=False):
         """gf: a GapFill whose gaps (and flanks, when a library is screened) are set.  k_pairs: [(k, k_velvet)] of
         assemble_gaps.py:87-122.  The screen runs at the SMALLEST k of the list: a read that shares a 51-mer with a flank shares
         its 31-mers too, so this is the superset every assembly k needs (the reference recruits once, then assembles at every k).
@@ -92,9 +94,23 @@ class Pipeline:
         anchor, anchors[-1], in anchor_mode; over the round-2 contigs with second_round, else over all of the step's contigs).  Results.ext
         (gf_ext_pick per gap), .ext_bases and .extended (counts); Pipeline.extended_sequences decodes them.  Single rank.  ext_base_cap:
         bytes of the fill buffer (default: the contig bases' capacity + 2 per gap, which no fill set can exceed); fetch() raises when
-        the fills do not fit."""
+        the fills do not fit.
+        rescue_round: the reference's rescue round (assemble_gaps.py:357-366) after the merge round's pick: per gap still
+        open, its high-quality reads (the tagger hits of MAPQ-60 records) that align clipped to two or more of its merged contigs are
+        bridges; they are appended as records with k = kv = RESCUE_MARK, the gap's own contigs and its bridges are merged again (merged
+        contigs appended with k = kv = 0), and the records the round appended are picked at anchors[-1] (Results.rescue / rescue_first).
+        Needs merge_in_step; single rank, without second_round.  Like second_round's candidates, the read ids assume that the libraries'
+        read names are distinct."""
         if anchor_mode not in ("exact", "align"):
             raise ValueError("anchor_mode %r: 'exact' or 'align'" % (anchor_mode,))
+        self.rescue_round = bool(rescue_round)
+        if self.rescue_round:
+            if not merge_in_step:
+                raise ValueError("rescue_round needs merge_in_step: the reads are aligned to the merged contigs")
+            if int(world) > 1 or force_exchange:
+                raise ValueError("rescue_round runs on a single rank")
+            if second_round:
+                raise ValueError("rescue_round with second_round: the order of the rounds is not settled")
         self.second_round = bool(second_round)
         if self.second_round:
             if int(world) > 1 or force_exchange:
@@ -442,6 +458,10 @@ class Pipeline:
             self._prepare_round2()
             if self.extended_fill:
                 self._ext_alloc()       # (the round may have grown the contig buffers)
+        if self.rescue_round:
+            self._prepare_rescue()
+            if self.extended_fill:
+                self._ext_alloc()
         if self.tag_ahead:          # the first step's tagger pass (untimed, like a warm-up step's)
             assert all(lb.second_stream for lb in self.libs), "tag_ahead needs DeviceLibrary(tag_ctx=...)"
             self._on_stream(lambda: [self.tagger(lb) for lb in self.libs])
@@ -590,6 +610,110 @@ class Pipeline:
             self._chk(lib.gf_pick_anchored2_from_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), a0, a1, first,
                                                      self.d_best.data_ptr(), self.ap + 16), "gf_pick_anchored2_from_dev")
 
+    # ---- rescue round ----------------------------------------------------------------------------------------------------------
+    def _rs_alloc(self):
+        self.rs_work_bytes = int(self.lib.gf_rescue_work_bytes(self.n_gaps, self.rs_hq_cap, self.rs_seed_cap, self.rs_log2))
+        if not self.rs_work_bytes:
+            raise ValueError("rescue_round: unsupported sizes (%d gaps)" % self.n_gaps)
+        self.d_rs_work = self._u8(self.rs_work_bytes)
+        self.rs_gap_bridges = self.lib.gf_rescue_gap_bridges(self.d_rs_work.data_ptr(), self.n_gaps, self.rs_hq_cap, self.rs_seed_cap, self.rs_log2)
+
+    def _rs_args(self):
+        return self.d_rs_work.data_ptr(), self.rs_hq_cap, self.rs_seed_cap, self.rs_log2
+
+    def _prepare_rescue(self):
+        """The step with the round run again and again, every buffer grown to the exact count the run before reported, until nothing
+        is beyond a capacity (the HQ keys, the window table, the seeds, the step's contig list that the round appends to twice)."""
+        dev = self.dev
+        if len(self.libs) > B.R2_MAX_LIBS:
+            raise ValueError("rescue_round: at most %d libraries" % B.R2_MAX_LIBS)
+        if not self.kk or not self.assemble_in_step or self.n_gaps < 1:
+            raise ValueError("rescue_round runs inside the step's assembly (k_pairs, assemble_in_step and gaps)")
+        if not 30 <= self.L <= 1000:
+            raise ValueError("rescue_round: read length %d outside 30..1000" % self.L)
+        self.rs_reads = (C.c_void_p * len(self.libs))(*[lb.d_reads.data_ptr() for lb in self.libs])
+        self.rs_nmask = (C.c_void_p * len(self.libs))(*[lb.d_nmask.data_ptr() if lb.d_nmask is not None else None for lb in self.libs])
+        self.d_rst = torch.zeros(B.RS_WORDS, dtype=torch.int32, device=dev)
+        self.d_rsets = torch.zeros(B.MG_WORDS, dtype=torch.int32, device=dev)     # the alignment sets' dedup
+        self.d_rmstats = torch.zeros(B.MG_WORDS, dtype=torch.int32, device=dev)   # the rescue's merge
+        self.rs_hq_cap, self.rs_seed_cap, self.rs_log2 = 4096, 4096, 12
+        self._rs_alloc()
+        for attempt in range(8):
+            torch.cuda.synchronize()
+            self._on_stream(lambda: self._step(recruited=True))
+            self.sync()
+            torch.cuda.synchronize()
+            st = self.d_rst.cpu().numpy().view(np.uint32)
+            ms = self.d_rmstats.cpu().numpy().view(np.uint32)
+            a1 = self.d_acnt.cpu().numpy()
+            n, q = int(a1[0]), int(a1[2:4].view(np.uint64)[0])
+            grown = False
+            if int(st[B.RS_HQ_KEYS]) > self.rs_hq_cap:
+                self.rs_hq_cap, grown = int(1.25 * int(st[B.RS_HQ_KEYS])) + 4096, True
+            need_log2 = max(12, int(2 * int(st[B.RS_WINDOWS]) + 16).bit_length())
+            if need_log2 > self.rs_log2 or int(st[B.RS_TAB_FULL]):
+                self.rs_log2, grown = max(need_log2, self.rs_log2 + 1), True
+            if int(st[B.RS_SEEDS]) > self.rs_seed_cap:
+                self.rs_seed_cap, grown = int(1.25 * int(st[B.RS_SEEDS])) + 4096, True
+            if n > self.contig_cap or q > self.seq_cap or int(st[B.RS_APPEND_ERR]) or (int(ms[B.MG_ERR]) & 96):
+                # (the merges' own outputs count beyond the list too: MG_E_CONTIGS / MG_E_OUTSEQ)
+                self.contig_cap, self.seq_cap = int(1.5 * max(n, self.contig_cap)) + 4096, int(1.5 * max(q, self.seq_cap)) + (1 << 20)
+                self.d_ctg, self.d_seq = self._u8(self.contig_cap * 32), self._u8(self.seq_cap)
+                if self.anchor_mode == "align":
+                    self.d_ctg_pick = self._u8(self.contig_cap * B.CTG_PICK.itemsize)
+                grown = True
+            if not grown:
+                break
+            self._rs_alloc()
+        else:
+            raise RuntimeError("rescue round: the buffers keep growing")
+        torch.cuda.synchronize()
+
+    def _rescue_keys(self):
+        """Enqueued after the pools: every library's HQ keys from its tagger hits (the tried gaps are chosen later, on the device)."""
+        lib, h = self.lib, self.h
+        self._chk(lib.gf_rescue_reset_dev(h, self.d_rs_work.data_ptr(), self.n_gaps, self.rs_hq_cap, self.rs_seed_cap, self.rs_log2, self.d_rst.data_ptr()),
+                  "gf_rescue_reset_dev")
+        for l, lb in enumerate(self.libs):
+            self._chk(lib.gf_rescue_hq_keys_dev(h, lb.d_thits.data_ptr(), lb.cp + 4 * CNT_TAG, lb.hit_cap, lb.d_recs.data_ptr(), lb.n_reads, l,
+                                                self.n_gaps, *self._rs_args(), self.d_rst.data_ptr()), "gf_rescue_hq_keys_dev")
+
+    def _rescue(self):
+        """Enqueued after the merge round's pick: bridges appended, the rescue sets merged, the appended records picked at anchors[-1]."""
+        lib, h = self.lib, self.h
+        ctg, seq, best = self.d_ctg.data_ptr(), self.d_seq.data_ptr(), self.d_best.data_ptr()
+        self._chk(lib.gf_rescue_bridges_dev(h, ctg, self.ap, self.contig_cap, seq, self.ap + 8, self.seq_cap, best, self.n_gaps, self.rs_reads,
+                                            self.rs_nmask, len(self.libs), self.L, *self._rs_args(), self.d_rsets.data_ptr(), self.d_rst.data_ptr()),
+                  "gf_rescue_bridges_dev")
+        first = self.d_rst.data_ptr() + 4 * B.RS_FIRST
+        self._chk(lib.gf_merge_rescue_dev(h, ctg, self.ap, self.contig_cap, seq, self.ap + 8, self.seq_cap, best, self.n_gaps, B._p(self.merge_params), 10,
+                                          self.merge_max_set, self.k_arr, self.kv_arr, min(16, len(self.kk)), self.d_mstats.data_ptr(), first,
+                                          self.rs_gap_bridges, self.d_rmstats.data_ptr()), "gf_merge_rescue_dev")
+        a = self.anchors[-1]
+        if self.anchor_mode == "align":
+            self._chk(lib.gf_pick_aligned_from_dev(h, ctg, self.ap, self.contig_cap, seq, a, 0, first, best, self.ap + 16, self.d_ctg_pick.data_ptr(),
+                                                   self.d_pstats.data_ptr()), "gf_pick_aligned_from_dev")
+        else:
+            self._chk(lib.gf_pick_anchored2_from_dev(h, ctg, self.ap, self.contig_cap, seq, a, 0, first, best, self.ap + 16), "gf_pick_anchored2_from_dev")
+
+    def _fetch_rescue(self, r):
+        st = self.d_rst.cpu().numpy().view(np.uint32)
+        ms = self.d_rmstats.cpu().numpy().view(np.uint32)
+        ss = self.d_rsets.cpu().numpy().view(np.uint32)
+        if int(st[B.RS_APPEND_ERR]) or int(ms[B.MG_ERR]):
+            raise RuntimeError("rescue round overflow: append flag %d, merge capacity flags %#x, %d contigs (cap %d), %d contig bases (cap %d)"
+                               % (int(st[B.RS_APPEND_ERR]), int(ms[B.MG_ERR]), r.n_contigs, self.contig_cap, r.n_seq, self.seq_cap))
+        first = int(st[B.RS_FIRST])
+        # HQ reads the round could not take: keys beyond their buffer, windows without room, seeds beyond their buffer, reads with more
+        # placements than the bridge kernel holds, contigs too long to seed, gaps with more records than the dedup takes
+        dropped = (max(0, int(st[B.RS_HQ_KEYS]) - self.rs_hq_cap) + int(st[B.RS_TAB_FULL]) + max(0, int(st[B.RS_SEEDS]) - self.rs_seed_cap)
+                   + int(st[B.RS_PLACE_OVF]) + int(st[B.RS_LONG]) + int(ss[B.MG_SKIPPED]))
+        idx = 0x7FFFFFFF - ((r.best >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64)
+        r.rescue_first = first
+        r.rescue = {"gaps_tried": int(st[B.RS_TRIED]), "hq_reads": int(st[B.RS_HQ]), "gaps_with_bridges": int(st[B.RS_GAPS_BRIDGED]),
+                    "bridges": int(st[B.RS_BRIDGES]), "merged_contigs": int(ms[B.MG_N_JOBS]), "closed": int(((r.best != 0) & (idx >= first)).sum()),
+                    "dropped": int(dropped)}
+
     def _check_cap(self, n, cap, what, lb):
         if n > cap:
             raise RuntimeError("library %s: %d %s exceed the capacity %d (add_library(hit_cap=...))" % (lb.name, n, what, cap))
@@ -606,6 +730,8 @@ class Pipeline:
             if not recruited:
                 self.hop_and_keys(lb)
             self.build_pools(lb, self.pool_ptr[l], self.lib_cap)
+        if self.rescue_round and self.kk:
+            self._rescue_keys()        # (they read this step's tagger hits: listed before the next step's tagger rewrites them)
         if self.tag_ahead:
             for lb in self.libs:        # the next step's tagger pass: behind every consumer of this step's hits, beside the assembly
                 self._chk(lib.gf_stream_wait(lb.h2, h), "gf_stream_wait")
@@ -686,6 +812,8 @@ class Pipeline:
                           "gf_pick_anchored2_from_dev")
         if self.second_round:
             self._round2()
+        if self.rescue_round:
+            self._rescue()
         if self.extended_fill:
             self._extend()
 
@@ -751,9 +879,13 @@ class Pipeline:
         if self.anchor_mode == "align":
             r.ctg_pick = np.frombuffer(self.d_ctg_pick[:r.n_contigs * B.CTG_PICK.itemsize].cpu().numpy().tobytes(), dtype=B.CTG_PICK)
             r.align_dropped, r.align_seed_overflow = (int(x) for x in self.d_pstats.cpu().numpy())
-        if r.merge is not None:      # gaps whose winning contig is a merged one
+        r.rescue, r.rescue_first = None, None
+        if self.rescue_round and self.kk:
+            self._fetch_rescue(r)
+        if r.merge is not None:      # gaps whose winning contig is a merged one (of the merge round: the rescue's records come after them)
             idx = 0x7FFFFFFF - ((r.best >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64)
-            r.merge["gaps_closed_by_merging"] = int(((r.best != 0) & (idx >= r.merge["contigs_before"])).sum())
+            end = r.rescue_first if r.rescue_first is not None else np.iinfo(np.int64).max
+            r.merge["gaps_closed_by_merging"] = int(((r.best != 0) & (idx >= r.merge["contigs_before"]) & (idx < end)).sum())
         r.round2, r.round2_first, r.round2_reads = None, None, None
         if self.second_round and self.kk:
             self._fetch_round2(r)

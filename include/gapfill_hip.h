@@ -655,6 +655,58 @@ int gf_contigs_append_dev(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_
 int gf_bridging_reads(gf_ctx* ctx_or_null, const char* ctg_text, const uint64_t* ctg_off, const uint64_t* ctg_set_off, const char* read_text,
                       const uint64_t* read_off, const uint64_t* read_set_off, size_t n_gaps, int seed_len, int budget, uint8_t* out_bridge);
 
+/* ---- the rescue round inside the device step (assemble_gaps.py:357-366, body :166-217; csrc/rescue.hip), after the merge
+ * round's pick.  Definition (the CLI's, GapAssembler.collect_high_quality_unmap_to_contigs_reads + gf_bridging_reads, seed 30, budget 2):
+ *   tried gaps   d_gap_best == 0 when gf_rescue_bridges_dev runs;
+ *   HQ reads     per tried gap the reads of the libraries' alignment-tagger hits whose record has MAPQ == 60 and a read (not 0xFFFFFFFF),
+ *                read = record's read ^ to_mate; each (gap, library, mate, read) once, ordered by (library, mate side, pair) — the CLI's
+ *                gap_reads_high_quality file; reads are identified by (library, read), which is the CLI's first-record-of-a-name rule when
+ *                the libraries' read names are distinct;
+ *   alignment set  the exact-containment dedup of the gap's records on the list (own contigs and the merge round's, k = kv = 0) = the CLI's
+ *                contigs.fa after the merge (drop_contained(new + nodup)); gaps with more than 1 024 such records are not tried (stats[11]);
+ *   bridge       gf_bridging_reads' predicate against the set: exact 30-base seed on either strand, at most 8 occurrences of a window per
+ *                contig strand in offset order, first seed per (contig, strand, diagonal), clipped = a read end beyond the contig or more
+ *                than 2 mismatches on either side of the seed, clipped AT a contig = every placement there clipped, a bridge is clipped at
+ *                two contigs at least; N-masked read bases never seed and always mismatch;
+ *   records      the bridges, in HQ order, appended to the list as records with k = kv = GF_RESCUE_MARK (tombstones, counters
+ *                that count every bridge, no record at or beyond contig_cap, nothing appended to a list that arrives overflowed).
+ * d_work: gf_rescue_work_bytes(n_gaps, hq_cap, seed_cap, log2_slots) bytes.  d_stats: u32[GF_RS_WORDS], every count exact whatever the
+ * capacities (a caller sizes from them and runs again: Pipeline.prepare). */
+#define GF_RESCUE_MARK 0xFFFF
+#define GF_RS_TRIED 0          /* gaps with d_gap_best == 0 */
+#define GF_RS_HQ_KEYS 1        /* keys listed by gf_rescue_hq_keys_dev (every gap; beyond hq_cap: not stored) */
+#define GF_RS_HQ 2             /* HQ reads of the tried gaps */
+#define GF_RS_WINDOWS 3        /* their 30-base windows (size the window table at least twice that) */
+#define GF_RS_TAB_FULL 4       /* windows the table had no room for */
+#define GF_RS_SEEDS 5          /* contig windows that an HQ read of the gap shares (beyond seed_cap: not stored) */
+#define GF_RS_PLACE_OVF 6      /* reads with more than 512 (contig, strand, diagonal) placements (no bridge) */
+#define GF_RS_GAPS_BRIDGED 7   /* tried gaps with a bridge */
+#define GF_RS_BRIDGES 8        /* bridges */
+#define GF_RS_FIRST 9          /* index of the first bridge record (d_first of the rescue's pick) */
+#define GF_RS_APPEND_ERR 10    /* 1: the list arrived overflowed (nothing appended); 2: the bridges went beyond a capacity */
+#define GF_RS_LONG 11          /* contigs of 2^24 bases or more (no seeds); gaps not tried, see above */
+#define GF_RS_WORDS 16
+size_t gf_rescue_work_bytes(size_t n_gaps, size_t hq_cap, size_t seed_cap, int log2_slots);
+/* zeroes d_stats and the key list: once per step, before the first gf_rescue_hq_keys_dev */
+int gf_rescue_reset_dev(gf_ctx* ctx, void* d_work, size_t n_gaps, size_t hq_cap, size_t seed_cap, int log2_slots, void* d_stats);
+/* one library's HQ keys (gap << 40 | lib << 36 | mate side << 35 | pair) from its tagger hits, for every gap (the tried gaps are chosen by
+ * gf_rescue_bridges_dev): may run before the pick, so that a tagger that rewrites d_thits next (Pipeline tag_ahead) can follow it */
+int gf_rescue_hq_keys_dev(gf_ctx* ctx, const void* d_thits, const void* d_n_thits, size_t thit_cap, const void* d_recs, size_t n_reads, int lib,
+                          size_t n_gaps, void* d_work, size_t hq_cap, size_t seed_cap, int log2_slots, void* d_stats);
+/* HQ reads of the tried gaps, alignment sets, seeds, bridges, append.  d_lib_reads / d_lib_nmask: n_lib device pointers (host arrays; the nmask
+ * array or its entries may be NULL); d_sets_stats: u32[32] of the alignment sets' dedup (gf_merge_open_gaps_dev's words). */
+int gf_rescue_bridges_dev(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t contig_cap, void* d_seq, void* d_seq_len, size_t seq_cap,
+                          const void* d_gap_best, size_t n_gaps, const void* const* d_lib_reads, const void* const* d_lib_nmask, int n_lib, int read_len,
+                          void* d_work, size_t hq_cap, size_t seed_cap, int log2_slots, void* d_sets_stats, void* d_stats);
+/* u32[n_gaps] bridges per gap inside d_work (the d_gap_bridges of gf_merge_rescue_dev) */
+const void* gf_rescue_gap_bridges(void* d_work, size_t n_gaps, size_t hq_cap, size_t seed_cap, int log2_slots);
+/* the rescue's merge: gf_merge_open_gaps_dev over the rescue SETS — per tried gap with a bridge its own contigs (the records before the merge
+ * round's, *(d_merge_stats + 7)) followed by its bridges (records from *d_rescue_first on) in record order — merged contigs appended with
+ * k = kv = 0.  Follow with gf_pick_*_from_dev(d_first = d_rescue_first). */
+int gf_merge_rescue_dev(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t contig_cap, void* d_seq, void* d_seq_len, size_t seq_cap,
+                        const void* d_gap_best, size_t n_gaps, const gf_ovl_params* params, int kmer_len_quick, int max_set, const int* k_list,
+                        const int* kv_list, int n_k, const void* d_merge_stats, const void* d_rescue_first, const void* d_gap_bridges, void* d_stats);
+
 /* ---- device memory + timing helpers (so a ctypes host needs no other HIP binding) ---------------------- */
 int gf_dev_alloc(gf_ctx* ctx, size_t bytes, void** d_ptr);
 int gf_dev_free(gf_ctx* ctx, void* d_ptr);
