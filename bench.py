@@ -11,13 +11,19 @@ GPU at N=1 (63 GB resident).  At N > 1 the SAME reads are split over the ranks (
 scaling = strong), gaps and the flank index are replicated, and every gap is assembled exactly once, by its owner rank, from
 the recruits of all ranks (the reference maps each gap to one Pool task, assemble_gaps.py:296-299).
 
-    python bench.py --gpus N --steps K --warmup W [--config C2|C3|C4|C5]
+    python bench.py --gpus N --steps K --warmup W [--config C2|C3|C4|C5] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel = the screen filter; algorithmic bytes = ceil(2L/8) per read,
-SURVEY.md §8d) and `cpu_baseline` (the oracle's C restatement — kind "port" — on the host cores on a bounded sample of the
-same workload — stripes over the WHOLE read and gap range, `parity_sample_ranges` — also checked bit-for-bit against the GPU's results on that sample).  At N=1 the default run appends `extras`:
-the same step on C2 (configs[1]) and on C5 (configs[4]: + mate-pair library IS 5000, k in {31,41,51}), each in a child process.
+A plain run sets up, warms up, times the K steps, writes --dump-outputs / --dump-contigs if asked and prints ONE JSON line on rank 0:
+the headline figure, `roofline` (dominant kernel = the screen filter; algorithmic bytes = ceil(2L/8) per read), and
+the counts, kernel spans and assembly statistics of the timed steps themselves.
+--full adds everything that takes work of its own behind the timed region: `cpu_baseline` (the oracle's C restatement — kind "port" —
+on the host cores on a bounded sample of the same workload — stripes over the WHOLE read and gap range, `parity_sample_ranges` — also
+checked bit-for-bit against the GPU's results on that sample; --no-cpu skips it), the truth check of every closed gap
+(`closed_truth_check`, `gaps_closed_correct`), the census of the open gaps, the merge round over all open gaps where the step runs
+without it (`contig_merge_round_all_gaps`), and at N=1 on the default configuration `extras` (--no-extras skips them): the same step
+on C2 (configs[1]), on C2 with planted repeats and on C5 (configs[4]: + mate-pair library IS 5000, k in {31,41,51}), each in a child
+process, and the CLI end to end on C3-sized files.
 """
 import argparse
 import ctypes as C
@@ -81,9 +87,14 @@ def parse_args():
                     help="the contig-merge round (assemble_gaps.py:301-306) for the gaps the first pick leaves open, on the device, INSIDE the timed step: "
                          "auto (default) = on where a library can span the gaps (the configurations with the mate-pair library: C5, C2RM) — with the "
                          "300-bp library alone every 2-kb gap stays open by construction, nothing can be closed by merging, and the round over all "
-                         "gaps is measured once behind the timed region instead (`contig_merge_round_all_gaps`); host = the host twin, untimed")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the C2 / C5 child runs that the default N=1 run appends as `extras`")
+                         "gaps is measured once behind the timed region instead (`contig_merge_round_all_gaps`, with --full); host = the host twin, "
+                         "untimed (needs --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, behind the timed region: the CPU baseline and its parity sample, the "
+                         "truth check of the closed gaps, the open-gap census, the merge round over all open gaps and (N=1, default configuration) "
+                         "the extras")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baseline and its parity sample")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the child runs that the default N=1 run appends as `extras`")
     ap.add_argument("--e2e-only", default="", help="run only the file-based end-to-end extra on this configuration (C2 / C3) and print its object")
     ap.add_argument("--dump-contigs", default="", help="rank 0 writes the gathered contigs (sorted) of the last step to this JSON file")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
@@ -94,6 +105,8 @@ def parse_args():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.gpus != 1:
         ap.error("--dump-outputs needs --gpus 1 (a rank holds the results of its own gaps only)")
+    if args.merge_round == "host" and not args.full:
+        ap.error("--merge-round host runs the host twin behind the timed region: add --full")
     return args
 
 
@@ -129,7 +142,7 @@ def main():
         launch_ranks(args)
     out, rank, world = run(args)
     # the extras run in child processes AFTER this process has released its device memory (run()'s tensors and contexts are gone)
-    if rank == 0 and world == 1 and args.config == "C4" and not args.no_extras and not args.no_cpu and not args.reads and args.mp_reads < 0:
+    if args.full and rank == 0 and world == 1 and args.config == "C4" and not args.no_extras and not args.no_cpu and not args.reads and args.mp_reads < 0:
         import gc
         gc.collect()
         torch.cuda.empty_cache()
@@ -364,14 +377,15 @@ def run(args):
     ctg = res.contigs
     n_closed, n_ctg_all, gaps_with_contig = n_closed_local, n_ctg, int(len(np.unique(ctg["gap"])))
     gather_ms = None
-    # ground truth (untimed): the sequence picked for every closed gap of this rank against the true bases behind the planted gap
     seq_host = res.seq
-    truth = truth_check(cfg0, gaps, flanks, ctg, seq_host, res.best, GapFill)
-    assert truth["closed"] == n_closed_local, (truth["closed"], n_closed_local)
-    n_correct = truth["correct"]
-    census = None
-    if not multi and n_closed_local:      # (runs that close gaps at all: with the 300-bp library alone every 2-kb gap is a coverage hole)
-        census = open_gap_census(cfg0, gaps, ctg, seq_host, res.best, GapFill)
+    truth, n_correct, census = None, 0, None
+    if args.full:
+        # ground truth (untimed): the sequence picked for every closed gap of this rank against the true bases behind the planted gap
+        truth = truth_check(cfg0, gaps, flanks, ctg, seq_host, res.best, GapFill)
+        assert truth["closed"] == n_closed_local, (truth["closed"], n_closed_local)
+        n_correct = truth["correct"]
+        if not multi and n_closed_local:      # (runs that close gaps at all: with the 300-bp library alone every 2-kb gap is a coverage hole)
+            census = open_gap_census(cfg0, gaps, ctg, seq_host, res.best, GapFill)
     merge_round = None
     if res.merge is not None:
         # The reference merges a gap's contigs before it picks (assemble_gaps.py:301-306, 335-339).  The step picks, sends the contigs of the
@@ -381,8 +395,9 @@ def run(args):
         merge_round = dict(res.merge, inside_the_timed_step=True)
         idx = 0x7FFFFFFF - ((res.best >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64)
         by_merge = (res.best != 0) & (idx >= res.merge["contigs_before"])
-        wrong_by_merge = sum(1 for g_ in truth["wrong_gaps"] if by_merge[g_])
-        merge_round["closed_correct"] = int(by_merge.sum()) - wrong_by_merge        # (of the gaps a MERGED contig closes: equal to the true sequence)
+        if truth is not None:
+            wrong_by_merge = sum(1 for g_ in truth["wrong_gaps"] if by_merge[g_])
+            merge_round["closed_correct"] = int(by_merge.sum()) - wrong_by_merge        # (of the gaps a MERGED contig closes: equal to the true sequence)
         merge_round["gaps_closed_without_merging"] = int((res.best != 0).sum() - by_merge.sum())
     elif merge_mode == "host" and not multi and n_closed_local and n_gaps - n_closed_local <= max(1000, n_gaps // 4):
         # the host twin of the round (MergeContigs.merge_sets: two batched GPU calls + host path search), AFTER the timed region: comparison runs
@@ -477,8 +492,11 @@ def run(args):
             "closed_truth_check": {"what": "the picked sequence of EVERY closed gap (pick_contigs.py:341-349 slice of the winning contig) compared with the "
                                            "true bases behind the planted N-run, regenerated from include/gf_synth.h: genome[start-5 : end+6] on the forward "
                                            "strand, genome[start-6 : end+5] when the contig is reverse-complemented (the reference's slice keeps one anchor base)",
-                                   "closed": n_closed, "correct": n_correct, "wrong_on_rank0": truth["wrong"][:8], "wrong_causes_rank0": truth["causes"]},
+                                   "closed": n_closed, "correct": n_correct, "wrong_on_rank0": truth["wrong"][:8], "wrong_causes_rank0": truth["causes"]}
+                                  if truth is not None else None,
         }
+        if truth is None:       # (no truth check without --full: nothing in the line says how many closed gaps are correct)
+            del out["gaps_closed_correct_per_s"], out["counts"]["gaps_closed_correct"], out["closed_truth_check"]
         # the assembly's algorithmic bytes ("report bytes anyway"): 38 B x pool reads in + 2 x 20 B x distinct k-mers
         # (16-B key + 4-B count, written once, read once) + contig bases out, per (k, kv) pass; LDS/latency-bound, so no roofline claim
         asm_ms = phases["assemble"]
@@ -512,10 +530,10 @@ def run(args):
                                    "bytes_sent_per_rank_and_step": int((world - 1) * (n_lib_ * pipe.slot_cap * rb + n_lib_ * n_gaps * 4)),
                                    "collectives_per_step": 2 + n_lib_,
                                    "collectives": "1 all-gather (counts) + 1 all-to-all (slots) + 1 all-gather per library (second-hop rows)"}
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, libs, flanks, gaps, L, kk, asm_pool_t, asm_off_t, ctg, d_seq, n_seq, d_best, step_s,
                                                n_screened, B, rb, merge_n0=res.merge["contigs_before"] if res.merge is not None else None)
-    if rank == 0 and merge_mode == "auto" and not merge_on and not multi and kk:
+    if args.full and rank == 0 and merge_mode == "auto" and not merge_on and not multi and kk:
         # no library spans the gaps (C2 / C3 / C4): the step above ran without the merge round; ONE more step with it, behind the timed region
         # (and behind every check of the timed steps' results), says what merging every open gap's contigs costs and yields — the reference
         # merges every gap (assemble_gaps.py:301-306)
@@ -760,7 +778,7 @@ def child_run(argv):
     process that has touched the GPU)."""
     r = None
     try:
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--no-extras", "--no-cpu"] + argv, stdout=subprocess.PIPE,
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--full", "--no-extras", "--no-cpu"] + argv, stdout=subprocess.PIPE,
                            stderr=subprocess.PIPE, timeout=900, env=dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0"))
         d = json.loads(r.stdout.decode().strip().splitlines()[-1])
         return {key: d[key] for key in ("value", "ms_per_step", "steps", "warmup", "gaps_per_s", "gaps_closed_per_s", "gaps_closed_correct_per_s",
@@ -774,7 +792,7 @@ def child_run(argv):
 
 
 def extra_headline(d, argv):
-    """A child run's object cut to its headline figures for the result line; `python bench.py --no-extras --no-cpu <argv>` prints it whole."""
+    """A child run's object cut to its headline figures for the result line; `python bench.py --full --no-extras --no-cpu <argv>` prints it whole."""
     if "error" in d:
         return dict(d, argv=argv)
     counts = d.get("counts", {})

@@ -307,8 +307,8 @@ def test_two_rank_owner_assembly_equals_the_single_process_run(tmp_path, config,
     """SURVEY.md §8e / north_star: the HIP kernels on two ranks (sharing this box's one GPU, gloo for the collectives), reads split,
     pools exchanged to the gap owners — the gathered contigs and the closed count equal the single-process run over all reads."""
     one, two = str(tmp_path / "one.json"), str(tmp_path / "two.json")
-    a = _bench(["--config", config, "--steps", "1", "--warmup", "0", "--no-cpu", "--no-extras", "--dump-contigs", one] + extra)
-    b = _bench(["--config", config, "--steps", "1", "--warmup", "0", "--no-cpu", "--no-extras", "--dump-contigs", two] + extra,
+    a = _bench(["--config", config, "--steps", "1", "--warmup", "0", "--full", "--no-cpu", "--no-extras", "--dump-contigs", one] + extra)
+    b = _bench(["--config", config, "--steps", "1", "--warmup", "0", "--full", "--no-cpu", "--no-extras", "--dump-contigs", two] + extra,
                env_extra={"GF_BENCH_BACKEND": "gloo", "GF_BENCH_ONE_GPU": "1"}, nproc=2)
     ja, jb = json.load(open(one)), json.load(open(two))
     assert ja["contigs"] == jb["contigs"] and len(ja["contigs"]) > 100
@@ -332,7 +332,7 @@ def test_two_rank_rccl_equals_single_process(tmp_path, config, extra):
     exact-size all-to-all of the owner exchange, the all-reduces of the results and the final gather on device tensors.  Same contigs,
     pools and closed gaps as the single-process run over all reads (one owner per gap, assemble_gaps.py:296-299)."""
     one, two = str(tmp_path / "one.json"), str(tmp_path / "two.json")
-    argv = ["--config", config, "--steps", "2", "--warmup", "1", "--no-cpu", "--no-extras"] + extra
+    argv = ["--config", config, "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-extras"] + extra
     a = _bench(argv + ["--dump-contigs", one])
     b = _bench(argv + ["--dump-contigs", two], env_extra={"GF_BENCH_BACKEND": "nccl", "HSA_ENABLE_IPC_MODE_LEGACY": "0"}, nproc=2)
     ja, jb = json.load(open(one)), json.load(open(two))
@@ -347,7 +347,7 @@ def test_exact_size_exchange_equals_the_padded_slots(tmp_path):
     """The owner exchange with exact split sizes and the counts inside the one all-to-all (default) against the equal-slot form with
     its all-gather of counts (GF_XCHG=slots), two ranks on this box's GPU over gloo: same contigs; the exact form sends fewer bytes."""
     one, two = str(tmp_path / "one.json"), str(tmp_path / "two.json")
-    argv = ["--config", "C5", "--reads", "4000000", "--mp-reads", "2000000", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-extras"]
+    argv = ["--config", "C5", "--reads", "4000000", "--mp-reads", "2000000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu", "--no-extras"]
     env = {"GF_BENCH_BACKEND": "gloo", "GF_BENCH_ONE_GPU": "1"}
     a = _bench(argv + ["--dump-contigs", one], env_extra=env, nproc=2)
     b = _bench(argv + ["--dump-contigs", two], env_extra=dict(env, GF_XCHG="slots"), nproc=2)
@@ -364,7 +364,7 @@ def test_rccl_branch_runs_at_world_one_and_changes_nothing(tmp_path, config, ext
     all_gather_into_tensor of the counts, all_to_all_single of the slots, device merge), all-reduces of the results, final gather —
     with world size 1, on device tensors.  Same contigs, pools and closed gaps as the plain single-process run."""
     one, two = str(tmp_path / "one.json"), str(tmp_path / "two.json")
-    argv = ["--config", config, "--steps", "2", "--warmup", "0", "--no-cpu", "--no-extras"] + extra
+    argv = ["--config", config, "--steps", "2", "--warmup", "0", "--full", "--no-cpu", "--no-extras"] + extra
     a = _bench(argv + ["--dump-contigs", one])
     b = _bench(argv + ["--dump-contigs", two], env_extra={"GF_BENCH_FORCE_EXCHANGE": "1", "GF_BENCH_BACKEND": "nccl", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29633"})
     ja, jb = json.load(open(one)), json.load(open(two))
@@ -380,7 +380,7 @@ def test_stream_and_layout_variants_of_the_step_change_nothing(tmp_path, env):
     on a second stream beside the filter) or change what the tagger streams (the 32-byte records instead of their key column) leave contigs,
     counts and closed gaps as they are — three steps in a row, so that the pipelined tagger's hand-over between steps is exercised."""
     one, two = str(tmp_path / "one.json"), str(tmp_path / "two.json")
-    argv = ["--config", "C5", "--reads", "4000000", "--mp-reads", "2000000", "--steps", "3", "--warmup", "1", "--no-cpu", "--no-extras"]
+    argv = ["--config", "C5", "--reads", "4000000", "--mp-reads", "2000000", "--steps", "3", "--warmup", "1", "--full", "--no-cpu", "--no-extras"]
     a = _bench(argv + ["--dump-contigs", one])
     b = _bench(argv + ["--dump-contigs", two], env_extra=env)
     ja, jb = json.load(open(one)), json.load(open(two))
@@ -415,7 +415,7 @@ def test_full_size_config_sample_parity(config):
     offset 4 GiB of the packed reads / the records / the key column, the shard boundaries of 2 / 4 / 8 ranks, seeded places —, the
     merged pools' assembly of 256 gaps drawn over the whole gap list (first and last included) at every (k, kv) and the closed flags
     equal the oracle / the host picker; every gap recruits reads and yields contigs."""
-    d = _bench(["--config", config, "--steps", "1", "--warmup", "0", "--no-extras"])
+    d = _bench(["--config", config, "--steps", "1", "--warmup", "0", "--full", "--no-extras"])
     cb = d["cpu_baseline"]
     assert cb["parity_recruit"] and cb["parity_assembly"] and cb["parity_pick"] and cb["parity_on_sample"], cb
     assert cb["sample_hits"] > 1000 and cb["sample_contigs"] > 100
@@ -464,7 +464,7 @@ def test_c2_full_size_complete_parity():
     oracle's k-mer screen and alignment tagger, every one of the 1 000 gaps' pools through the oracle's assembly and the host picker —
     hit lists, contigs and pick words of the GPU step equal them (collect_reads_for_gaps.py:68-263, collect_discordant_low_mapq_reads.py:31-84
     for the recruit rules)."""
-    d = _bench(["--config", "C2", "--steps", "1", "--warmup", "0", "--no-extras", "--cpu-sample-reads", "-1", "--cpu-sample-gaps", "-1"], timeout=2400)
+    d = _bench(["--config", "C2", "--steps", "1", "--warmup", "0", "--full", "--no-extras", "--cpu-sample-reads", "-1", "--cpu-sample-gaps", "-1"], timeout=2400)
     cb = d["cpu_baseline"]
     assert cb["parity_sample"] == "complete", cb["parity_sample"]
     w = cb["parity_sample_ranges"]

@@ -29,6 +29,6 @@ for c in $CFGS; do
   esac
 done
 if [[ " $CFGS " == *" c4 "* ]]; then
-  cd $R && timeout 900 python3 bench.py --steps 20 --warmup 5 > $S/${RND}_bench_default_n1.json 2> $S/${RND}_bench_default_n1.err < /dev/null
+  cd $R && timeout 900 python3 bench.py --steps 20 --warmup 5 --full > $S/${RND}_bench_default_n1.json 2> $S/${RND}_bench_default_n1.err < /dev/null
 fi
 ls -la $S
