@@ -16,15 +16,16 @@ What the reference does with files between processes —
     gf_assemble_multi_dev                                      every (k, kv) pair (a-6)
     gf_pick_anchored2_dev                                      closed gaps (f-1)
     gf_merge_open_gaps_dev + gf_pick_anchored2_from_dev        contig merger for the gaps still open, second pick (f-3; merge_in_step)
-    gf_contig_kmer_table_dev + gf_recruit_by_contigs_dev       second assembly round for the gaps still open (second_round):
+    gf_contig_kmer_table_dev + gf_recruit_by_contigs_dev       second assembly round for the gaps still open (second_round.py):
       + gf_round2_pools_dev + gf_assemble_multi_dev            both-unmapped pairs recruited by the round-1 contigs' k-mers, pools
       + gf_contigs_append_dev + gf_pick_*_from_dev             = round-1 rows + recruits, assembled and picked again
-    gf_rescue_hq_keys_dev + gf_rescue_bridges_dev              rescue round for the gaps still open after the merge pick (rescue_round):
+    gf_rescue_hq_keys_dev + gf_rescue_bridges_dev              rescue round for the gaps still open after the merge pick (rescue_round.py):
       + gf_merge_rescue_dev + gf_pick_*_from_dev               high-quality reads clipped at two contigs join the own contigs, merge, pick at 15
-    gf_pick_extended[_aligned]_dev                             partial fills of the gaps every pick left open (extended_fill)
+    gf_pick_extended[_aligned]_dev                             partial fills of the gaps every pick left open (extended_fill.py)
 
-`Pipeline` owns the sizing pass (capacities follow what the libraries actually recruit), every intermediate buffer, the stream
-wiring and — in a multi-rank run — the one exchange step.  Two callers: bench.py (libraries synthesised on the
+`Pipeline` owns the sizing pass (capacities follow what the libraries actually recruit), every buffer of the core step, the stream
+wiring and — in a multi-rank run — the one exchange step; an optional round keeps its buffers, sizing, launches and
+results in its own module, and the step calls the rounds that are switched on by name.  Two callers: bench.py (libraries synthesised on the
 device; `step()` is what it times) and the CLI (`gappadder_amd/device_collect.py`: libraries ingested from BAM + FASTQ files,
 per-gap FASTQ / FASTA files WRITTEN FROM the results).  torch is the device-memory and collective plumbing; every kernel is
 behind the C ABI.  There is no CPU path: `_lib.lib()` raises when libgapfill_hip.so is missing."""
@@ -35,6 +36,9 @@ import numpy as np
 import torch
 
 from . import _lib as B
+from . import extended_fill as EXT
+from . import rescue_round as RS
+from . import second_round as R2
 from . import sharding as SH
 
 # counters of a library (device u32 words of `d_cnt`): 0 screen hits, 4 tagger hits, 8 second-hop hits, 12 pool keys,
@@ -63,8 +67,9 @@ class DeviceLibrary:
 
 
 class Results:
-    """What one step left on the device, fetched once (contigs, their bases, the pick words, the pools when asked for)."""
-    pass
+    """What one step left on the device, fetched once (contigs, their bases, the pick words, the pools when asked for).  The fields of
+    the merge round and of the optional rounds are None unless the round ran."""
+    merge = rescue = rescue_first = round2 = round2_first = round2_reads = extended = ext = ext_bases = None
 
 
 class Pipeline:
@@ -83,52 +88,28 @@ class Pipeline:
         anchor_mode: how every pick of the step anchors the flanks on the contigs — "exact" anchors (gf_pick_anchored2_dev) or "align",
         seed-and-extend of the whole flanks (gf_pick_aligned_dev; `anchors` are then the score thresholds); with "align" the Results
         carry `ctg_pick` (gf_ctg_pick per contig) and `align_dropped` / `align_seed_overflow` (gf_pick_aligned_dev's d_stats).
-        second_round: the reference's second assembly round (assemble_gaps.py:344-351) inside the step for the gaps the first pick
-        leaves open: the pairs with both mates unmapped (FLAG & 12 == 12) that share a canonical k-mer (the smallest k of k_pairs in
-        16..64) with a gap's round-1 contigs are appended to its pool, the gap is assembled again at every (k, kv) and picked over the
-        round-2 contigs only (appended after round 1's; Results.round2 / round2_first).  Single rank, without merge_in_step.
-        The candidate pairs are listed from the libraries' alignment records once, in prepare(): like the key column, they assume the
-        records do not change after prepare() (a caller that rewrites d_recs prepares a new Pipeline).
-        extended_fill: the reference's last stage (pick_extended_contigs, assemble_gaps.py:367-368) after the last pick of the step: every
-        gap still open is filled from each side as far as a contig reaches, the parts joined by "NN" (gf_pick_extended_dev; the shorter
-        anchor, anchors[-1], in anchor_mode; over the round-2 contigs with second_round, else over all of the step's contigs).  Results.ext
-        (gf_ext_pick per gap), .ext_bases and .extended (counts); Pipeline.extended_sequences decodes them.  Single rank.  ext_base_cap:
-        bytes of the fill buffer (default: the contig bases' capacity + 2 per gap, which no fill set can exceed); fetch() raises when
-        the fills do not fit.
-        rescue_round: the reference's rescue round (assemble_gaps.py:357-366) after the merge round's pick: per gap still
-        open, its high-quality reads (the tagger hits of MAPQ-60 records) that align clipped to two or more of its merged contigs are
-        bridges; they are appended as records with k = kv = RESCUE_MARK, the gap's own contigs and its bridges are merged again (merged
-        contigs appended with k = kv = 0), and the records the round appended are picked at anchors[-1] (Results.rescue / rescue_first).
-        Needs merge_in_step; single rank, without second_round.  Like second_round's candidates, the read ids assume that the libraries'
-        read names are distinct."""
-        if anchor_mode not in ("exact", "align"):
-            raise ValueError("anchor_mode %r: 'exact' or 'align'" % (anchor_mode,))
-        self.rescue_round = bool(rescue_round)
-        if self.rescue_round:
-            if not merge_in_step:
-                raise ValueError("rescue_round needs merge_in_step: the reads are aligned to the merged contigs")
-            if int(world) > 1 or force_exchange:
-                raise ValueError("rescue_round runs on a single rank")
-            if second_round:
-                raise ValueError("rescue_round with second_round: the order of the rounds is not settled")
-        self.second_round = bool(second_round)
-        if self.second_round:
-            if int(world) > 1 or force_exchange:
-                raise ValueError("second_round runs on a single rank")
-            if merge_in_step:
-                raise ValueError("second_round with merge_in_step: the order of the merge and the second round is not settled")
-            ks = [int(a) for a, _ in k_pairs if 16 <= int(a) <= 64]
-            if not ks:
-                raise ValueError("second_round needs a k in 16..64 among k_pairs")
-            self.k_round2 = min(ks)
+        second_round (second_round.py), rescue_round (rescue_round.py), extended_fill with ext_base_cap (extended_fill.py): the
+        reference's later stages inside the step, each described in its module; in the step they run in this order after the merge
+        round's pick."""
+        # what the options exclude, before anything touches gf or the library
+        single_rank = int(world) == 1 and not force_exchange
+        k_round2 = min([int(a) for a, _ in k_pairs if 16 <= int(a) <= 64], default=None)
+        for bad, why in ((anchor_mode not in ("exact", "align"), "anchor_mode %r: 'exact' or 'align'" % (anchor_mode,)),
+                         (rescue_round and not merge_in_step, "rescue_round needs merge_in_step: the reads are aligned to the merged contigs"),
+                         (rescue_round and not single_rank, "rescue_round runs on a single rank"),
+                         (rescue_round and second_round, "rescue_round with second_round: the order of the rounds is not settled"),
+                         (second_round and not single_rank, "second_round runs on a single rank"),
+                         (second_round and merge_in_step, "second_round with merge_in_step: the order of the merge and the second round is not settled"),
+                         (second_round and k_round2 is None, "second_round needs a k in 16..64 among k_pairs"),
+                         (extended_fill and not single_rank, "extended_fill runs on a single rank"),
+                         (extended_fill and len(k_pairs) > B.EXT_MAX_PAIRS, "extended_fill: at most %d (k, kv) pairs" % B.EXT_MAX_PAIRS)):
+            if bad:
+                raise ValueError(why)
         self.anchor_mode = anchor_mode
-        self.extended_fill = bool(extended_fill)
-        if self.extended_fill:
-            if int(world) > 1 or force_exchange:
-                raise ValueError("extended_fill runs on a single rank")
-            if len(k_pairs) > B.EXT_MAX_PAIRS:
-                raise ValueError("extended_fill: at most %d (k, kv) pairs" % B.EXT_MAX_PAIRS)
-        self.ext_base_cap_arg = int(ext_base_cap) if ext_base_cap is not None else None
+        # the optional rounds, in the order the step runs them; None: off
+        self.round2 = R2.SecondRound(self, k_round2) if second_round else None
+        self.rescue = RS.RescueRound(self) if rescue_round else None
+        self.ext = EXT.ExtendedFill(self, int(ext_base_cap) if ext_base_cap is not None else None) if extended_fill else None
         self.gf, self.lib, self.h = gf, B.lib(), gf.handle
         self.n_gaps, self.L, self.kk = int(n_gaps), int(read_len), [(int(a), int(b)) for a, b in k_pairs]
         self.rb = self.lib.gf_packed_read_bytes(self.L)
@@ -137,6 +118,7 @@ class Pipeline:
         self.multi = self.world > 1 or bool(force_exchange)
         self.coll_dev = self.dev if backend == "nccl" else torch.device("cpu")
         self.min_count, self.min_contig, self.anchors = int(min_count), int(min_contig), tuple(int(a) for a in anchors)
+        self.anchor_pair = (self.anchors[0], self.anchors[1] if len(self.anchors) > 1 else 0)       # a pick's two rounds; 0: no second one
         self.clip_dist, self.anchor_mapq = int(clip_dist), int(anchor_mapq)
         self.k_screen = int(k_screen) if k_screen else (min(a for a, _ in self.kk) if self.kk else 31)
         self.keep_read_ids = bool(keep_read_ids)
@@ -420,10 +402,11 @@ class Pipeline:
             # block + an all-gather of the counts (the form of rounds 2-5)
             self.exact_exchange = os.environ.get("GF_XCHG", "exact") != "slots"
             if self.exact_exchange:
-                self.xchg_rows = SH.exchange_rows_table(per_dst, self.coll_dev, self.backend)
-                self.xchg = SH.ExactOwnerExchange(world, self.rank, n_lib, n_gaps, self.xchg_rows, rb, dev, self.backend)
+                rows = SH.exchange_rows_table(per_dst, self.coll_dev, self.backend)
+                self.xchg = SH.ExactOwnerExchange(world, self.rank, n_lib, n_gaps, rows, rb, dev, self.backend)
             else:
                 self.xchg = SH.OwnerExchange(world, n_lib, n_gaps, self.slot_cap, rb, dev, self.backend)
+            self.xchg_kernels = self._exchange_kernels()
         else:
             self.slot_cap = self.lib_cap
             self.merged_cap = max(4096, int(1.25 * sum(self.rows_lib)) + 1024)
@@ -433,286 +416,84 @@ class Pipeline:
         # (contigs: a few dozen per gap and k on an i.i.d. draft; the deep pools of a repeat-bearing draft fragment into many more:
         # room grows with the pooled reads)
         nk = max(1, len(self.kk))
-        self.contig_cap = (64 * n_gaps + 4096 + sum(self.rows_lib) // 4) * nk
-        self.seq_cap = (24576 * n_gaps + (1 << 20) + 32 * sum(self.rows_lib)) * nk
-        self.d_ctg = self._u8(self.contig_cap * 32)
-        self.d_seq = self._u8(self.seq_cap)
+        self._alloc_contig_list(*self.contig_caps(sum(self.rows_lib)))
         self.d_gap_err = torch.zeros(max(1, n_gaps), dtype=torch.int32, device=dev)
         self.d_best = torch.zeros(max(1, n_gaps), dtype=torch.int64, device=dev)
         # assembly counters: 0 contigs (u32), 2-3 contig bases (u64), 4 gaps closed (u32)
         self.d_acnt = torch.zeros(8, dtype=torch.int32, device=dev)
         self.ap = self.d_acnt.data_ptr()
         self.d_mstats = torch.zeros(B.MG_WORDS, dtype=torch.int32, device=dev)      # statistics of the merge round (gf_merge_open_gaps_dev)
-        if self.anchor_mode == "align":        # per contig the selection of the align-mode pick, and its two statistics words
-            self.d_ctg_pick = self._u8(self.contig_cap * B.CTG_PICK.itemsize)
+        if self.anchor_mode == "align":        # the align-mode picks' two statistics words (their selection per contig: _alloc_contig_list)
             self.d_pstats = torch.zeros(2, dtype=torch.int32, device=dev)
         pr = np.zeros(1, dtype=B.OVL_PARAMS)
         pr[0] = tuple(self.gf.MERGER_PARAMS)[:7] + (0.0,)       # ContigsMerger's options as GAPPadder sets them (MergeContigs.py:75)
         self.merge_params = pr
         self.k_arr = (C.c_int * nk)(*[a for a, _ in self.kk])
         self.kv_arr = (C.c_int * nk)(*[b for _, b in self.kk])
-        if self.extended_fill:
-            self._ext_alloc()
         torch.cuda.synchronize()
-        if self.second_round:
-            self._prepare_round2()
-            if self.extended_fill:
-                self._ext_alloc()       # (the round may have grown the contig buffers)
-        if self.rescue_round:
-            self._prepare_rescue()
-            if self.extended_fill:
-                self._ext_alloc()
+        if self.round2 is not None:
+            self.round2.prepare()
+        if self.rescue is not None:
+            self.rescue.prepare()
+        if self.ext is not None:        # (after the rounds: either may have grown the contig list its buffer is sized by)
+            self.ext.prepare()
         if self.tag_ahead:          # the first step's tagger pass (untimed, like a warm-up step's)
             assert all(lb.second_stream for lb in self.libs), "tag_ahead needs DeviceLibrary(tag_ctx=...)"
             self._on_stream(lambda: [self.tagger(lb) for lb in self.libs])
             self.sync()
         self.prepared = True
 
-    def _ext_alloc(self):
-        cap = self.ext_base_cap_arg if self.ext_base_cap_arg is not None else self.seq_cap + 2 * self.n_gaps
-        if getattr(self, "ext_base_cap", None) == cap:
-            return
-        self.ext_base_cap = cap
-        self.d_ext = self._u8(self.n_gaps * B.EXT_PICK.itemsize)
-        self.d_ext_bases = self._u8(cap)
-        self.d_ext_stats = torch.zeros(B.EXT_WORDS, dtype=torch.int32, device=self.dev)
-
-    def _extend(self):
-        """Enqueued after the last pick of the step: the partial fills of the gaps d_best leaves open."""
-        first = self.d_r2st.data_ptr() + 4 * B.R2_FIRST if self.second_round else None
-        fn, what = ((self.lib.gf_pick_extended_aligned_dev, "gf_pick_extended_aligned_dev") if self.anchor_mode == "align"
-                    else (self.lib.gf_pick_extended_dev, "gf_pick_extended_dev"))
-        self._chk(fn(self.h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), self.anchors[-1], self.k_arr, self.kv_arr,
-                     len(self.kk), first, self.d_best.data_ptr(), self.d_ext.data_ptr(), self.d_ext_bases.data_ptr(), self.ext_base_cap,
-                     self.d_ext_stats.data_ptr()), what)
-
-    # ---- second assembly round: sizing (untimed) ---------------------------------------------------------------------------
-    def _r2_caps(self, rows):
+    def contig_caps(self, rows):
+        """Records and bases of the contig list of an assembly over `rows` pooled reads."""
         nk = max(1, len(self.kk))
         return (64 * self.n_gaps + 4096 + rows // 4) * nk, (24576 * self.n_gaps + (1 << 20) + 32 * rows) * nk
 
-    def _r2_alloc(self):
-        dev = self.dev
-        self.d_r2tab = self._u8(24 << self.r2_log2)
-        self.d_r2keys = torch.empty(self.r2_key_cap, dtype=torch.int64, device=dev)
-        self.d_r2sorted = torch.empty(self.r2_key_cap, dtype=torch.int64, device=dev)
-        self.d_r2work = torch.empty(int(self.lib.gf_round2_work_words(self.r2_key_cap, self.n_gaps)), dtype=torch.int32, device=dev)
-        self.d_r2pool = self._u8(self.r2_pool_cap * self.rb + 64)
-        self.d_ctg2 = self._u8(self.r2_ctg_cap * 32)
-        self.d_seq2 = self._u8(self.r2_seq_cap)
+    def _alloc_contig_list(self, contig_cap, seq_cap):
+        """The step's contig list: records, bases and (align mode) the picks' selection per contig."""
+        self.contig_cap, self.seq_cap = int(contig_cap), int(seq_cap)
+        self.d_ctg = self._u8(self.contig_cap * 32)
+        self.d_seq = self._u8(self.seq_cap)
+        if self.anchor_mode == "align":
+            self.d_ctg_pick = self._u8(self.contig_cap * B.CTG_PICK.itemsize)
 
-    def _prepare_round2(self):
-        """Candidates of every library (they depend on the records alone: listed once, like the key column — the records must not change
-        after prepare()), then the step with the round
-        run again and again, every buffer grown to the exact count the run before reported, until nothing is beyond a capacity."""
-        lib, h, dev = self.lib, self.h, self.dev
-        if len(self.libs) > B.R2_MAX_LIBS:
-            raise ValueError("second_round: at most %d libraries" % B.R2_MAX_LIBS)
-        if not self.kk or not self.assemble_in_step:
-            raise ValueError("second_round runs inside the step's assembly (k_pairs and assemble_in_step)")
-        for lb in self.libs:
-            lb.d_r2bits = self._u8(((lb.n_reads // 2 + 31) // 32) * 4)
-            lb.d_r2n = torch.zeros(4, dtype=torch.int32, device=dev)
-            lb.r2_cap, lb.d_r2pairs = 0, torch.empty(1, dtype=torch.int32, device=dev)
-            for _ in range(2):
-                torch.cuda.synchronize()
-                self._chk(lib.gf_both_unmapped_reads_dev(h, lb.d_recs.data_ptr(), lb.n_recs, lb.n_reads, lb.d_r2bits.data_ptr(), lb.d_r2pairs.data_ptr(),
-                                                         lb.r2_cap, lb.d_r2n.data_ptr()), "gf_both_unmapped_reads_dev")
-                self.gf.sync()
-                n = int(lb.d_r2n[0])
-                if n <= lb.r2_cap:
-                    break
-                lb.r2_cap, lb.d_r2pairs = n, torch.empty(n + 1, dtype=torch.int32, device=dev)
-        self.r2_lib_ptrs = (C.c_void_p * len(self.libs))(*[lb.d_reads.data_ptr() for lb in self.libs])
-        self.d_r2st = torch.zeros(B.R2_WORDS, dtype=torch.int32, device=dev)
-        self.d_acnt2 = torch.zeros(8, dtype=torch.int32, device=dev)
-        self.d_gap_err2 = torch.zeros(max(1, self.n_gaps), dtype=torch.int32, device=dev)
-        # round-2 rows per gap, then their offsets (the pool_off of the round-2 assembly)
-        self.d_r2rows_all = torch.zeros(2 * (self.n_gaps + 1), dtype=torch.int64, device=dev)
-        self.d_r2rows, self.d_r2off = self.d_r2rows_all[:self.n_gaps + 1], self.d_r2rows_all[self.n_gaps + 1:]
-        self.r2_log2, self.r2_key_cap, self.r2_pool_cap = 12, 4096, 4096
-        self.r2_ctg_cap, self.r2_seq_cap = self._r2_caps(0)
-        self._r2_alloc()
-        big = int(self.max_pool_rows)
-        for attempt in range(8):
+    def _size_round(self, name, grow):
+        """Sizing of an optional round: the step with the round runs on the hits prepare() left until grow() — which reads the round's
+        counters and enlarges what they outgrew — reports that everything fitted."""
+        for _ in range(8):
             torch.cuda.synchronize()
             self._on_stream(lambda: self._step(recruited=True))
             self.sync()
             torch.cuda.synchronize()
-            st = self.d_r2st.cpu().numpy().view(np.uint32)
-            a1, a2 = self.d_acnt.cpu().numpy(), self.d_acnt2.cpu().numpy()
-            n2, s2 = int(a2[0]), int(a2[2:4].view(np.uint64)[0])
-            rows = int(st[B.R2_ROWS:B.R2_ROWS + 2].view(np.uint64)[0])
-            grown = False
-            need_log2 = max(12, int(2 * int(st[B.R2_KMERS]) + 16).bit_length())
-            if need_log2 > self.r2_log2 or int(st[B.R2_TAB_FULL]):
-                self.r2_log2, grown = max(need_log2, self.r2_log2 + 1), True
-            if int(st[B.R2_HITS]) > self.r2_key_cap:
-                self.r2_key_cap, grown = int(1.25 * int(st[B.R2_HITS])) + 4096, True
-            if rows > self.r2_pool_cap:
-                self.r2_pool_cap, grown = int(1.25 * rows) + 4096, True
-            if n2 > self.r2_ctg_cap or s2 > self.r2_seq_cap:
-                c2, q2 = self._r2_caps(rows)
-                self.r2_ctg_cap, self.r2_seq_cap, grown = max(c2, int(1.25 * n2)), max(q2, int(1.25 * s2)), True
-            # the step's list holds both rounds' contigs
-            n1, q1 = int(st[B.R2_FIRST]), int(a1[2:4].view(np.uint64)[0]) - (0 if int(st[B.R2_APPEND_ERR]) else s2)
-            if n1 + n2 > self.contig_cap or q1 + s2 > self.seq_cap:
-                self.contig_cap, self.seq_cap = max(self.contig_cap, int(1.25 * (n1 + n2)) + 4096), max(self.seq_cap, int(1.25 * (q1 + s2)) + (1 << 20))
-                self.d_ctg, self.d_seq = self._u8(self.contig_cap * 32), self._u8(self.seq_cap)
-                if self.anchor_mode == "align":
-                    self.d_ctg_pick = self._u8(self.contig_cap * B.CTG_PICK.itemsize)
-                grown = True
-            # the assembly's workspace bounds cover the round-2 pools too (a pool beyond asm_big_pool_reads would set its gap error)
-            sizes = self.d_r2rows[:self.n_gaps].cpu().numpy()
-            deep = int(sizes.max()) if len(sizes) else 0
-            if deep > big:
-                big = deep
-                bound = big if big <= 4096 else max(4096, self.asm_bound, int(np.percentile(sizes[sizes > 0], 99)))
-                self.gf.set_option("asm_max_pool_reads", max(1, bound))
-                self.gf.set_option("asm_big_pool_reads", max(1, min(0x1FFFFF, big)))
-                grown = True
-            if not grown:
+            if not grow():
                 break
-            self._r2_alloc()
         else:
-            raise RuntimeError("second round: the buffers keep growing")
+            raise RuntimeError("%s: the buffers keep growing" % name)
         torch.cuda.synchronize()
 
-    def _round2(self):
-        """Enqueued right after the first pick: recruitment, round-2 pools, assembly, append, pick over the round-2 contigs."""
-        lib, h, n_gaps, k = self.lib, self.h, self.n_gaps, self.k_round2
-        st = self.d_r2st.data_ptr()
-        self._chk(lib.gf_memset_dev(h, st, 0, 4 * B.R2_WORDS) or lib.gf_memset_dev(h, self.d_r2keys.data_ptr(), 0xFF, 8 * self.r2_key_cap),
-                  "gf_memset_dev")
-        self._chk(lib.gf_contig_kmer_table_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), self.d_best.data_ptr(), n_gaps,
-                                               k, self.d_r2tab.data_ptr(), self.r2_log2, st), "gf_contig_kmer_table_dev")
-        for l, lb in enumerate(self.libs):
-            self._chk(lib.gf_recruit_by_contigs_dev(h, lb.d_reads.data_ptr(), lb.d_nmask.data_ptr() if lb.d_nmask is not None else None, lb.n_reads,
-                                                    self.L, lb.d_r2pairs.data_ptr(), lb.d_r2n.data_ptr(), lb.r2_cap, l, k, self.d_r2tab.data_ptr(),
-                                                    self.r2_log2, self.d_r2keys.data_ptr(), self.r2_key_cap, st), "gf_recruit_by_contigs_dev")
-        self._chk(lib.gf_round2_pools_dev(h, self.d_r2keys.data_ptr(), self.d_r2sorted.data_ptr(), self.r2_key_cap, self.r2_lib_ptrs, len(self.libs), self.L,
-                                          self.asm_ptr, self.asm_off, self.d_best.data_ptr(), n_gaps, self.d_r2work.data_ptr(),
-                                          self.d_r2rows_all.data_ptr(), self.d_r2pool.data_ptr(), self.r2_pool_cap, st), "gf_round2_pools_dev")
-        ap2 = self.d_acnt2.data_ptr()
-        self._chk(lib.gf_assemble_multi_dev(h, self.d_r2pool.data_ptr(), None, self.d_r2off.data_ptr(), n_gaps, self.r2_pool_cap, self.L, self.k_arr,
-                                            self.kv_arr, len(self.kk), self.min_count, self.min_contig, self.d_ctg2.data_ptr(), self.r2_ctg_cap, ap2,
-                                            self.d_seq2.data_ptr(), self.r2_seq_cap, ap2 + 8, self.d_gap_err2.data_ptr()), "gf_assemble_multi_dev (round 2)")
-        self._chk(lib.gf_contigs_append_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), self.ap + 8, self.seq_cap,
-                                            self.d_ctg2.data_ptr(), ap2, self.r2_ctg_cap, self.d_seq2.data_ptr(), ap2 + 8, self.r2_seq_cap, st),
-                  "gf_contigs_append_dev")
-        first = st + 4 * B.R2_FIRST
-        a0, a1 = self.anchors[0], (self.anchors[1] if len(self.anchors) > 1 else 0)
-        if self.anchor_mode == "align":
-            self._chk(lib.gf_pick_aligned_from_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), a0, a1, first,
-                                                   self.d_best.data_ptr(), self.ap + 16, self.d_ctg_pick.data_ptr(), self.d_pstats.data_ptr()),
-                      "gf_pick_aligned_from_dev")
-        else:
-            self._chk(lib.gf_pick_anchored2_from_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), a0, a1, first,
-                                                     self.d_best.data_ptr(), self.ap + 16), "gf_pick_anchored2_from_dev")
+    def _exchange_kernels(self):
+        """The (pack, merge) pair the chosen exchange form calls (sharding.ExactOwnerExchange.run / OwnerExchange.run)."""
+        lib, h, n_gaps, n_lib, L, world = self.lib, self.h, self.n_gaps, len(self.libs), self.L, self.world
 
-    # ---- rescue round ----------------------------------------------------------------------------------------------------------
-    def _rs_alloc(self):
-        self.rs_work_bytes = int(self.lib.gf_rescue_work_bytes(self.n_gaps, self.rs_hq_cap, self.rs_seed_cap, self.rs_log2))
-        if not self.rs_work_bytes:
-            raise ValueError("rescue_round: unsupported sizes (%d gaps)" % self.n_gaps)
-        self.d_rs_work = self._u8(self.rs_work_bytes)
-        self.rs_gap_bridges = self.lib.gf_rescue_gap_bridges(self.d_rs_work.data_ptr(), self.n_gaps, self.rs_hq_cap, self.rs_seed_cap, self.rs_log2)
+        def pack(l, send, cap, cnt):
+            self._chk(lib.gf_pools_pack_for_owners_dev(h, self.pool_ptr[l], self.libs[l].d_pool_off.data_ptr(), n_gaps, L, world, self.batch,
+                                                       l, n_lib, send.data_ptr(), cap, cnt.data_ptr(), self.d_xerr.data_ptr()),
+                      "gf_pools_pack_for_owners_dev")
 
-    def _rs_args(self):
-        return self.d_rs_work.data_ptr(), self.rs_hq_cap, self.rs_seed_cap, self.rs_log2
+        def merge(recv, cap, all_cnt):
+            self._chk(lib.gf_pools_merge_dev(h, recv.data_ptr(), cap, all_cnt.data_ptr(), n_lib, world, n_gaps, L, self.rank, world,
+                                             self.batch, self.d_merged.data_ptr(), self.merged_cap, self.d_moff.data_ptr(), self.d_xerr.data_ptr()),
+                      "gf_pools_merge_dev")
 
-    def _prepare_rescue(self):
-        """The step with the round run again and again, every buffer grown to the exact count the run before reported, until nothing
-        is beyond a capacity (the HQ keys, the window table, the seeds, the step's contig list that the round appends to twice)."""
-        dev = self.dev
-        if len(self.libs) > B.R2_MAX_LIBS:
-            raise ValueError("rescue_round: at most %d libraries" % B.R2_MAX_LIBS)
-        if not self.kk or not self.assemble_in_step or self.n_gaps < 1:
-            raise ValueError("rescue_round runs inside the step's assembly (k_pairs, assemble_in_step and gaps)")
-        if not 30 <= self.L <= 1000:
-            raise ValueError("rescue_round: read length %d outside 30..1000" % self.L)
-        self.rs_reads = (C.c_void_p * len(self.libs))(*[lb.d_reads.data_ptr() for lb in self.libs])
-        self.rs_nmask = (C.c_void_p * len(self.libs))(*[lb.d_nmask.data_ptr() if lb.d_nmask is not None else None for lb in self.libs])
-        self.d_rst = torch.zeros(B.RS_WORDS, dtype=torch.int32, device=dev)
-        self.d_rsets = torch.zeros(B.MG_WORDS, dtype=torch.int32, device=dev)     # the alignment sets' dedup
-        self.d_rmstats = torch.zeros(B.MG_WORDS, dtype=torch.int32, device=dev)   # the rescue's merge
-        self.rs_hq_cap, self.rs_seed_cap, self.rs_log2 = 4096, 4096, 12
-        self._rs_alloc()
-        for attempt in range(8):
-            torch.cuda.synchronize()
-            self._on_stream(lambda: self._step(recruited=True))
-            self.sync()
-            torch.cuda.synchronize()
-            st = self.d_rst.cpu().numpy().view(np.uint32)
-            ms = self.d_rmstats.cpu().numpy().view(np.uint32)
-            a1 = self.d_acnt.cpu().numpy()
-            n, q = int(a1[0]), int(a1[2:4].view(np.uint64)[0])
-            grown = False
-            if int(st[B.RS_HQ_KEYS]) > self.rs_hq_cap:
-                self.rs_hq_cap, grown = int(1.25 * int(st[B.RS_HQ_KEYS])) + 4096, True
-            need_log2 = max(12, int(2 * int(st[B.RS_WINDOWS]) + 16).bit_length())
-            if need_log2 > self.rs_log2 or int(st[B.RS_TAB_FULL]):
-                self.rs_log2, grown = max(need_log2, self.rs_log2 + 1), True
-            if int(st[B.RS_SEEDS]) > self.rs_seed_cap:
-                self.rs_seed_cap, grown = int(1.25 * int(st[B.RS_SEEDS])) + 4096, True
-            if n > self.contig_cap or q > self.seq_cap or int(st[B.RS_APPEND_ERR]) or (int(ms[B.MG_ERR]) & 96):
-                # (the merges' own outputs count beyond the list too: MG_E_CONTIGS / MG_E_OUTSEQ)
-                self.contig_cap, self.seq_cap = int(1.5 * max(n, self.contig_cap)) + 4096, int(1.5 * max(q, self.seq_cap)) + (1 << 20)
-                self.d_ctg, self.d_seq = self._u8(self.contig_cap * 32), self._u8(self.seq_cap)
-                if self.anchor_mode == "align":
-                    self.d_ctg_pick = self._u8(self.contig_cap * B.CTG_PICK.itemsize)
-                grown = True
-            if not grown:
-                break
-            self._rs_alloc()
-        else:
-            raise RuntimeError("rescue round: the buffers keep growing")
-        torch.cuda.synchronize()
+        def pack_v(l, send, slot_base, slot_cap, cnt_base, cnt):
+            self._chk(lib.gf_pools_pack_for_owners_v_dev(h, self.pool_ptr[l], self.libs[l].d_pool_off.data_ptr(), n_gaps, L, world, self.batch,
+                                                         l, n_lib, send.data_ptr(), slot_base.data_ptr(), slot_cap.data_ptr(), cnt_base.data_ptr(),
+                                                         cnt.data_ptr(), self.d_xerr.data_ptr()), "gf_pools_pack_for_owners_v_dev")
 
-    def _rescue_keys(self):
-        """Enqueued after the pools: every library's HQ keys from its tagger hits (the tried gaps are chosen later, on the device)."""
-        lib, h = self.lib, self.h
-        self._chk(lib.gf_rescue_reset_dev(h, self.d_rs_work.data_ptr(), self.n_gaps, self.rs_hq_cap, self.rs_seed_cap, self.rs_log2, self.d_rst.data_ptr()),
-                  "gf_rescue_reset_dev")
-        for l, lb in enumerate(self.libs):
-            self._chk(lib.gf_rescue_hq_keys_dev(h, lb.d_thits.data_ptr(), lb.cp + 4 * CNT_TAG, lb.hit_cap, lb.d_recs.data_ptr(), lb.n_reads, l,
-                                                self.n_gaps, *self._rs_args(), self.d_rst.data_ptr()), "gf_rescue_hq_keys_dev")
-
-    def _rescue(self):
-        """Enqueued after the merge round's pick: bridges appended, the rescue sets merged, the appended records picked at anchors[-1]."""
-        lib, h = self.lib, self.h
-        ctg, seq, best = self.d_ctg.data_ptr(), self.d_seq.data_ptr(), self.d_best.data_ptr()
-        self._chk(lib.gf_rescue_bridges_dev(h, ctg, self.ap, self.contig_cap, seq, self.ap + 8, self.seq_cap, best, self.n_gaps, self.rs_reads,
-                                            self.rs_nmask, len(self.libs), self.L, *self._rs_args(), self.d_rsets.data_ptr(), self.d_rst.data_ptr()),
-                  "gf_rescue_bridges_dev")
-        first = self.d_rst.data_ptr() + 4 * B.RS_FIRST
-        self._chk(lib.gf_merge_rescue_dev(h, ctg, self.ap, self.contig_cap, seq, self.ap + 8, self.seq_cap, best, self.n_gaps, B._p(self.merge_params), 10,
-                                          self.merge_max_set, self.k_arr, self.kv_arr, min(16, len(self.kk)), self.d_mstats.data_ptr(), first,
-                                          self.rs_gap_bridges, self.d_rmstats.data_ptr()), "gf_merge_rescue_dev")
-        a = self.anchors[-1]
-        if self.anchor_mode == "align":
-            self._chk(lib.gf_pick_aligned_from_dev(h, ctg, self.ap, self.contig_cap, seq, a, 0, first, best, self.ap + 16, self.d_ctg_pick.data_ptr(),
-                                                   self.d_pstats.data_ptr()), "gf_pick_aligned_from_dev")
-        else:
-            self._chk(lib.gf_pick_anchored2_from_dev(h, ctg, self.ap, self.contig_cap, seq, a, 0, first, best, self.ap + 16), "gf_pick_anchored2_from_dev")
-
-    def _fetch_rescue(self, r):
-        st = self.d_rst.cpu().numpy().view(np.uint32)
-        ms = self.d_rmstats.cpu().numpy().view(np.uint32)
-        ss = self.d_rsets.cpu().numpy().view(np.uint32)
-        if int(st[B.RS_APPEND_ERR]) or int(ms[B.MG_ERR]):
-            raise RuntimeError("rescue round overflow: append flag %d, merge capacity flags %#x, %d contigs (cap %d), %d contig bases (cap %d)"
-                               % (int(st[B.RS_APPEND_ERR]), int(ms[B.MG_ERR]), r.n_contigs, self.contig_cap, r.n_seq, self.seq_cap))
-        first = int(st[B.RS_FIRST])
-        # HQ reads the round could not take: keys beyond their buffer, windows without room, seeds beyond their buffer, reads with more
-        # placements than the bridge kernel holds, contigs too long to seed, gaps with more records than the dedup takes
-        dropped = (max(0, int(st[B.RS_HQ_KEYS]) - self.rs_hq_cap) + int(st[B.RS_TAB_FULL]) + max(0, int(st[B.RS_SEEDS]) - self.rs_seed_cap)
-                   + int(st[B.RS_PLACE_OVF]) + int(st[B.RS_LONG]) + int(ss[B.MG_SKIPPED]))
-        idx = 0x7FFFFFFF - ((r.best >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64)
-        r.rescue_first = first
-        r.rescue = {"gaps_tried": int(st[B.RS_TRIED]), "hq_reads": int(st[B.RS_HQ]), "gaps_with_bridges": int(st[B.RS_GAPS_BRIDGED]),
-                    "bridges": int(st[B.RS_BRIDGES]), "merged_contigs": int(ms[B.MG_N_JOBS]), "closed": int(((r.best != 0) & (idx >= first)).sum()),
-                    "dropped": int(dropped)}
+        def merge_v(recv, slot_base, cnt_base):
+            self._chk(lib.gf_pools_merge_v_dev(h, recv.data_ptr(), slot_base.data_ptr(), cnt_base.data_ptr(), n_lib, world, n_gaps, L, self.rank,
+                                               world, self.batch, self.d_merged.data_ptr(), self.merged_cap, self.d_moff.data_ptr(),
+                                               self.d_xerr.data_ptr()), "gf_pools_merge_v_dev")
+        return (pack_v, merge_v) if self.exact_exchange else (pack, merge)
 
     def _check_cap(self, n, cap, what, lb):
         if n > cap:
@@ -730,8 +511,8 @@ class Pipeline:
             if not recruited:
                 self.hop_and_keys(lb)
             self.build_pools(lb, self.pool_ptr[l], self.lib_cap)
-        if self.rescue_round and self.kk:
-            self._rescue_keys()        # (they read this step's tagger hits: listed before the next step's tagger rewrites them)
+        if self.rescue is not None:
+            self.rescue.enqueue_keys()        # (they read this step's tagger hits: listed before the next step's tagger rewrites them)
         if self.tag_ahead:
             for lb in self.libs:        # the next step's tagger pass: behind every consumer of this step's hits, beside the assembly
                 self._chk(lib.gf_stream_wait(lb.h2, h), "gf_stream_wait")
@@ -744,40 +525,19 @@ class Pipeline:
                       or lib.gf_memset_dev(h, self.d_pstats.data_ptr(), 0, 8), "gf_memset_dev")
         if not self.need_merge:
             self.asm_ptr, self.asm_off, self.asm_rows = self.pool_ptr[0], self.libs[0].d_pool_off.data_ptr(), self.lib_cap
-        elif not self.multi:
-            for l, lb in enumerate(self.libs):
-                self._chk(lib.gf_pool_counts_dev(h, lb.d_pool_off.data_ptr(), n_gaps, self.d_libcnt.data_ptr() + 4 * l * n_gaps), "gf_pool_counts_dev")
-            self._chk(lib.gf_pools_merge_dev(h, self.d_pools.data_ptr(), self.lib_cap, self.d_libcnt.data_ptr(), n_lib, 1, n_gaps, L, 0, 1, self.batch,
-                                             self.d_merged.data_ptr(), self.merged_cap, self.d_moff.data_ptr(), self.d_xerr.data_ptr()),
-                      "gf_pools_merge_dev")
-            self.asm_ptr, self.asm_off, self.asm_rows = self.d_merged.data_ptr(), self.d_moff.data_ptr(), self.merged_cap
         else:
-            # the one exchange step: rows regrouped by owner rank, counts all-gathered, slots all-to-all'ed
-            # (equal-sized slots: no host sizes, no host sync), owners merge in (library, source rank) order
-            def pack(l, send, cap, cnt):
-                self._chk(lib.gf_pools_pack_for_owners_dev(h, self.pool_ptr[l], self.libs[l].d_pool_off.data_ptr(), n_gaps, L, self.world, self.batch,
-                                                           l, n_lib, send.data_ptr(), cap, cnt.data_ptr(), self.d_xerr.data_ptr()),
-                          "gf_pools_pack_for_owners_dev")
-
-            def merge(recv, cap, all_cnt):
-                self._chk(lib.gf_pools_merge_dev(h, recv.data_ptr(), cap, all_cnt.data_ptr(), n_lib, self.world, n_gaps, L, self.rank, self.world,
-                                                 self.batch, self.d_merged.data_ptr(), self.merged_cap, self.d_moff.data_ptr(), self.d_xerr.data_ptr()),
+            if not self.multi:
+                for l, lb in enumerate(self.libs):
+                    self._chk(lib.gf_pool_counts_dev(h, lb.d_pool_off.data_ptr(), n_gaps, self.d_libcnt.data_ptr() + 4 * l * n_gaps), "gf_pool_counts_dev")
+                self._chk(lib.gf_pools_merge_dev(h, self.d_pools.data_ptr(), self.lib_cap, self.d_libcnt.data_ptr(), n_lib, 1, n_gaps, L, 0, 1, self.batch,
+                                                 self.d_merged.data_ptr(), self.merged_cap, self.d_moff.data_ptr(), self.d_xerr.data_ptr()),
                           "gf_pools_merge_dev")
-            def pack_v(l, send, slot_base, slot_cap, cnt_base, cnt):
-                self._chk(lib.gf_pools_pack_for_owners_v_dev(h, self.pool_ptr[l], self.libs[l].d_pool_off.data_ptr(), n_gaps, L, self.world, self.batch,
-                                                             l, n_lib, send.data_ptr(), slot_base.data_ptr(), slot_cap.data_ptr(), cnt_base.data_ptr(),
-                                                             cnt.data_ptr(), self.d_xerr.data_ptr()), "gf_pools_pack_for_owners_v_dev")
-
-            def merge_v(recv, slot_base, cnt_base):
-                self._chk(lib.gf_pools_merge_v_dev(h, recv.data_ptr(), slot_base.data_ptr(), cnt_base.data_ptr(), n_lib, self.world, n_gaps, L, self.rank,
-                                                   self.world, self.batch, self.d_merged.data_ptr(), self.merged_cap, self.d_moff.data_ptr(),
-                                                   self.d_xerr.data_ptr()), "gf_pools_merge_v_dev")
-            ev0 = self._fixed_mark()
-            if self.exact_exchange:
-                self.xchg.run(pack_v, merge_v)
             else:
-                self.xchg.run(pack, merge)
-            self._fixed_span("owner_exchange", ev0)
+                # the one exchange step: rows regrouped by owner rank, counts all-gathered, slots all-to-all'ed
+                # (equal-sized slots: no host sizes, no host sync), owners merge in (library, source rank) order
+                ev0 = self._fixed_mark()
+                self.xchg.run(*self.xchg_kernels)
+                self._fixed_span("owner_exchange", ev0)
             self.asm_ptr, self.asm_off, self.asm_rows = self.d_merged.data_ptr(), self.d_moff.data_ptr(), self.merged_cap
         if self.kk and self.assemble_in_step:
             self.assemble()
@@ -790,32 +550,34 @@ class Pipeline:
                                             len(self.kk), self.min_count, self.min_contig, self.d_ctg.data_ptr(), self.contig_cap, self.ap,
                                             self.d_seq.data_ptr(), self.seq_cap, self.ap + 8, self.d_gap_err.data_ptr()), "gf_assemble_multi_dev")
         # which gaps are closed: both flanks anchored on one contig (pick_contigs.py:64-358; scores 30 then 15, assemble_gaps.py:336, 365)
-        a0, a1 = self.anchors[0], (self.anchors[1] if len(self.anchors) > 1 else 0)
-        if self.anchor_mode == "align":
-            self._chk(lib.gf_pick_aligned_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), a0, a1, self.d_best.data_ptr(),
-                                              self.ap + 16, self.d_ctg_pick.data_ptr(), self.d_pstats.data_ptr()), "gf_pick_aligned_dev")
-        else:
-            self._chk(lib.gf_pick_anchored2_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), a0, a1,
-                                                self.d_best.data_ptr(), self.ap + 16), "gf_pick_anchored2_dev")
+        self._pick(*self.anchor_pair)
         if self.merge_in_step:
             # the open gaps' contigs through the contig merger, merged contigs appended (k = kv = 0), second pick over THEM only
             self._chk(lib.gf_merge_open_gaps_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), self.ap + 8, self.seq_cap,
                                                  self.d_best.data_ptr(), self.n_gaps, B._p(self.merge_params), 10, self.merge_max_set,
                                                  self.k_arr, self.kv_arr, min(16, len(self.kk)), self.d_mstats.data_ptr()), "gf_merge_open_gaps_dev")
-            if self.anchor_mode == "align":
-                self._chk(lib.gf_pick_aligned_from_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), a0, a1,
-                                                       self.d_mstats.data_ptr() + 4 * B.MG_N0, self.d_best.data_ptr(), self.ap + 16,
-                                                       self.d_ctg_pick.data_ptr(), self.d_pstats.data_ptr()), "gf_pick_aligned_from_dev")
-            else:
-                self._chk(lib.gf_pick_anchored2_from_dev(h, self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), a0, a1,
-                                                         self.d_mstats.data_ptr() + 4 * B.MG_N0, self.d_best.data_ptr(), self.ap + 16),
-                          "gf_pick_anchored2_from_dev")
-        if self.second_round:
-            self._round2()
-        if self.rescue_round:
-            self._rescue()
-        if self.extended_fill:
-            self._extend()
+            self._pick(*self.anchor_pair, first=self.d_mstats.data_ptr() + 4 * B.MG_N0)
+        if self.round2 is not None:
+            self.round2.enqueue()
+        if self.rescue is not None:
+            self.rescue.enqueue()
+        if self.ext is not None:
+            self.ext.enqueue()
+
+    def _pick(self, a_long, a_short, first=None, own=None):
+        """One pick in the Pipeline's anchor mode over the contigs from index *first on (a device address; None: all of them) of the step's
+        list — read when the call is enqueued: a caller may have changed the capacities — or of `own` = (contigs, their counter, capacity,
+        bases, pick words, closed counter, selection per contig, statistics: the last two in align mode) device addresses."""
+        lib, align = self.lib, self.anchor_mode == "align"
+        if own is None:
+            own = (self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), self.d_best.data_ptr(), self.ap + 16) \
+                + ((self.d_ctg_pick.data_ptr(), self.d_pstats.data_ptr()) if align else ())
+        if first is None:
+            fn, what = (lib.gf_pick_aligned_dev, "gf_pick_aligned_dev") if align else (lib.gf_pick_anchored2_dev, "gf_pick_anchored2_dev")
+        else:
+            fn, what = ((lib.gf_pick_aligned_from_dev, "gf_pick_aligned_from_dev") if align
+                        else (lib.gf_pick_anchored2_from_dev, "gf_pick_anchored2_from_dev"))
+        self._chk(fn(self.h, *own[:4], a_long, a_short, *(() if first is None else (first,)), *own[4:]), what)
 
     def step(self, n=1):
         assert self.prepared, "Pipeline.prepare() first"
@@ -845,7 +607,7 @@ class Pipeline:
         torch.cuda.synchronize()
         r = Results()
         acnt = self.d_acnt.cpu().numpy()
-        r.n_contigs, r.n_seq, r.n_closed = int(acnt[0]), int(acnt[2:4].view(np.uint64)[0]), int(acnt[4])
+        r.n_contigs, r.n_seq, r.n_closed = int(acnt[0]), counter_u64(acnt), int(acnt[4])
         xerr = int(self.d_xerr[0])
         for lb in self.libs:
             c = lb.d_cnt.cpu().numpy()
@@ -861,7 +623,6 @@ class Pipeline:
         if xerr or n_err or r.n_contigs > self.contig_cap or r.n_seq > self.seq_cap:
             raise RuntimeError("step overflow: exchange/merge flag %#x, %d gap errors, %d contigs (cap %d), %d contig bases (cap %d)"
                                % (xerr & 0xFFFFFFFF, n_err, r.n_contigs, self.contig_cap, r.n_seq, self.seq_cap))
-        r.merge = None
         if self.merge_in_step and self.kk:
             ms = self.d_mstats.cpu().numpy().view(np.uint32)
             if int(ms[B.MG_ERR]):
@@ -879,64 +640,20 @@ class Pipeline:
         if self.anchor_mode == "align":
             r.ctg_pick = np.frombuffer(self.d_ctg_pick[:r.n_contigs * B.CTG_PICK.itemsize].cpu().numpy().tobytes(), dtype=B.CTG_PICK)
             r.align_dropped, r.align_seed_overflow = (int(x) for x in self.d_pstats.cpu().numpy())
-        r.rescue, r.rescue_first = None, None
-        if self.rescue_round and self.kk:
-            self._fetch_rescue(r)
+        if self.rescue is not None:
+            self.rescue.fetch(r)
         if r.merge is not None:      # gaps whose winning contig is a merged one (of the merge round: the rescue's records come after them)
-            idx = 0x7FFFFFFF - ((r.best >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64)
+            idx = pick_index(r.best)
             end = r.rescue_first if r.rescue_first is not None else np.iinfo(np.int64).max
             r.merge["gaps_closed_by_merging"] = int(((r.best != 0) & (idx >= r.merge["contigs_before"]) & (idx < end)).sum())
-        r.round2, r.round2_first, r.round2_reads = None, None, None
-        if self.second_round and self.kk:
-            self._fetch_round2(r)
-        r.extended, r.ext, r.ext_bases = None, None, None
-        if self.extended_fill and self.kk:
-            self._fetch_extended(r)
+        if self.round2 is not None:
+            self.round2.fetch(r)
+        if self.ext is not None and self.kk:
+            self.ext.fetch(r)
         if pools:
             r.pool_off = r.asm_off_t.cpu().numpy().astype(np.int64)
             r.pool_rows = r.asm_pool_t[:r.asm_rows_total * self.rb].cpu().numpy().reshape(-1, self.rb)
         return r
-
-    def _fetch_round2(self, r):
-        st = self.d_r2st.cpu().numpy().view(np.uint32)
-        a2 = self.d_acnt2.cpu().numpy()
-        n2, s2 = int(a2[0]), int(a2[2:4].view(np.uint64)[0])
-        n_err = int(self.d_gap_err2.sum())
-        if n_err or int(st[B.R2_APPEND_ERR]) or n2 > self.r2_ctg_cap or s2 > self.r2_seq_cap:
-            raise RuntimeError("second round overflow: %d gap errors, append flag %d, %d contigs (cap %d), %d contig bases (cap %d)"
-                               % (n_err, int(st[B.R2_APPEND_ERR]), n2, self.r2_ctg_cap, s2, self.r2_seq_cap))
-        first = int(st[B.R2_FIRST])
-        n_keys = min(int(st[B.R2_HITS]), self.r2_key_cap)
-        cand = [int(lb.d_r2n[0]) for lb in self.libs]
-        # recruits the round could not take: table entries without room, keys beyond their buffer, candidates beyond theirs, pools beyond theirs
-        dropped = (int(st[B.R2_TAB_FULL]) + max(0, int(st[B.R2_HITS]) - self.r2_key_cap) + sum(max(0, c - lb.r2_cap) for c, lb in zip(cand, self.libs))
-                   + (2 * int(st[B.R2_UNIQUE]) if int(st[B.R2_POOL_OVF]) else 0))
-        idx = 0x7FFFFFFF - ((r.best >> np.uint64(1)) & np.uint64(0x7FFFFFFF)).astype(np.int64)
-        r.round2_first = first
-        r.round2 = {"gaps_tried": int(st[B.R2_TRIED]), "gaps_with_recruits": int(st[B.R2_WITH]), "reads_recruited": 2 * int(st[B.R2_UNIQUE]),
-                    "contigs": int(st[B.R2_N2]), "gaps_closed": int(((r.best != 0) & (idx >= first)).sum()), "dropped": int(dropped),
-                    "candidates": 2 * sum(cand)}
-        if self.keep_read_ids:      # per gap with recruits: [(library, read id)] in round-2 pool order
-            keys = np.unique(self.d_r2sorted[:n_keys].cpu().numpy().view(np.uint64))
-            keys = keys[keys != np.uint64(0xFFFFFFFFFFFFFFFF)]
-            gap, libi, pair = (keys >> np.uint64(40)).astype(np.int64), ((keys >> np.uint64(36)) & np.uint64(15)).astype(np.int64), \
-                (keys & np.uint64((1 << 36) - 1)).astype(np.int64)
-            out = {}
-            for g, l, p in zip(gap.tolist(), libi.tolist(), pair.tolist()):
-                out.setdefault(g, []).extend([(l, 2 * p), (l, 2 * p + 1)])
-            r.round2_reads = out
-
-    def _fetch_extended(self, r):
-        st = self.d_ext_stats.cpu().numpy().view(np.uint32)
-        total = int(st[B.EXT_BASES]) | (int(st[B.EXT_BASES + 1]) << 32)
-        if int(st[B.EXT_OVERFLOW]) or total > self.ext_base_cap:
-            raise RuntimeError("extended fill overflow: %d fill bases, buffer of %d (Pipeline(ext_base_cap=...))" % (total, self.ext_base_cap))
-        r.extended = {"gaps_extended": int(st[B.EXT_EXTENDED]), "left_only": int(st[B.EXT_LEFT_ONLY]), "right_only": int(st[B.EXT_RIGHT_ONLY]),
-                      "both_sides": int(st[B.EXT_BOTH]), "bases": total}
-        if self.anchor_mode == "align":
-            r.extended["align_dropped"], r.extended["align_seed_overflow"] = int(st[B.EXT_ALIGN_DROPPED]), int(st[B.EXT_ALIGN_SEED_OVERFLOW])
-        r.ext = np.frombuffer(self.d_ext[:self.n_gaps * B.EXT_PICK.itemsize].cpu().numpy().tobytes(), dtype=B.EXT_PICK)
-        r.ext_bases = self.d_ext_bases[:total].cpu().numpy().tobytes()
 
     def extended_sequences(self, res):
         """The partial fills of the last step (extended_fill): {gap: (left contig index or -1, right contig index or -1, fill or None,
@@ -945,15 +662,10 @@ class Pipeline:
         from .pick_contigs import decode_extended
         if res.ext is None:
             raise ValueError("extended_sequences needs the Results of a Pipeline(extended_fill=True) step")
-        ctg, seq = res.contigs, res.seq
-
-        def contig_seq(i):
-            c = ctg[i]
-            return seq[int(c["seq_off"]):int(c["seq_off"]) + int(c["length"])].decode()
         out = {}
         for g in np.nonzero((res.ext["left"] != B.EXT_NONE) | (res.ext["right"] != B.EXT_NONE))[0]:
             rec = res.ext[g]
-            d = decode_extended(rec, contig_seq)
+            d = decode_extended(rec, lambda i: contig_text(res, i))
             dev = res.ext_bases[int(rec["off"]):int(rec["off"]) + int(rec["len"])].decode() if int(rec["len"]) else None
             if dev != d[2]:
                 raise RuntimeError("gap %d: the device's fill does not match its record" % g)
@@ -970,7 +682,7 @@ class Pipeline:
         ("gaps_skipped_large"): the contig graph of a repeat-bearing gap has thousands of paths (C2 with planted repeats and mate pairs:
         53 641 merged strings for 176 gaps, 158 s on the host, and 50 of the 174 gaps they close are closed with a wrong sequence)."""
         from .MergeContigs import MAX_SET, drop_contained, merge_sets
-        ctg, seq = res.contigs, res.seq
+        ctg = res.contigs
         open_gaps = np.nonzero(res.best == 0)[0]
         order = np.argsort(ctg["gap"], kind="stable")
         gs = ctg["gap"][order]
@@ -978,7 +690,7 @@ class Pipeline:
         sets, gaps_of, skipped = [], [], 0
         for g, a, z in zip(open_gaps, lo, hi):
             if z - a >= 2:
-                recs = [("c%d" % i, seq[int(ctg[i]["seq_off"]):int(ctg[i]["seq_off"]) + int(ctg[i]["length"])].decode()) for i in order[a:z]]
+                recs = [("c%d" % i, contig_text(res, i)) for i in order[a:z]]
                 recs = drop_contained(recs) if len(recs) <= MAX_SET else recs
                 if 2 <= len(recs) <= min(MAX_SET, max_set):
                     sets.append(recs)
@@ -1005,16 +717,13 @@ class Pipeline:
         d_b2 = torch.zeros(max(1, self.n_gaps), dtype=torch.int64, device=self.dev)
         d_n2 = torch.tensor([len(new), 0, 0, 0], dtype=torch.int32, device=self.dev)
         torch.cuda.synchronize()
-        a0, a1 = self.anchors[0], (self.anchors[1] if len(self.anchors) > 1 else 0)
+        own = (d_c2.data_ptr(), d_n2.data_ptr(), len(new), d_s2.data_ptr(), d_b2.data_ptr(), d_n2.data_ptr() + 8)
         if self.anchor_mode == "align":
             d_p2 = torch.zeros(len(new) * B.CTG_PICK.itemsize, dtype=torch.uint8, device=self.dev)
             d_st2 = torch.zeros(2, dtype=torch.int32, device=self.dev)
             torch.cuda.synchronize()
-            self._chk(self.lib.gf_pick_aligned_dev(self.h, d_c2.data_ptr(), d_n2.data_ptr(), len(new), d_s2.data_ptr(), a0, a1, d_b2.data_ptr(),
-                                                   d_n2.data_ptr() + 8, d_p2.data_ptr(), d_st2.data_ptr()), "gf_pick_aligned_dev")
-        else:
-            self._chk(self.lib.gf_pick_anchored2_dev(self.h, d_c2.data_ptr(), d_n2.data_ptr(), len(new), d_s2.data_ptr(), a0, a1, d_b2.data_ptr(),
-                                                     d_n2.data_ptr() + 8), "gf_pick_anchored2_dev")
+            own += (d_p2.data_ptr(), d_st2.data_ptr())
+        self._pick(*self.anchor_pair, own=own)
         self.gf.sync()
         b2 = d_b2[:self.n_gaps].cpu().numpy().view(np.uint64)
         out["closed"] = {int(g): decode_best(b2[g]) for g in np.nonzero(b2)[0]}
@@ -1033,8 +742,7 @@ class Pipeline:
         out = {}
         for g in np.nonzero(res.best)[0]:
             a_len, span1, ci, rev = decode_best(res.best[g])
-            c = res.contigs[ci]
-            seq = res.seq[int(c["seq_off"]):int(c["seq_off"]) + int(c["length"])].decode()
+            seq = contig_text(res, ci)
             if res.anchor_mode == "align":
                 p = res.ctg_pick[ci]
                 lp, rp, lm, rm = int(p["lp"]), int(p["rp"]), int(p["lm"]), int(p["rm"])
@@ -1058,7 +766,23 @@ class Pipeline:
         return out
 
 
+def pick_index(best):
+    """Index of the winning contig of a gap_best word (an int) or of an array of them (u64)."""
+    return 0x7FFFFFFF - ((best >> 1) & 0x7FFFFFFF)
+
+
 def decode_best(b):
     """gap_best word (gf_pick_anchored_dev) -> (anchor length, span + 1, contig index, reverse strand?)."""
     b = int(b)
-    return b >> 56, (b >> 32) & 0xFFFFFF, 0x7FFFFFFF - ((b >> 1) & 0x7FFFFFFF), b & 1
+    return b >> 56, (b >> 32) & 0xFFFFFF, pick_index(b), b & 1
+
+
+def counter_u64(a, word=2):
+    """The u64 in words `word`, `word + 1` of a fetched array of 32-bit counters (the assembly's counters keep the contig bases in 2-3)."""
+    return int(a[word:word + 2].view(np.uint64)[0])
+
+
+def contig_text(res, i):
+    """Bases of contig i of a Results."""
+    c = res.contigs[i]
+    return res.seq[int(c["seq_off"]):int(c["seq_off"]) + int(c["length"])].decode()

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import pick_util as PK
+from step_util import L, N_PAIRS, picks as _picks, setup as _setup
 
 pytestmark = pytest.mark.gpu
 
@@ -508,7 +509,6 @@ def test_contig_kmer_table_and_recruitment_against_a_plain_reference(gf, k):
 
 # ---- C. the pipeline: an overflowing step raises, and the next one is clean ---------------------------------------------------------
 
-SEED, SLEN, NSCF, GPS, L, N_PAIRS = 20260021, 200_000, 4, 6, 150, 80_000
 LAYOUTS = {"mixed550_k31": (550, [(31, 29)]), "mixed450_k51_61": (450, [(51, 49), (61, 59)])}
 FEATURES = {"default": {}, "merge_in_step": {"merge_in_step": True}, "second_round": {"second_round": True},
             "extended_fill": {"extended_fill": True}}
@@ -516,14 +516,10 @@ FEATURES = {"default": {}, "merge_in_step": {"merge_in_step": True}, "second_rou
 
 @pytest.fixture(scope="module", params=sorted(LAYOUTS))
 def layout(request):
-    from test_gpu_second_round import _setup
-    import test_gpu_second_round as T
-    assert (T.SEED, T.SLEN, T.NSCF, T.GPS, T.L, T.N_PAIRS) == (SEED, SLEN, NSCF, GPS, L, N_PAIRS)
     return _setup(*LAYOUTS[request.param])
 
 
 def _summary(pipe, res):
-    from test_gpu_second_round import _picks
     per_gap = collections.Counter((int(c["gap"]), int(c["k"]), int(c["kv"]), _text(res.contigs, res.seq, i)) for i, c in enumerate(res.contigs))
     out = {"n": (res.n_contigs, res.n_seq, res.n_closed), "contigs": per_gap, "picks": _picks(res), "merge": res.merge, "round2": res.round2}
     if res.ext is not None:

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import pick_util as PK
+from step_util import contigs as _contigs, picks as _picks, run as _run, setup as _setup
 
 pytestmark = pytest.mark.gpu
 
@@ -164,7 +165,6 @@ def test_device_extension_equals_the_host_twin(mode):
 
 # ---- Pipeline(extended_fill=True) on synthetic steps ----------------------------------------------------------------------------------
 
-SEED, SLEN, NSCF, GPS, L, N_PAIRS = 20260021, 200_000, 4, 6, 150, 80_000
 # name -> (gap length, k pairs): round 1 reaches about one insert (300 bp) past each flank; 900 bp / k 31 closes none of the 24 gaps,
 # 550 bp / k 31 closes 3 (a second round closes all 24 of both); 2 000 bp stays open after two rounds
 CONFIGS = {"open900_k31": (900, [(31, 29)]), "mixed550_k31": (550, [(31, 29)]), "open2000_k31": (2000, [(31, 29)])}
@@ -173,43 +173,7 @@ SETTINGS = {"plain": {}, "merge": {"merge_in_step": True}, "round2": {"second_ro
 
 @pytest.fixture(scope="module", params=sorted(CONFIGS))
 def layout(request):
-    import torch
-    from gappadder_amd.hip_api import GapFill
-    gap_len, kk = CONFIGS[request.param]
-    gf = GapFill(0)
-    cfg = GapFill.synth_cfg(seed=SEED, scaffold_len=SLEN, n_scaffolds=NSCF, gaps_per_scaffold=GPS, gap_len=gap_len, read_len=L)
-    gaps, flanks = GapFill.synth_layout(cfg)
-    gf.set_gaps(gaps, NSCF, flanks)
-    rb = (L + 3) // 4
-    d_reads = torch.empty(2 * N_PAIRS * rb + 64, dtype=torch.uint8, device="cuda")
-    d_recs = torch.empty(2 * N_PAIRS * 32, dtype=torch.uint8, device="cuda")
-    gf.synth_pairs_dev(cfg, 0, N_PAIRS, d_reads.data_ptr(), d_recs.data_ptr())
-    gf.sync()
-    return request.param, gf, cfg, gaps, flanks, d_reads, d_recs, kk
-
-
-def _run(layout, steps=1, **kw):
-    from gappadder_amd.pipeline import DeviceLibrary, Pipeline
-    _, gf, cfg, gaps, flanks, d_reads, d_recs, kk = layout
-    pipe = Pipeline(gf, len(gaps), L, kk, **kw)
-    pipe.add_library(DeviceLibrary("x", 300, 30, 2 * N_PAIRS, d_reads, d_recs))
-    pipe.prepare()
-    out = []
-    for _ in range(steps):
-        pipe.step()
-        out.append(pipe.fetch())
-    return pipe, out
-
-
-def _contigs(res):
-    return [(int(c["gap"]), int(c["k"]), int(c["kv"]), res.seq[int(c["seq_off"]):int(c["seq_off"]) + int(c["length"])].decode()) for c in res.contigs]
-
-
-def _picks(res):
-    """Pick words with the contig named by its bases (the device's contig order is unspecified)."""
-    from gappadder_amd.pipeline import decode_best
-    texts = _contigs(res)
-    return {g: decode_best(w)[:2] + (decode_best(w)[3], texts[decode_best(w)[2]][3]) for g, w in enumerate(res.best.tolist()) if w}
+    return (request.param,) + _setup(*CONFIGS[request.param])
 
 
 def _true_parts(layout, fills):
@@ -236,8 +200,8 @@ def runs(layout):
     on, off = {}, {}
     for name, kw in SETTINGS.items():
         for mode in ("exact", "align"):
-            on[name, mode] = _run(layout, steps=2, extended_fill=True, anchor_mode=mode, **kw)
-            off[name, mode] = _run(layout, anchor_mode=mode, **kw)
+            on[name, mode] = _run(layout[1:], steps=2, extended_fill=True, anchor_mode=mode, **kw)
+            off[name, mode] = _run(layout[1:], anchor_mode=mode, **kw)
     return on, off
 
 
@@ -293,7 +257,7 @@ def test_extension_changes_nothing_else(runs, setting, mode):
 
 
 def test_too_small_fill_buffer_is_reported(layout):
-    pipe, _ = _run(layout, steps=0, extended_fill=True, ext_base_cap=64)
+    pipe, _ = _run(layout[1:], steps=0, extended_fill=True, ext_base_cap=64)
     pipe.step()
     with pytest.raises(RuntimeError, match="extended fill overflow"):
         pipe.fetch()

@@ -237,7 +237,7 @@ def test_a_contig_list_the_rescue_overflows_raises_and_the_next_step_is_clean(ho
     pipe.step()
     with pytest.raises(RuntimeError):
         pipe.fetch()
-    st = pipe.d_rst.cpu().numpy()
+    st = pipe.rescue.d_st.cpu().numpy()
     if where == "bridges":
         from gappadder_amd import _lib as B
         assert int(st[B.RS_APPEND_ERR]) == 2 and int(st[B.RS_BRIDGES]) == 1 and int(pipe.d_acnt[0]) >= first + 1

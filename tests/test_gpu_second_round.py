@@ -6,43 +6,15 @@ import numpy as np
 import pytest
 
 import sample_check as SC
+from step_util import L, N_PAIRS, picks as _picks, run as _run, setup as _setup, text as _text
 
 pytestmark = pytest.mark.gpu
 
-SEED, SLEN, NSCF, GPS, L, N_PAIRS = 20260021, 200_000, 4, 6, 150, 80_000
 # name -> (gap length, k pairs, does the first round close some of the 24 gaps?).  Round 1 reaches about one insert (300 bp) past each
 # flank; measured on the GPU: 900 bp / k 31 closes 0 of 24 in round 1 (24 with round 2), 550 bp / k 31 closes 3 (24 with round 2),
 # 450 bp / k 51 + 61 closes 15 (24 with round 2)
 CONFIGS = {"open900_k31": (900, [(31, 29)], False), "mixed550_k31": (550, [(31, 29)], True),
            "mixed450_k51_61": (450, [(51, 49), (61, 59)], True)}
-
-
-def _setup(gap_len, kk):
-    import torch
-    from gappadder_amd.hip_api import GapFill
-    gf = GapFill(0)
-    cfg = GapFill.synth_cfg(seed=SEED, scaffold_len=SLEN, n_scaffolds=NSCF, gaps_per_scaffold=GPS, gap_len=gap_len, read_len=L)
-    gaps, flanks = GapFill.synth_layout(cfg)
-    gf.set_gaps(gaps, NSCF, flanks)
-    rb = (L + 3) // 4
-    d_reads = torch.empty(2 * N_PAIRS * rb + 64, dtype=torch.uint8, device="cuda")
-    d_recs = torch.empty(2 * N_PAIRS * 32, dtype=torch.uint8, device="cuda")
-    gf.synth_pairs_dev(cfg, 0, N_PAIRS, d_reads.data_ptr(), d_recs.data_ptr())
-    gf.sync()
-    return gf, cfg, gaps, flanks, d_reads, d_recs, kk
-
-
-def _run(env, steps=1, pools=False, **kw):
-    from gappadder_amd.pipeline import DeviceLibrary, Pipeline
-    gf, cfg, gaps, flanks, d_reads, d_recs, kk = env
-    pipe = Pipeline(gf, len(gaps), L, kk, **kw)
-    pipe.add_library(DeviceLibrary("x", 300, 30, 2 * N_PAIRS, d_reads, d_recs))
-    pipe.prepare()
-    out = []
-    for _ in range(steps):
-        pipe.step()
-        out.append(pipe.fetch(pools=pools))
-    return pipe, out
 
 
 @pytest.fixture(scope="module", params=sorted(CONFIGS))
@@ -64,17 +36,6 @@ def on(env):
 @pytest.fixture(scope="module")
 def off(env):
     return _run(env)
-
-
-def _text(res, i):
-    c = res.contigs[i]
-    return res.seq[int(c["seq_off"]):int(c["seq_off"]) + int(c["length"])].decode()
-
-
-def _picks(res):
-    """Pick words with the contig named by its bases (the device's contig order is unspecified)."""
-    from gappadder_amd.pipeline import decode_best
-    return {g: decode_best(w)[:2] + (decode_best(w)[3], _text(res, decode_best(w)[2])) for g, w in enumerate(res.best.tolist()) if w}
 
 
 def _contig_set(res, lo=0, hi=None):

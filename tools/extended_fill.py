@@ -8,20 +8,14 @@ bases after the left anchor (from one base earlier when it keeps an anchor base)
 """
 import argparse
 import json
-import os
-import sys
-import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from preset_setup import preset_setup, release, timed_steps
 
 
 def main():
     import bench
     import torch
-    from gappadder_amd import _lib as B
     from gappadder_amd.hip_api import GapFill
-    from gappadder_amd.pipeline import DeviceLibrary, Pipeline
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="C4", choices=sorted(bench.PRESETS))
     ap.add_argument("--steps", type=int, default=3)
@@ -30,40 +24,20 @@ def main():
     ap.add_argument("--anchor-modes", default="exact,align")
     ap.add_argument("--modes", default="off,on")
     args = ap.parse_args()
-    seed, slen, nscf, gps, glen, dreads, kk = bench.PRESETS[args.config]
-    glen = args.gap_len or glen
-    n_reads = (args.reads or dreads) // 2 * 2
-    L = 150
-    rep_p, rep_c = bench.REPEATS.get(args.config, (0, 50))
-    cfg = GapFill.synth_cfg(seed=seed, scaffold_len=slen, n_scaffolds=nscf, gaps_per_scaffold=gps, gap_len=glen, read_len=L,
-                            insert_mean=300, insert_sd=30, repeat_period=rep_p, repeat_copies=rep_c)
-    gaps, flanks = GapFill.synth_layout(cfg)
-    gf = GapFill(0)
-    gf.set_gaps(gaps, nscf, flanks)
-    rb = B.lib().gf_packed_read_bytes(L)
-    d_reads = torch.empty(n_reads * rb + 64, dtype=torch.uint8, device="cuda")
-    d_recs = torch.empty(max(1, n_reads) * 32, dtype=torch.uint8, device="cuda")
-    gf.synth_pairs_dev(cfg, 0, n_reads // 2, d_reads.data_ptr(), d_recs.data_ptr())
-    gf.sync()
+    s = preset_setup(args.config, reads=args.reads, gap_len=args.gap_len)
+    gaps, cfg = s.gaps, s.cfg
     for amode in args.anchor_modes.split(","):
         for mode in args.modes.split(","):
-            pipe = Pipeline(gf, len(gaps), L, kk, anchor_mode=amode, extended_fill=(mode == "on"))
-            pipe.add_library(DeviceLibrary("short-insert", 300, 30, n_reads, d_reads, d_recs))
-            pipe.prepare()
-            pipe.step(1)
-            pipe.barrier()
-            t0 = time.perf_counter()
-            pipe.step(args.steps)
-            pipe.barrier()
-            ms = (time.perf_counter() - t0) * 1e3 / args.steps
+            pipe = s.pipeline(anchor_mode=amode, extended_fill=(mode == "on"))
+            ms = timed_steps(pipe, args.steps)
             res = pipe.fetch()
-            line = {"config": args.config, "gap_len": glen, "reads": n_reads, "anchor_mode": amode, "extended_fill": mode, "gaps": len(gaps),
+            line = {"config": args.config, "gap_len": s.gap_len, "reads": s.reads, "anchor_mode": amode, "extended_fill": mode, "gaps": len(gaps),
                     "ms_per_step": round(ms, 3), "closed": int((res.best != 0).sum())}
             if res.extended is not None:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
                 for _ in range(args.steps):
-                    pipe._extend()
+                    pipe.ext.enqueue()
                 e1.record()
                 pipe.barrier()
                 line["extension_ms"] = round(e0.elapsed_time(e1) / args.steps, 4)
@@ -86,8 +60,7 @@ def main():
                 line["parts"], line["parts_equal_to_truth"] = n_parts, n_true
             print(json.dumps(line), flush=True)
             del pipe, res
-            torch.cuda.synchronize()
-            torch.cuda.empty_cache()
+            release()
 
 
 if __name__ == "__main__":

@@ -1,0 +1,72 @@
+"""What the per-feature scripts (second_round.py, rescue_round.py, extended_fill.py, anchor_modes.py) share: one bench preset as a GapFill
+with its gaps set and the preset's libraries synthesised on the device."""
+import os
+import sys
+import time
+import types
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+L = 150
+
+
+def preset_setup(config, reads=0, gap_len=0, mp_reads=0, edit_flanks=None):
+    """reads / gap_len: read records of the short-insert library / gap length (0: the preset's); mp_reads: read records of the preset's
+    mate-pair library (IS 5000 / sd 500; 0: none); edit_flanks(flanks) -> flanks: the draft's flanks as the picker is to see them.
+    Returns a namespace: gf, cfg (the short-insert library's), gaps, kk, gap_len, reads, libs [(name, IS mean, IS sd, read records,
+    d_reads, d_recs, pull_mates)], truth(g) = the two strings a closed gap's sequence may equal (gf_synth_truth), pipeline(**flags)."""
+    import bench
+    import torch
+    from gappadder_amd import _lib as B
+    from gappadder_amd.hip_api import GapFill
+    from gappadder_amd.pipeline import DeviceLibrary, Pipeline
+    seed, slen, nscf, gps, glen, dreads, kk = bench.PRESETS[config]
+    glen = gap_len or glen
+    rep_p, rep_c = bench.REPEATS.get(config, (0, 50))
+
+    def synth_cfg(is_mean, is_sd, lib_no):
+        return GapFill.synth_cfg(seed=seed, scaffold_len=slen, n_scaffolds=nscf, gaps_per_scaffold=gps, gap_len=glen, read_len=L,
+                                 insert_mean=is_mean, insert_sd=is_sd, library=lib_no, repeat_period=rep_p, repeat_copies=rep_c)
+    cfg = synth_cfg(300, 30, 0)
+    gaps, flanks = GapFill.synth_layout(cfg)
+    gf = GapFill(0)
+    gf.set_gaps(gaps, nscf, edit_flanks(flanks) if edit_flanks else flanks)
+    rb = B.lib().gf_packed_read_bytes(L)
+    lib_defs = [("short-insert", 300, 30, 0, (reads or dreads) // 2 * 2, 1)] + ([("mate-pair", 5000, 500, 1, mp_reads // 2 * 2, 0)] if mp_reads else [])
+    libs = []
+    for name, is_mean, is_sd, lib_no, n, pull in lib_defs:
+        d_reads = torch.empty(n * rb + 64, dtype=torch.uint8, device="cuda")
+        d_recs = torch.empty(max(1, n) * 32, dtype=torch.uint8, device="cuda")
+        gf.synth_pairs_dev(synth_cfg(is_mean, is_sd, lib_no), 0, n // 2, d_reads.data_ptr(), d_recs.data_ptr())
+        libs.append((name, is_mean, is_sd, n, d_reads, d_recs, pull))
+    gf.sync()
+
+    def truth(g):
+        st, en, sc = int(gaps[g]["start"]), int(gaps[g]["end"]), int(gaps[g]["scaffold"])
+        return GapFill.synth_truth(cfg, sc, st - 5, en - st + 11), GapFill.synth_truth(cfg, sc, st - 6, en - st + 11)
+
+    def pipeline(**flags):
+        pipe = Pipeline(gf, len(gaps), L, kk, **flags)
+        for name, is_mean, is_sd, n, d_reads, d_recs, pull in libs:
+            pipe.add_library(DeviceLibrary(name, is_mean, is_sd, n, d_reads, d_recs, pull_mates=pull))
+        return pipe
+    return types.SimpleNamespace(gf=gf, cfg=cfg, gaps=gaps, kk=kk, gap_len=glen, reads=libs[0][3], libs=libs, truth=truth, pipeline=pipeline)
+
+
+def timed_steps(pipe, steps):
+    """prepare(), a warm-up step, then `steps` steps between barriers: wall milliseconds per step."""
+    pipe.prepare()
+    pipe.step(1)
+    pipe.barrier()
+    t0 = time.perf_counter()
+    pipe.step(steps)
+    pipe.barrier()
+    return (time.perf_counter() - t0) * 1e3 / steps
+
+
+def release():
+    """Between two settings of a script, after the caller dropped its Pipeline: the device memory goes back before the next one sizes."""
+    import torch
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
