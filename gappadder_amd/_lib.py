@@ -58,6 +58,21 @@ EXT_WORDS, EXT_MAX_PAIRS = 12, 32
 _lib = None
 
 
+class ProbeColumnGeom(C.Structure):
+    """gf_probe_geom: the probe geometry a library's probe column was built for (include/gapfill_hip.h)."""
+    _fields_ = [("n_reads", C.c_uint64), ("read_len", C.c_uint32), ("k", C.c_uint32), ("first", C.c_uint32), ("stride", C.c_uint32),
+                ("np", C.c_uint32), ("ext", C.c_uint32), ("use", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def key(self):
+        """What a column depends on (not `use`, which is advice, nor the reserved word)."""
+        return (self.n_reads, self.read_len, self.k, self.first, self.stride, self.np, self.ext)
+
+
+class ScreenView(C.Structure):
+    """gf_screen_view (test aid, gf_screen_debug_view)."""
+    _fields_ = [(n, C.c_void_p) for n in ("count", "fills", "pairs", "n_cand", "cand")] + [(n, C.c_uint32) for n in ("n_writers", "cap", "gs", "n_groups")]
+
+
 class GapFillError(RuntimeError):
     def __init__(self, code, what, detail=""):
         self.code = code
@@ -112,6 +127,11 @@ def lib():
         "gf_fastq_records_text": (i32, [vp, vp, vp, vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp, sz, vp, szp, szp]),
         "gf_screen_reads": (i32, [vp, vp, vp, sz, i32, i32, i32, vp, sz, szp]),
         "gf_screen_reads_dev": (i32, [vp, vp, vp, sz, i32, i32, i32, vp, sz, vp]),
+        "gf_screen_debug_view": (i32, [vp, C.POINTER(ScreenView)]),
+        "gf_probe_geometry": (i32, [vp, sz, i32, i32, C.POINTER(ProbeColumnGeom)]),
+        "gf_probe_column_bytes": (sz, [C.POINTER(ProbeColumnGeom)]),
+        "gf_read_probes_dev": (i32, [vp, vp, sz, i32, i32, vp, C.POINTER(ProbeColumnGeom)]),
+        "gf_screen_reads_probes_dev": (i32, [vp, vp, vp, vp, C.POINTER(ProbeColumnGeom), sz, i32, i32, i32, vp, sz, vp]),
         "gf_tag_alignments": (i32, [vp, vp, sz, i32, i32, i32, i32, vp, sz, szp]),
         "gf_tag_alignments_dev": (i32, [vp, vp, sz, i32, i32, i32, i32, vp, sz, vp]),
         "gf_tag_low_mapq": (i32, [vp, vp, sz, vp, sz, vp, sz, szp]),

@@ -146,7 +146,7 @@ void gf_destroy(gf_ctx* ctx) {
     (void)hipStreamSynchronize(ctx->stream);
     drain_timing(ctx);
     for (auto& kv : ctx->index) free_flank_index(ctx, kv.second);
-    for (DevBuf* b : {&ctx->cand, &ctx->cand2, &ctx->part_ws, &ctx->tag_stage, &ctx->verify_stage, &ctx->bam_stream, &ctx->bam_recs, &ctx->asm_table, &ctx->asm_surv, &ctx->asm_nodes, &ctx->asm_jump, &ctx->asm_big, &ctx->rowgap, &ctx->pool_ws, &ctx->xchg_ws, &ctx->xchg_ws2, &ctx->counters, &ctx->stage_in, &ctx->stage_out, &ctx->stage_aux, &ctx->table, &ctx->r2_tmp, &ctx->ext_ws, &ctx->rs_tmp})
+    for (DevBuf* b : {&ctx->cand, &ctx->cand2, &ctx->cand_keep, &ctx->part_ws, &ctx->tag_stage, &ctx->verify_stage, &ctx->bam_stream, &ctx->bam_recs, &ctx->asm_table, &ctx->asm_surv, &ctx->asm_nodes, &ctx->asm_jump, &ctx->asm_big, &ctx->rowgap, &ctx->pool_ws, &ctx->xchg_ws, &ctx->xchg_ws2, &ctx->counters, &ctx->stage_in, &ctx->stage_out, &ctx->stage_aux, &ctx->table, &ctx->r2_tmp, &ctx->ext_ws, &ctx->rs_tmp})
         if (b->p) (void)hipFree(b->p);
     for (auto& kv : ctx->anchor_tabs) if (kv.second.p) (void)hipFree(kv.second.p);
     drop_tag_maps(ctx);
@@ -231,6 +231,7 @@ int gf_set_option(gf_ctx* ctx, const char* name, long value) {
     if (!strcmp(name, "tag_bins_log2")) { ctx->tag_bins_log2 = std::max(13, std::min(19, (int)value)); drop_tag_maps(ctx); return GF_OK; }
     if (!strcmp(name, "tag_fine_log2")) { ctx->tag_fine_log2 = std::max(20, std::min(28, (int)value)); drop_tag_maps(ctx); return GF_OK; }
     if (!strcmp(name, "tag_nt")) { ctx->tag_nt = value != 0; return GF_OK; }
+    if (!strcmp(name, "screen_keep_cand")) { if (value && !getenv("GF_DIAGNOSTICS")) return GF_E_UNSUPPORTED; ctx->screen_keep_cand = value != 0; return GF_OK; }
     if (!strcmp(name, "screen_pf4_cap8")) { ctx->screen_pf4_cap8 = (int)value; return GF_OK; }
     if (!strcmp(name, "screen_ext")) { ctx->screen_ext = value != 0; return GF_OK; }
     if (!strcmp(name, "screen_verify_batch")) { ctx->screen_verify_batch = (int)value; return GF_OK; }
@@ -311,6 +312,54 @@ int gf_screen_reads_dev(gf_ctx* ctx, const void* d_reads, const void* d_nmask, s
     int rc = build_flank_index(ctx, k, &ix);
     if (rc) return rc;
     return launch_screen(ctx, *ix, d_reads, d_nmask, n_reads, read_len, min_hits, d_out, cap, d_n_out);
+}
+
+// the flank index of k where the context has gaps and flanks (what decides which filter a screen takes); null otherwise
+static int probe_index(gf_ctx* ctx, int k, FlankIndex** ix) {
+    *ix = nullptr;
+    if (!ctx || ctx->gaps.empty() || ctx->flank_left.empty()) return GF_OK;
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    return build_flank_index(ctx, k, ix);
+}
+
+int gf_probe_geometry(gf_ctx* ctx, size_t n_reads, int read_len, int k, gf_probe_geom* out) {
+    if (!out || read_len < k || read_len > 1000 || k < 16 || k > 64) return GF_E_INVAL;
+    FlankIndex* ix = nullptr;
+    const int rc = probe_index(ctx, k, &ix);
+    if (rc) return rc;
+    fill_probe_geom(ctx, ix, n_reads, read_len, k, out);
+    return GF_OK;
+}
+
+size_t gf_probe_column_bytes(const gf_probe_geom* g) {
+    return g && g->np ? (((size_t)g->n_reads + 63) & ~(size_t)63) * g->np * 4 : 0;
+}
+
+int gf_read_probes_dev(gf_ctx* ctx, const void* d_reads, size_t n_reads, int read_len, int k, void* d_probes, gf_probe_geom* built_for) {
+    if (!ctx || !d_probes || !built_for || (n_reads && !d_reads) || read_len < k || read_len > 1000 || k < 16 || k > 64) return GF_E_INVAL;
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    FlankIndex* ix = nullptr;
+    const int rc = probe_index(ctx, k, &ix);
+    if (rc) return rc;
+    return launch_read_probes(ctx, ix, d_reads, n_reads, read_len, k, d_probes, built_for);
+}
+
+int gf_screen_reads_probes_dev(gf_ctx* ctx, const void* d_reads, const void* d_nmask, const void* d_probes, const gf_probe_geom* built_for,
+                               size_t n_reads, int read_len, int k, int min_hits, void* d_out, size_t cap, void* d_n_out) {
+    if (!ctx || !d_n_out || (n_reads && !d_reads) || (cap && !d_out) || (d_probes && !built_for)) return GF_E_INVAL;
+    if (ctx->gaps.empty() && ctx->n_scaffolds == 0) return GF_E_STATE;
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    FlankIndex* ix = nullptr;
+    int rc = build_flank_index(ctx, k, &ix);
+    if (rc) return rc;
+    return launch_screen(ctx, *ix, d_reads, d_nmask, n_reads, read_len, min_hits, d_out, cap, d_n_out, d_probes, built_for);
+}
+
+int gf_screen_debug_view(gf_ctx* ctx, gf_screen_view* out) {
+    if (!ctx || !out) return GF_E_INVAL;
+    if (!getenv("GF_DIAGNOSTICS")) return GF_E_UNSUPPORTED;
+    *out = ctx->screen_view;
+    return out->pairs ? GF_OK : GF_E_STATE;
 }
 
 int gf_screen_last_overflow(gf_ctx* ctx, size_t* n_reads_dropped) {

@@ -116,12 +116,14 @@ struct gf_ctx {
     uint32_t max_gaps_per_kmer = 0;     // 0 = unlimited
     int bitmap_log2_override = 0;
     int index_host = 0;         // 1: build the flank index on the host (comparator of the device builder)
-    int screen_variant = 0;     // filter kernel: 0 automatic; 9 plain, 13 pipelined, 16 / 17 256-bucket partitioned with whole-line / unaligned stores (tests run each)
+    int screen_variant = 0;     // filter kernel: 0 automatic; 9 plain, 13 pipelined, 16 / 17 256-bucket partitioned with whole-line / unaligned stores, 18 = 16 from the packed rows even where a probe column is given (tests run each)
     int screen_verify_batch = 64;  // verify kernel: candidates per wave and pass
     int screen_verify_ext = 1;   // min_hits == 1 without repeat mask: seed-and-extend verification instead of the k-mer table
     int screen_verify_gate = 1;  // verify kernel: consult the k-mer table only around exact 16-mer hits
     int screen_stream_policy = 1;  // pipelined filter: read stream loaded non-temporal (nt): keeps the L2 for the bitmap, -8 % fabric fetches
     int screen_ext = 1;          // 256-bucket filter: check the bases next to a seed against the flanks' (0: 16-base seeds as they are)
+    int screen_keep_cand = 0;    // diagnostics (option screen_keep_cand, refused unless GF_DIAGNOSTICS is set): keep a copy of the partitioned filter's candidate list
+    gf_screen_view screen_view = {};   // the last partitioned filter's workspace (gf_screen_debug_view)
     int screen_pf4_cap8 = 0;     // tests: capacity of the 4-byte filter's pair list (0: sized from the reads)
     int screen_lds_log2_max = 20;   // coarse LDS bitmap of the screen: at most 2^20 bits (128 KiB)
     int tag_dbg = 0;             // diagnostics of the key-column tagger (option tag_dbg, refused unless GF_DIAGNOSTICS is set)
@@ -162,7 +164,7 @@ struct gf_ctx {
     size_t low_b1 = 0, low_b2 = 0;
 
     // scratch
-    gf::DevBuf cand, cand2, part_ws, tag_stage, verify_stage, bam_stream, bam_recs, asm_table, asm_surv, asm_nodes, asm_jump, asm_big, rowgap, pool_ws, xchg_ws, xchg_ws2, merge_ws, counters, stage_in, stage_out, stage_aux, table, r2_tmp, ext_ws, rs_tmp;
+    gf::DevBuf cand, cand2, cand_keep, part_ws, tag_stage, verify_stage, bam_stream, bam_recs, asm_table, asm_surv, asm_nodes, asm_jump, asm_big, rowgap, pool_ws, xchg_ws, xchg_ws2, merge_ws, counters, stage_in, stage_out, stage_aux, table, r2_tmp, ext_ws, rs_tmp;
     size_t bam_n_recs = 0;       // alignment records gf_bam_pack left in bam_recs (for gf_tag_*_bam)
     size_t bam_stream_len = 0;   // inflated BAM bytes gf_bgzf_inflate left in bam_stream
     // timing
@@ -227,8 +229,17 @@ void free_flank_index(gf_ctx* ctx, FlankIndex& ix);
 // screen.hip
 int build_flank_index_dev(gf_ctx* ctx, int k, FlankIndex& ix);   // index_dev.hip
 int build_sgrp_dev(gf_ctx* ctx, FlankIndex& ix);                 // index_dev.hip: d_sgrp from d_sset / d_sval / d_occ / d_fpk
+// The probed 16-mers of a read of read_len bases under a k-mer screen: base offsets first + j * stride, j < np; `ext` = bases checked
+// behind every seed by the 256-bucket filter (0 when ext_allowed is false: the other filters).  The one source of these numbers for
+// the filter, the verification and the probe column.
+struct ProbeSpots { uint32_t first, stride, np, ext; };
+ProbeSpots probe_geometry(int read_len, int k, bool ext_allowed);
+void fill_probe_geom(gf_ctx* ctx_or_null, const FlankIndex* ix_or_null, size_t n_reads, int read_len, int k, gf_probe_geom* g);   // what the 256-bucket filter probes
+int launch_read_probes(gf_ctx* ctx, const FlankIndex* ix_or_null, const void* d_reads, size_t n_reads, int read_len, int k, void* d_probes, gf_probe_geom* geom);
+// d_probes + built_for: the library's probe column and the geometry it was built for (or null): used only where it is valid for this screen
 int launch_screen(gf_ctx* ctx, const FlankIndex& ix, const void* d_reads, const void* d_nmask, size_t n_reads,
-                  int read_len, int min_hits, void* d_out, size_t cap, void* d_n_out);
+                  int read_len, int min_hits, void* d_out, size_t cap, void* d_n_out, const void* d_probes = nullptr,
+                  const gf_probe_geom* built_for = nullptr);
 // tagger.hip
 int launch_tag(gf_ctx* ctx, const void* d_recs, size_t n, int insert_size, int sd, int clip_dist, int anchor_mapq,
                void* d_out, size_t cap, void* d_n_out, void* d_low, size_t low_cap, void* d_n_low, const void* d_keys = nullptr);

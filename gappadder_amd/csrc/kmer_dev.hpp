@@ -98,7 +98,18 @@ GF_HD uint32_t hash_kmer(K128 v, int log2cap) {
     return (uint32_t)(x >> (64 - log2cap));
 }
 
-GF_HD uint32_t hash_s16_bitmap(uint32_t key, int log2bits) { return (key * 0x9E3779B1u) >> (32 - log2bits); }
+constexpr uint32_t S16_MUL = 0x9E3779B1u;   // multiplier of hash_s16_bitmap (odd: key -> key * S16_MUL is a bijection of the 32-bit words)
+GF_HD uint32_t hash_s16_bitmap(uint32_t key, int log2bits) { return (key * S16_MUL) >> (32 - log2bits); }
+// THE PROBE COLUMN of a read library (gf_read_probes_dev; the 256-bucket filter's pass A streams it instead of the packed rows).
+// For read r and probe j < np one 32-bit word: the scrambled canonical 16-mer of the read at base offset first + j * stride,
+//   word(r, j) = probe_word(the 16 bases as a left-aligned 32-bit word)
+// — exactly what pass A ranks, so it neither extracts nor reverse-complements nor multiplies.  first / stride / np: probe_geometry
+// (gf_internal.hpp).  Layout: one PLANE per probe, plane j at word j * plane, plane = n_reads rounded up to 64, the pad zero:
+// pass A's unit is a wave's tile of 64 consecutive reads, which is 256 aligned contiguous bytes of every plane — two whole 128-byte
+// lines per load instruction, a dword per lane.  (np words per read back to back would make a lane's 12 bytes straddle lines and
+// dwordx3 loads at a 12-byte lane stride.)  The raw 16-mer instead of the scrambled one would leave ~10 VALU instructions per probe in
+// pass A and save nothing in bytes.
+GF_HD uint32_t probe_word(uint32_t w16) { return canon16(w16) * S16_MUL; }
 // second bit of a key inside its level-1 bitmap word: the low product bits, which no word or first-bit index uses while
 // the bitmap has <= 2^27 bits (beyond that the two overlap: still exact, only less selective)
 GF_HD uint32_t hash_s16_bit2(uint32_t key) { return (key * 0x9E3779B1u) & 31u; }

@@ -168,7 +168,6 @@ __device__ __forceinline__ void wave_lds_sync() {
 // (bijective): every bitmap index is a shift of p, and key = p * M^-1 when the exact set is consulted.  The exact set is
 // read four consecutive slots at a time (linear probing, table padded by three wrap-around slots), which settles almost
 // every lookup in one request; the leftovers (3rd+ passing probe of a lane, a run of four foreign keys) take a serial path.
-constexpr uint32_t S16_MUL = 0x9E3779B1u;   // multiplier of hash_s16_bitmap
 constexpr uint32_t mul_inverse_u32(uint32_t a) {
     uint32_t x = a;   // Newton: x <- x (2 - a x) doubles the correct low bits
     for (int i = 0; i < 6; ++i) x *= 2u - a * x;
@@ -282,6 +281,8 @@ struct Part4Params {
     const uint32_t* sgrp;         // grouped exact set {key x 4, ext x 4}
     uint32_t ext;                 // bases checked next to the seed (0: none)
     uint32_t* cand8x;             // per list entry: the ext word of the pair's 16-mer
+    const uint32_t* probes;       // pass A's column form: the library's probe column, `plane` words per probe
+    uint64_t plane;
 };
 constexpr uint32_t PF4_OBUF = 80;     // list entries buffered per wave of pass B (8 + 4 bytes each)
 // the pair's key in the grouped exact set, from group g on: found -> its ext word
@@ -544,6 +545,11 @@ __global__ __launch_bounds__(64 * PF2_WAVES) void pf4_scatter_kernel(Part4Params
 //   Copy-out: the listed lines leave, 32 lanes per line.
 // A wave stages ONE tile at a time (its second tile waits in the prefetch registers until the first one's probes are taken): the
 // 64 KiB of open lines fit for reads up to 160 bases.  All probes of a read are in one group (np <= 4).
+// LDS of pf4_scatter_kernel (unaligned runs): the filter is taken only where this form fits, the whole-line form is chosen on top of it
+constexpr size_t pf4_scatter_lds_bytes(size_t slice_words) {
+    return (size_t)PF2_WAVES * PF2_TILES * slice_words * 4 + (size_t)PF2_BATCH * 5 + (size_t)PF2_NB * (PF4_STAGE + 1) * 4 + (6 * PF2_NB + 8) * 4;
+}
+constexpr size_t pf4_slice_words(uint32_t rb) { return ((size_t)64 * rb + 16 + 7) / 8 * 2; }   // a staged 64-read tile + pad, in words
 constexpr uint32_t PF4_LINE = 32;
 constexpr uint32_t pf4_stage_of(uint32_t G) { return G >= 4 ? 8u : 16u; }   // groups of fill history staged in LDS (what fits beside the lines)
 constexpr size_t pf4_lines_lds_bytes(size_t slice_words, uint32_t G) {
@@ -561,8 +567,12 @@ __device__ __forceinline__ void vm_wait_range(uint32_t n) {   // s_waitcnt vmcnt
 // NG = groups per tile iteration: a read's G x NG probe slots are taken from the staged tile at once and sorted G at a time — k = 31 on
 // 150-base reads has eight probes per read = two groups of four through the same branch-free machinery (before: pf4_scatter_kernel<4>,
 // 16.1 ms per launch at C5 against this kernel's 9.8 ms for C4's three probes).  Probe slots beyond np (np < G x NG) are dead.
-template <uint32_t G, bool BYTES, uint32_t NG = 1>   // BYTES: the probes start at byte boundaries (k = 51, 31, ... at 2 bits per base): one byte permute fetches them
-__global__ __launch_bounds__(64 * PF2_WAVES) void pf4_scatter_lines_kernel(Part4Params Q, uint32_t slice_words) {
+// COL: the probes come from the library's probe column (Part4Params::probes, defined in gf_internal.hpp) instead of the packed rows: a
+// wave's 64 reads are 256 aligned, contiguous bytes of each probe's plane, loaded straight into registers one iteration ahead — no tile
+// in LDS (slice_words == 0), no extraction, canonical form or scrambling per probe.  Everything behind the fetch is the same code.
+template <uint32_t G, bool BYTES, uint32_t NG, bool COL>   // BYTES: the probes start at byte boundaries (k = 51, 31, ... at 2 bits per base): one byte permute fetches them
+__device__ __forceinline__ void pf4_scatter_lines_body(const Part4Params& Q, uint32_t slice_words) {
+    static_assert(!COL || NG == 1, "the column form takes all probes of a read as one group");
     extern __shared__ uint32_t sm[];   // [16 waves x 1 tile][sent][carry 2 x 256 x 32][fill stage 256 x (ST + 1)][hist 3 x 256][written 2 x 256][desc 256][offs 256][lga, lsrc: 2 x (256 + sent lines)][cnt 8]
     const FilterParams& P = Q.F;
     constexpr uint32_t NT = 64 * PF2_WAVES;
@@ -593,6 +603,15 @@ __global__ __launch_bounds__(64 * PF2_WAVES) void pf4_scatter_lines_kernel(Part4
     if (tid < 8) cnt[tid] = 0;
     constexpr int NPF = 4;   // 64 reads x <= 64 B
     u32x4 pf[PF2_TILES][NPF];
+    uint32_t pc[PF2_TILES][G];   // COL: the tiles' column words
+    auto prefetch_col = [&](uint64_t t, uint32_t q) {   // (the planes are padded to whole tiles: every lane of a live tile has a word)
+        const bool on = t < n_tiles;
+#pragma unroll
+        for (uint32_t u = 0; u < G; ++u) {
+            const void* base = uniform_ptr(on ? (const void*)(Q.probes + (uint64_t)u * Q.plane + t * 64) : (const void*)Q.count);
+            vm_load32(pc[q][u], on ? lane * 4 : 0u, base);
+        }
+    };
     auto prefetch = [&](uint64_t t, uint32_t q) {
         const bool on = t < n_tiles;
         const uint64_t byte0 = on ? t * tile_bytes : 0;
@@ -607,7 +626,17 @@ __global__ __launch_bounds__(64 * PF2_WAVES) void pf4_scatter_lines_kernel(Part4
     const uint64_t t_step = (uint64_t)gridDim.x * PF2_WAVES * PF2_TILES;
     const uint64_t n_iter = (n_tiles + t_step - 1) / t_step;
 #pragma unroll
-    for (uint32_t q = 0; q < PF2_TILES; ++q) prefetch(((uint64_t)blockIdx.x * PF2_WAVES + wv) * PF2_TILES + q, q);
+    for (uint32_t q = 0; q < PF2_TILES; ++q) {
+        if constexpr (COL) prefetch_col(((uint64_t)blockIdx.x * PF2_WAVES + wv) * PF2_TILES + q, q);
+        else prefetch(((uint64_t)blockIdx.x * PF2_WAVES + wv) * PF2_TILES + q, q);
+    }
+    if constexpr (COL) {
+        vm_wait<0>();
+#pragma unroll
+        for (uint32_t q = 0; q < PF2_TILES; ++q)
+#pragma unroll
+            for (uint32_t u = 0; u < G; ++u) vm_ready(pc[q][u]);
+    }
     uint32_t hsel = 0, wsel = 0;
     uint32_t stores_since = 0;   // copy-out stores this wave has issued since its last prefetch (wave-uniform)
     __syncthreads();
@@ -617,6 +646,16 @@ __global__ __launch_bounds__(64 * PF2_WAVES) void pf4_scatter_lines_kernel(Part4
         const uint32_t octet0 = (uint32_t)((it * t_step + (uint64_t)blockIdx.x * PF2_WAVES * PF2_TILES) * 8);   // octet of batch index 0
         uint32_t pka[PF2_TILES][G * NG];      // the raw 16-mers of every probe slot of the iteration's tiles
         const uint32_t bit0 = lane * P.rb * 8;
+        if constexpr (COL) {
+            // this iteration's column words have arrived (awaited before the loop / at the end of the previous iteration); the next
+            // iteration's are asked for now and have the whole iteration to come
+#pragma unroll
+            for (uint32_t q = 0; q < PF2_TILES; ++q)
+#pragma unroll
+                for (uint32_t u = 0; u < G; ++u) pka[q][u] = pc[q][u];
+#pragma unroll
+            for (uint32_t q = 0; q < PF2_TILES; ++q) prefetch_col(t0 + q + t_step, q);
+        } else {
 #pragma unroll
         for (uint32_t q = 0; q < PF2_TILES; ++q) {
             // tile q's loads were issued before the loads of the tiles behind it and the previous copy-out's stores: those may stay in flight
@@ -645,6 +684,7 @@ __global__ __launch_bounds__(64 * PF2_WAVES) void pf4_scatter_lines_kernel(Part4
                                   : stream32(tile, bit0 + P.first2 + (NG == 1 || u < P.np ? u : 0u) * P.stride2);
             wave_lds_sync();   // the tile's probes are taken (LDS operations of a wave execute in order): the next tile may take its place
         }
+        }
         stores_since = 0;
 #pragma unroll
       for (uint32_t gi = 0; gi < NG; ++gi) {
@@ -661,7 +701,7 @@ __global__ __launch_bounds__(64 * PF2_WAVES) void pf4_scatter_lines_kernel(Part4
 #pragma unroll
                 for (uint32_t u = 0; u < G; ++u) {
                     if (NG == 1 || gi * G + u < P.np) {
-                        pk[q][u] = canon16(pka[q][gi * G + u]) * S16_MUL;
+                        pk[q][u] = COL ? pka[q][gi * G + u] : canon16(pka[q][gi * G + u]) * S16_MUL;
                         rank[q][u] = atomicAdd(&hist[pk[q][u] >> (32 - PF2_NB_LOG2)], 1u);
                     } else { pk[q][u] = 0u; rank[q][u] = EMPTY32; }
                 }
@@ -782,6 +822,16 @@ __global__ __launch_bounds__(64 * PF2_WAVES) void pf4_scatter_lines_kernel(Part4
         hsel = hsel == 2 ? 0 : hsel + 1;
         wsel ^= 1u;
       }
+        if constexpr (COL) {
+            // The words asked for at the top of this iteration are awaited HERE, not at the top of the next one: a value that crosses the
+            // loop edge may be copied to another register there, and a copy made before the data is in reads the register's old content
+            // (seen: 4 of 86 456 hits lost).  Issued before this iteration's copy-out stores: those may stay in flight.
+            vm_wait_range<0, 15>((uint32_t)__builtin_amdgcn_readfirstlane(stores_since));
+#pragma unroll
+            for (uint32_t q = 0; q < PF2_TILES; ++q)
+#pragma unroll
+                for (uint32_t u = 0; u < G; ++u) vm_ready(pc[q][u]);
+        }
     }
     vm_wait<0>();   // the last prefetch (idle tiles) still targets this wave's registers
     __syncthreads();
@@ -793,6 +843,43 @@ __global__ __launch_bounds__(64 * PF2_WAVES) void pf4_scatter_lines_kernel(Part4
         const uint32_t w = written2[wsel * PF2_NB + i] & TMASK;
         Q.count[(size_t)i * Q.n_writers + writer] = w;
         fill_row(i)[Q.n_groups] = w;
+    }
+}
+
+template <uint32_t G, bool BYTES, uint32_t NG = 1>
+__global__ __launch_bounds__(64 * PF2_WAVES) void pf4_scatter_lines_kernel(Part4Params Q, uint32_t slice_words) {
+    pf4_scatter_lines_body<G, BYTES, NG, false>(Q, slice_words);
+}
+template <uint32_t G>
+__global__ __launch_bounds__(64 * PF2_WAVES) void pf4_scatter_col_kernel(Part4Params Q) {
+    pf4_scatter_lines_body<G, false, 1, true>(Q, 0u);
+}
+
+// ---- the probe column's stand-alone producer (gf_read_probes_dev): a tile of 256 rows staged in LDS, one read per lane, one
+// coalesced store per probe plane
+__global__ __launch_bounds__(256) void read_probes_kernel(const uint8_t* reads, uint64_t n_reads, uint32_t rb, uint32_t first2, uint32_t stride2,
+                                                          uint32_t np, uint64_t plane, uint32_t* probes) {
+    extern __shared__ uint32_t tile[];  // TILE_READS * rb bytes + 16 B pad
+    const uint32_t tid = threadIdx.x;
+    const uint32_t tile_bytes = TILE_READS * rb;
+    const uint64_t total_bytes = n_reads * rb;
+    const uint64_t n_tiles = (n_reads + TILE_READS - 1) / TILE_READS;
+    uint8_t* tb = reinterpret_cast<uint8_t*>(tile);
+    for (uint64_t t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+        const uint64_t byte0 = t * tile_bytes;
+        const uint32_t nbytes = (uint32_t)((total_bytes - byte0) < tile_bytes ? (total_bytes - byte0) : tile_bytes);
+        const uint32_t n16 = nbytes & ~15u;
+        const uint8_t* src = reads + byte0;
+        for (uint32_t i = tid * 16; i < n16; i += 256 * 16)
+            *reinterpret_cast<uint4*>(tb + i) = *reinterpret_cast<const uint4*>(src + i);
+        for (uint32_t i = n16 + tid; i < nbytes; i += 256) tb[i] = src[i];
+        if (tid < 16) tb[nbytes + tid] = 0;
+        __syncthreads();
+        const uint64_t r = t * TILE_READS + tid;
+        if (r < plane)   // (the pad behind the last read, up to a whole 64-read tile, is zero)
+            for (uint32_t j = 0; j < np; ++j)
+                probes[(uint64_t)j * plane + r] = r < n_reads ? probe_word(stream32(tile, tid * rb * 8 + first2 + j * stride2)) : 0u;
+        __syncthreads();
     }
 }
 
@@ -1904,8 +1991,70 @@ __global__ __launch_bounds__(64) void screen_verify_ext_kernel(VerifyParams P) {
     if (stage_n) flush_stage();
 }
 
+// Probed 16-mers of a read: offsets first + j * stride, stride = k - 15.  A k-mer at offset p in [0, L - k] covers the 16-mer
+// offsets [p, p + stride - 1], so the probes must start at first <= k - 16 and reach L - k: np = floor((L - k) / stride) + 1 of
+// them do — one fewer than probing from offset 0 to the end of the read whenever (L - 16) mod stride < k - 16 (150-base reads:
+// k = 51: 3 instead of 4, k = 41: 5 instead of 6, k = 31: 8 instead of 9).  first = the byte-aligned offset closest below k - 16
+// that still reaches (the pipelined kernel fetches byte-aligned probes faster).
+// The 256-bucket filter checks `ext` more bases behind every seed (Part4Params::ext): a k-mer must then contain the 16-mer AND
+// those bases, so the stride is k - 15 - ext and first <= k - 16 - ext; ext = the most (<= 2) that leaves np as it is
+// (150-base reads: k = 51: 2, stride 34; k = 41: 2; k = 31: 1).
+ProbeSpots probe_geometry(int read_len, int k, bool ext_allowed) {
+    const int stride = k - 15;
+    int ext = 0;
+    if (ext_allowed)
+        for (int e = 2; e >= 1 && !ext; --e)
+            if (stride - e >= 1 && (read_len - k) / (stride - e) == (read_len - k) / stride) ext = e;
+    ProbeSpots g;
+    g.ext = (uint32_t)ext;
+    g.stride = (uint32_t)(stride - ext);
+    g.np = (uint32_t)((read_len - k) / (int)g.stride + 1);
+    g.first = (uint32_t)(k - 16 - ext);
+    const int lo = (read_len - k) - (int)(g.np - 1) * (int)g.stride;
+    const uint32_t al = g.first & ~3u;
+    if ((int)al >= lo) g.first = al;
+    return g;
+}
+
+// is the 256-bucket partitioned filter the one launch_screen takes for these reads?
+static bool pf4_chosen(const gf_ctx* ctx, const FlankIndex& ix, size_t n_reads, uint32_t rb) {
+    return (ctx->screen_variant == 16 || ctx->screen_variant == 17 || ctx->screen_variant == 18 || (ctx->screen_variant == 0 && n_reads >= (1u << 20))) &&
+           ix.bm_log2 >= 27 && ix.bm_log2 <= 28 && rb <= 64 && ix.d_sgrp && pf4_scatter_lds_bytes(pf4_slice_words(rb)) <= 156 * 1024;
+}
+
+// ix: the flank index of k when the context has gaps (the column is then wanted only where the filter would take it), or null
+void fill_probe_geom(gf_ctx* ctx, const FlankIndex* ix, size_t n_reads, int read_len, int k, gf_probe_geom* g) {
+    const ProbeSpots pg = probe_geometry(read_len, k, !ctx || ctx->screen_ext != 0);
+    const uint32_t rb = (uint32_t)((read_len + 3) / 4);
+    // a column pays where it is at most half the row; the column form of pass A takes up to four probes of reads the whole-line form takes
+    // (`use` does not repeat two rare conditions of launch_screen — a key set sparse enough for the pipelined kernel although its bitmap
+    // has 2^27 bits, and a pair workspace whose line index passes 32 bits —: a column kept there is checked again at the screen and not streamed)
+    g->reserved = 0;
+    g->use = pg.np >= 1 && pg.np <= 4 && 2 * 4 * pg.np <= rb && rb <= 64 && pf4_lines_lds_bytes(pf4_slice_words(rb), pg.np) <= 160 * 1024 &&
+             (!ctx || !ix || (pf4_chosen(ctx, *ix, n_reads, rb) && ctx->screen_variant != 17 && ctx->screen_variant != 18));
+    g->n_reads = n_reads;
+    g->read_len = (uint32_t)read_len;
+    g->k = (uint32_t)k;
+    g->first = pg.first;
+    g->stride = pg.stride;
+    g->np = pg.np;
+    g->ext = pg.ext;
+}
+
+int launch_read_probes(gf_ctx* ctx, const FlankIndex* ix, const void* d_reads, size_t n_reads, int read_len, int k, void* d_probes, gf_probe_geom* geom) {
+    fill_probe_geom(ctx, ix, n_reads, read_len, k, geom);
+    if (n_reads == 0) return GF_OK;
+    const uint32_t rb = (uint32_t)((read_len + 3) / 4);
+    const uint64_t plane = ((uint64_t)n_reads + 63) & ~(uint64_t)63;
+    const size_t n_tiles = (n_reads + TILE_READS - 1) / TILE_READS;
+    hipLaunchKernelGGL(read_probes_kernel, dim3((unsigned)std::min<size_t>(n_tiles, (size_t)ctx->n_cu * 8)), dim3(256), TILE_READS * rb + 16, ctx->stream,
+                       (const uint8_t*)d_reads, (uint64_t)n_reads, rb, 2 * geom->first, 2 * geom->stride, geom->np, plane, (uint32_t*)d_probes);
+    GF_HIP(ctx, hipGetLastError());
+    return GF_OK;
+}
+
 int launch_screen(gf_ctx* ctx, const FlankIndex& ix, const void* d_reads, const void* d_nmask, size_t n_reads,
-                  int read_len, int min_hits, void* d_out, size_t cap, void* d_n_out) {
+                  int read_len, int min_hits, void* d_out, size_t cap, void* d_n_out, const void* d_probes, const gf_probe_geom* built_for) {
     // one-shot (gf_stream_wait_after_filter): taken here, so that no exit below leaves it armed for a later, unrelated pass
     gf_ctx* const waiter = ctx->after_filter;
     ctx->after_filter = nullptr;
@@ -1924,32 +2073,13 @@ int launch_screen(gf_ctx* ctx, const FlankIndex& ix, const void* d_reads, const 
     F.reads = (const uint8_t*)d_reads;
     F.n_reads = n_reads;
     F.rb = rb;
-    // Probed 16-mers of a read: offsets first + j * stride, stride = k - 15.  A k-mer at offset p in [0, L - k] covers the 16-mer
-    // offsets [p, p + stride - 1], so the probes must start at first <= k - 16 and reach L - k: np = floor((L - k) / stride) + 1 of
-    // them do — one fewer than probing from offset 0 to the end of the read whenever (L - 16) mod stride < k - 16 (150-base reads:
-    // k = 51: 3 instead of 4, k = 41: 5 instead of 6, k = 31: 8 instead of 9).  first = the byte-aligned offset closest below k - 16
-    // that still reaches (the pipelined kernel fetches byte-aligned probes faster).
-    // The 256-bucket filter checks `ext` more bases behind every seed (Part4Params::ext): a k-mer must then contain the 16-mer AND
-    // those bases, so the stride is k - 15 - ext and first <= k - 16 - ext; ext = the most (<= 2) that leaves np as it is
-    // (150-base reads: k = 51: 2, stride 34; k = 41: 2; k = 31: 1).
-    const bool use_pf4 = (ctx->screen_variant == 16 || ctx->screen_variant == 17 || (ctx->screen_variant == 0 && n_reads >= (1u << 20))) && ix.bm_log2 >= 27 &&
-                         ix.bm_log2 <= 28 && rb <= 64 && ix.d_sgrp &&
-                         ((size_t)PF2_WAVES * PF2_TILES * (((size_t)64 * rb + 16 + 7) / 8 * 2) * 4 + (size_t)PF2_BATCH * 5 + (size_t)PF2_NB * (PF4_STAGE + 1) * 4 +
-                          (6 * PF2_NB + 8) * 4) <= 156 * 1024;
-    int ext = 0;
-    if (use_pf4 && ctx->screen_ext)
-        for (int e = 2; e >= 1 && !ext; --e)
-            if (ix.stride - e >= 1 && (read_len - ix.k) / (ix.stride - e) == (read_len - ix.k) / ix.stride) ext = e;
-    const int stride_probe = ix.stride - ext;
-    const uint32_t np_probe = (uint32_t)((read_len - ix.k) / stride_probe + 1);
-    uint32_t first_probe = (uint32_t)(ix.k - 16 - ext);
-    {
-        const int lo = (read_len - ix.k) - (int)(np_probe - 1) * stride_probe;
-        const uint32_t al = first_probe & ~3u;
-        if ((int)al >= lo) first_probe = al;
-    }
-    F.stride2 = 2 * (uint32_t)stride_probe;
-    F.first2 = 2 * first_probe;
+    // the probed 16-mers: probe_geometry (the 256-bucket filter alone checks bases behind a seed)
+    const bool use_pf4 = pf4_chosen(ctx, ix, n_reads, rb);
+    const ProbeSpots pg = probe_geometry(read_len, ix.k, use_pf4 && ctx->screen_ext);
+    const int ext = (int)pg.ext, stride_probe = (int)pg.stride;
+    const uint32_t np_probe = pg.np, first_probe = pg.first;
+    F.stride2 = 2 * pg.stride;
+    F.first2 = 2 * pg.first;
     F.np = np_probe;
     F.bitmap = ix.d_bitmap;
     F.sset = ix.d_sset;
@@ -1998,10 +2128,10 @@ int launch_screen(gf_ctx* ctx, const FlankIndex& ix, const void* d_reads, const 
         Q.F = F;
         Q.sgrp = ix.d_sgrp;
         Q.ext = (uint32_t)ext;
-        const size_t slice_words = ((size_t)64 * rb + 16 + 7) / 8 * 2;
+        const size_t slice_words = pf4_slice_words(rb);
         const size_t tiles64 = (n_reads + 63) / 64;
         const size_t tiles_wg = (size_t)PF2_WAVES * PF2_TILES;      // tiles per workgroup and iteration
-        const size_t lds_a = tiles_wg * slice_words * 4 + (size_t)PF2_BATCH * 5 + (size_t)PF2_NB * (PF4_STAGE + 1) * 4 + (6 * PF2_NB + 8) * 4;
+        const size_t lds_a = pf4_scatter_lds_bytes(slice_words);
         Q.n_writers = (uint32_t)std::min<size_t>(std::min<size_t>((tiles64 + tiles_wg - 1) / tiles_wg, (size_t)ctx->n_cu), 256);   // the pair list carries the writer in 8 bits
         Q.tiles_wg = (uint32_t)tiles_wg;
         const size_t n_iter = (tiles64 + (size_t)Q.n_writers * tiles_wg - 1) / ((size_t)Q.n_writers * tiles_wg);
@@ -2033,11 +2163,23 @@ int launch_screen(gf_ctx* ctx, const FlankIndex& ix, const void* d_reads, const 
         Q.chunk_b = (uint8_t*)(ws + b_cnt + b_seen + b_fill + (size_t)Q.cap8 * 12);
         Q.pairs = (uint32_t*)(ws + b_cnt + b_seen + b_fill + b_c8);
         GF_HIP(ctx, hipMemsetAsync(ws + b_cnt - 256, 0, 256 + b_seen, ctx->stream));
-        ctx->screen_kernels = std::string(lines ? "pf4_scatter_lines_kernel<" : "pf4_scatter_kernel<") + std::to_string(grp) + "u, " +
+        // The library's probe column instead of its rows: only the whole-line form with all probes in one group, and only a column built
+        // for exactly this call's reads and geometry (screen_variant 18: the rows all the same)
+        const size_t plane = (n_reads + 63) & ~(size_t)63;
+        const bool col = lines && Q.n_grp == 1 && d_probes && built_for && ctx->screen_variant != 18 && built_for->use &&
+                         built_for->n_reads == n_reads && built_for->read_len == (uint32_t)read_len && built_for->k == (uint32_t)ix.k &&
+                         built_for->first == pg.first && built_for->stride == pg.stride && built_for->np == pg.np && built_for->ext == pg.ext;
+        Q.probes = col ? (const uint32_t*)d_probes : nullptr;
+        Q.plane = plane;
+        ctx->screen_kernels = col ? "pf4_scatter_col_kernel<" + std::to_string(grp) + "u>,pf4_probe_kernel,pf4_resolve_kernel,pf4_list_kernel" :
+                              std::string(lines ? "pf4_scatter_lines_kernel<" : "pf4_scatter_kernel<") + std::to_string(grp) + "u, " +
                               (((F.first2 & 7u) == 0 && (F.stride2 & 7u) == 0) ? "true" : "false") + (lines ? (Q.n_grp == 2 ? ", 2u" : ", 1u") : "") +
                               ">,pf4_probe_kernel,pf4_resolve_kernel,pf4_list_kernel";
         LaunchTimer tm(ctx, GF_KERNEL_SCREEN);
-        if (lines) {
+        if (col) {
+            void (*scatter)(Part4Params) = grp == 1 ? pf4_scatter_col_kernel<1> : grp == 2 ? pf4_scatter_col_kernel<2> : grp == 3 ? pf4_scatter_col_kernel<3> : pf4_scatter_col_kernel<4>;
+            hipLaunchKernelGGL(scatter, dim3(Q.n_writers), dim3(64 * PF2_WAVES), pf4_lines_lds_bytes(0, grp), ctx->stream, Q);
+        } else if (lines) {
             const bool bytes = (F.first2 & 7u) == 0 && (F.stride2 & 7u) == 0;
             void (*scatter)(Part4Params, uint32_t) =
                 Q.n_grp == 2 ? (bytes ? pf4_scatter_lines_kernel<4, true, 2> : pf4_scatter_lines_kernel<4, false, 2>) :      // (five to eight probes per read: grp == 4)
@@ -2056,6 +2198,14 @@ int launch_screen(gf_ctx* ctx, const FlankIndex& ix, const void* d_reads, const 
         const size_t lds_r = (size_t)4 * 8 * (((2 * (size_t)rb + 3) / 4) * 4 + 4) * 4;
         hipLaunchKernelGGL(pf4_resolve_kernel, dim3((unsigned)ctx->n_cu * 8), dim3(256), lds_r, ctx->stream, Q);
         hipLaunchKernelGGL(pf4_list_kernel, dim3((unsigned)std::min<size_t>((size_t)ctx->n_cu * 4, (n_reads + 32 * 256 - 1) / (32 * 256))), dim3(256), 0, ctx->stream, Q);
+        ctx->screen_view = gf_screen_view{Q.count, Q.fills, Q.pairs, nullptr, nullptr, Q.n_writers, Q.cap, Q.gs, Q.n_groups};
+        if (ctx->screen_keep_cand) {   // diagnostics: the verification passes reuse the candidate buffer, so the tests get a copy of it
+            if ((rc = ensure(ctx, ctx->cand_keep, std::max<size_t>(n_reads, 1) * 4 + 16))) return rc;
+            GF_HIP(ctx, hipMemcpyAsync(ctx->cand_keep.p, d_cnt, 4, hipMemcpyDeviceToDevice, ctx->stream));
+            GF_HIP(ctx, hipMemcpyAsync((uint8_t*)ctx->cand_keep.p + 16, F.cand, n_reads * 4, hipMemcpyDeviceToDevice, ctx->stream));
+            ctx->screen_view.n_cand = (const uint32_t*)ctx->cand_keep.p;
+            ctx->screen_view.cand = (const uint32_t*)((uint8_t*)ctx->cand_keep.p + 16);
+        }
     } else {
         const size_t n_tiles = (n_reads + TILE_READS - 1) / TILE_READS;
         const unsigned grid = (unsigned)std::min<size_t>(n_tiles, (size_t)ctx->n_cu * 8);

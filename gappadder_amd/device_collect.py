@@ -429,7 +429,9 @@ class DeviceCollector:
                 torch.cuda.empty_cache()
         kk = self._usable_pairs(L)
         pipe = Pipeline(gf, len(gaps), L, kk, device=self.dev, anchor_mapq=self.anchor_mapq, clip_dist=self.clip_dist,
-                        k_screen=k_screen or None, keep_read_ids=True)
+                        k_screen=k_screen or None, keep_read_ids=True, probe_column=False)
+        # (no probe column on the file path: a file-born library is screened once, and until the packing kernels write the column while
+        # they hold the bases, building it is a pass of its own — 38 B read + 4 np written per read — that costs more than pass A saves)
         pipe.assemble_in_step = False
         for lb in libs:
             pipe.add_library(lb)

@@ -54,7 +54,7 @@ class DeviceLibrary:
     over all ranks, `first_pair` = this rank's first pair (contiguous shards)."""
 
     def __init__(self, name, is_mean, is_sd, n_reads, d_reads, d_recs, n_recs=None, pull_mates=1, d_nmask=None, n_total=None,
-                 first_pair=0, tag_ctx=None, screen=True, d_rec_keys=None):
+                 first_pair=0, tag_ctx=None, screen=True, d_rec_keys=None, d_probes=None, probe_geom=None):
         self.name, self.is_mean, self.is_sd, self.pull_mates = name, int(is_mean), int(is_sd), int(pull_mates)
         self.n_reads, self.d_reads, self.d_recs, self.d_nmask = int(n_reads), d_reads, d_recs, d_nmask
         self.n_recs = int(n_reads if n_recs is None else n_recs)
@@ -63,6 +63,9 @@ class DeviceLibrary:
         self.tag_ctx = tag_ctx          # a second GapFill (second stream) for the tagger + second hop, or None: the pipeline's
         self.screen = bool(screen)      # False: alignment-based recruitment only (the reference's own mode)
         self.d_rec_keys = d_rec_keys    # the records' key column (gf_alnrec_keys_dev); None: Pipeline.add_library builds it
+        # the reads' probe column and the geometry it was built for (gf_read_probes_dev, or the file path's packing kernels); None:
+        # Pipeline.add_library builds it where it pays
+        self.d_probes, self.probe_geom = d_probes, probe_geom
         self.counts = {}
 
 
@@ -75,7 +78,7 @@ class Results:
 class Pipeline:
     def __init__(self, gf, n_gaps, read_len, k_pairs, device=None, world=1, rank=0, backend="nccl", force_exchange=False,
                  min_count=2, min_contig=40, anchors=(30, 15), clip_dist=250, anchor_mapq=30, k_screen=None, keep_read_ids=False,
-                 key_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False,
+                 key_column=True, probe_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False,
                  extended_fill=False, ext_base_cap=None, rescue_round=False):
         """gf: a GapFill whose gaps (and flanks, when a library is screened) are set.  k_pairs: [(k, k_velvet)] of
         assemble_gaps.py:87-122.  The screen runs at the SMALLEST k of the list: a read that shares a 51-mer with a flank shares
@@ -85,6 +88,10 @@ class Pipeline:
         ({pos, scaffold | MAPQ-0 bit}, built once when a library is added: 7.2 GB for C4's 900 M records) and the tagger streams THAT —
         a record far from every gap, 99 % of a BAM, is decided by (scaffold, position) alone (the reference's `focal_region.has_key(POS)`,
         collect_reads_for_gaps.py:104) — fetching the 32-byte record only of what passes its bin maps.
+        probe_column: the screened libraries keep, beside the packed reads, the 16-mers the filter's first pass probes — np 4-byte words per
+        read, built once when a library is added (k = 51 on 150 bases: 12 of a read's 38 bytes, 10.8 GB for C4's 900 M reads) — and that
+        pass streams THEM; only where 4 * np is at most half a packed read and the column fits (else nothing is built and the pass reads
+        the rows).  A column built for another geometry (k, read length, read count) is rebuilt before it is used.
         anchor_mode: how every pick of the step anchors the flanks on the contigs — "exact" anchors (gf_pick_anchored2_dev) or "align",
         seed-and-extend of the whole flanks (gf_pick_aligned_dev; `anchors` are then the score thresholds); with "align" the Results
         carry `ctg_pick` (gf_ctg_pick per contig) and `align_dropped` / `align_seed_overflow` (gf_pick_aligned_dev's d_stats).
@@ -123,6 +130,7 @@ class Pipeline:
         self.k_screen = int(k_screen) if k_screen else (min(a for a, _ in self.kk) if self.kk else 31)
         self.keep_read_ids = bool(keep_read_ids)
         self.key_column = bool(key_column)
+        self.probe_column = bool(probe_column)
         # merge_in_step: the contig-merge round (assemble_gaps.py:301-306 run_contigs_merge: dedup + ContigsMerger per gap) runs INSIDE the
         # step, on the device, for the gaps the first pick leaves open, followed by a second pick over the merged contigs — the reference
         # merges before it picks (:335-339); a gap the pick closes from its own contigs gains nothing from merging.  Merged contigs are
@@ -181,8 +189,34 @@ class Pipeline:
             torch.cuda.synchronize()
             self._chk(self.lib.gf_alnrec_keys_dev(self.h, lb.d_recs.data_ptr(), lb.n_recs, lb.d_rec_keys.data_ptr()), "gf_alnrec_keys_dev")
             self.gf.sync()
+        if self.probe_column and lb.screen:
+            self._probe_column(lb)
         self.libs.append(lb)
         return lb
+
+    def _probe_column(self, lb):
+        """The library's probe column for THIS pipeline's screen (k_screen, read length, the library's reads): kept when it was built for
+        exactly that, built (again) otherwise; None where a column does not pay or does not fit (the filter then reads the rows)."""
+        if not 16 <= self.k_screen <= min(64, self.L):
+            return
+        want = B.ProbeColumnGeom()
+        self._chk(self.lib.gf_probe_geometry(self.h, lb.n_reads, self.L, self.k_screen, C.byref(want)), "gf_probe_geometry")
+        if lb.d_probes is not None and lb.probe_geom is not None and lb.probe_geom.key() == want.key():
+            return
+        lb.d_probes = lb.probe_geom = None
+        nbytes = self.lib.gf_probe_column_bytes(C.byref(want))
+        if not want.use or not lb.n_reads:
+            return
+        try:
+            d_probes = torch.empty(nbytes // 4, dtype=torch.int32, device=self.dev)
+        except torch.cuda.OutOfMemoryError:
+            return
+        torch.cuda.synchronize()
+        geom = B.ProbeColumnGeom()
+        self._chk(self.lib.gf_read_probes_dev(self.h, lb.d_reads.data_ptr(), lb.n_reads, self.L, self.k_screen, d_probes.data_ptr(), C.byref(geom)),
+                  "gf_read_probes_dev")
+        self.gf.sync()
+        lb.d_probes, lb.probe_geom = d_probes, geom
 
     def _alloc_hit_buffers(self, lb, hit_cap):
         lb.hit_cap = int(hit_cap)
@@ -203,8 +237,10 @@ class Pipeline:
                 # verification pass: beside the filter the two only took turns on the memory system (C4: 36.5 ms together, 26.6 + 10.5 alone)
                 self._chk(lib.gf_stream_wait_after_filter(lb.h2, h), "gf_stream_wait_after_filter")
         if lb.screen:
-            self._chk(lib.gf_screen_reads_dev(h, lb.d_reads.data_ptr(), lb.d_nmask.data_ptr() if lb.d_nmask is not None else None, lb.n_reads,
-                                              self.L, self.k_screen, 1, lb.d_hits.data_ptr(), lb.hit_cap, lb.cp), "gf_screen_reads_dev")
+            col = self.probe_column and lb.d_probes is not None     # (the library checks the geometry again: a stale column is not used)
+            self._chk(lib.gf_screen_reads_probes_dev(h, lb.d_reads.data_ptr(), lb.d_nmask.data_ptr() if lb.d_nmask is not None else None,
+                                                     lb.d_probes.data_ptr() if col else None, C.byref(lb.probe_geom) if col else None, lb.n_reads,
+                                                     self.L, self.k_screen, 1, lb.d_hits.data_ptr(), lb.hit_cap, lb.cp), "gf_screen_reads_probes_dev")
         if tagger:
             self.tagger(lb)
 

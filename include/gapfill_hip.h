@@ -107,7 +107,8 @@ int gf_stream_wait_after_filter(gf_ctx* waiter, gf_ctx* producer);
  * the host comparator instead of the device kernels — same index up to slot order; a test aid, refused unless the environment
  * has GF_DIAGNOSTICS set).
  * Ablation / diagnostic switches (results never change): "screen_variant" (0 automatic, 9 plain, 13 pipelined,
- * 16 partitioned with 256 buckets and 4-byte pairs, 17 the same with unaligned pair runs in its first pass), "screen_ext" (1: the
+ * 16 partitioned with 256 buckets and 4-byte pairs, 17 the same with unaligned pair runs in its first pass, 18 = 16 with the first pass
+ * on the packed rows even where a probe column is given), "screen_ext" (1: the
  * partitioned filter drops seeds whose neighbouring bases are none of the flanks'; 0: 16-base seeds as they are),
  * "screen_verify_ext" (1: seed-and-extend verification when min_hits == 1), "screen_verify_gate",
  * "screen_verify_batch", "screen_stream_policy", "screen_lds_log2_max", "screen_pf4_cap8",
@@ -262,6 +263,44 @@ int gf_screen_reads(gf_ctx* ctx, const uint8_t* packed_reads, const uint32_t* n_
 /* device variant: d_out order is unspecified; *d_n_out (device u32, zeroed by the call) = hits produced. */
 int gf_screen_reads_dev(gf_ctx* ctx, const void* d_packed_reads, const void* d_n_mask_or_null, size_t n_reads,
                         int read_len, int k, int min_hits, void* d_out, size_t cap, void* d_n_out);
+/* The same screen over a library that keeps a PROBE COLUMN beside its packed reads.  The partitioned filter's first pass needs np
+ * 16-mers of a read (k = 51 on 150-base reads: 3 x 4 of its 38 bytes); the column holds exactly those, as the scrambled canonical words
+ * that pass ranks (definition and layout: kmer_dev.hpp, probe_word), one plane per probe, a plane = n_reads rounded up to 64 words.
+ *   gf_probe_geometry     what the partitioned filter probes for (n_reads, read_len, k) — one source with the screen itself — and `use`:
+ *                         whether a column is worth keeping.  It is not where it would not pay or not be taken: more than 4 probes per
+ *                         read, 4 * np above half the packed read bytes (k = 31 on 150 bases: 32 of 38), reads the whole-line filter does
+ *                         not take, and — when the context has its gaps — a key set or read count for which the screen picks another
+ *                         filter (small key sets: the pipelined kernel).  ctx may be NULL: the geometry under the default options.
+ *   gf_probe_column_bytes bytes of the column: np planes of n_reads rounded up to 64 words
+ *   gf_read_probes_dev    builds the column from the packed reads (one pass over them) and reports the geometry it built for
+ *   gf_screen_reads_probes_dev  gf_screen_reads_dev; the first pass streams the column when `built_for` equals the geometry of THIS call
+ *                         and the filter chosen is the whole-line partitioned one — otherwise the packed rows, as without a column
+ *                         (gf_screen_kernels tells which: pf4_scatter_col_kernel / pf4_scatter_lines_kernel).  Same hits either way. */
+typedef struct {
+    uint64_t n_reads;
+    uint32_t read_len, k;
+    uint32_t first, stride, np;   /* probe j of a read: the 16 bases at offset first + j * stride */
+    uint32_t ext;                 /* bases the filter checks behind a seed (they set the stride) */
+    uint32_t use;                 /* 1: the first pass would stream a column of this geometry; 0: it reads the rows, keep none */
+    uint32_t reserved;
+} gf_probe_geom;
+int gf_probe_geometry(gf_ctx* ctx, size_t n_reads, int read_len, int k, gf_probe_geom* out);
+size_t gf_probe_column_bytes(const gf_probe_geom* geom);
+int gf_read_probes_dev(gf_ctx* ctx, const void* d_packed_reads, size_t n_reads, int read_len, int k, void* d_probes /* gf_probe_column_bytes */,
+                       gf_probe_geom* built_for);
+int gf_screen_reads_probes_dev(gf_ctx* ctx, const void* d_packed_reads, const void* d_n_mask_or_null, const void* d_probes_or_null,
+                               const gf_probe_geom* built_for, size_t n_reads, int read_len, int k, int min_hits, void* d_out, size_t cap,
+                               void* d_n_out);
+/* Test aid (GF_E_UNSUPPORTED unless GF_DIAGNOSTICS is set in the environment): what the last screen on this context that took the
+ * partitioned filter left in its workspace, as device pointers that stay valid until the next screen — the pairs of its first pass
+ * ([256 buckets][n_writers][cap] entries, `count` of them written per part, in generation order), the fill history ([bucket][writer][gs]
+ * words, n_groups + 1 of them used) and, with the option "screen_keep_cand" set, a copy of the candidate list the filter handed to the
+ * verification (order unspecified).  The row form and the column form of the first pass must leave all of it identical. */
+typedef struct {
+    const uint32_t *count, *fills, *pairs, *n_cand, *cand;
+    uint32_t n_writers, cap, gs, n_groups;
+} gf_screen_view;
+int gf_screen_debug_view(gf_ctx* ctx, gf_screen_view* out);
 /* The device variant cannot return GF_E_UNSUPPORTED for the one thing the verification may not be able to finish — a read with more
  * than 15 000 (k-mer position, gap) matches, i.e. a low-complexity read against hundreds of flanks that share its k-mers: such a read
  * is counted and its hits are incomplete.  This reads the counter of the LAST gf_screen_reads_dev call on this context (it waits for
