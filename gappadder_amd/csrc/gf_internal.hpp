@@ -222,13 +222,14 @@ int launch_align_ext(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs
 int launch_merge_sets(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t contig_cap, void* d_seq, void* d_seq_len, size_t seq_cap,
                       const void* d_gap_best, size_t n_gaps, const gf_ovl_params* params, void* d_stats, MgSetsView* view);
 
-// index.cpp
+// index.hip
 int build_flank_index(gf_ctx* ctx, int k, FlankIndex** out);
 void free_flank_index(gf_ctx* ctx, FlankIndex& ix);
+// index_dev.hip
+int build_flank_index_dev(gf_ctx* ctx, int k, FlankIndex& ix);
+int build_sgrp_dev(gf_ctx* ctx, FlankIndex& ix);                 // d_sgrp from d_sset / d_sval / d_occ / d_fpk
 
-// screen.hip
-int build_flank_index_dev(gf_ctx* ctx, int k, FlankIndex& ix);   // index_dev.hip
-int build_sgrp_dev(gf_ctx* ctx, FlankIndex& ix);                 // index_dev.hip: d_sgrp from d_sset / d_sval / d_occ / d_fpk
+// screen.hip (launch_read_probes: screen_pf4.hip; what the screen's units share among themselves: screen_dev.hpp)
 // The probed 16-mers of a read of read_len bases under a k-mer screen: base offsets first + j * stride, j < np; `ext` = bases checked
 // behind every seed by the 256-bucket filter (0 when ext_allowed is false: the other filters).  The one source of these numbers for
 // the filter, the verification and the probe column.
@@ -247,13 +248,13 @@ int launch_alnrec_keys(gf_ctx* ctx, const void* d_recs, size_t n, void* d_keys);
 int launch_low_mapq(gf_ctx* ctx, const void* d_recs, size_t n, const gf_dpos* table, size_t n_rows, void* d_out,
                     size_t cap, void* d_n_out, const void* d_low, const void* d_n_low, size_t low_cap);
 
-// assemble.hip
 // second hop: hashed bit map of the table rows' neighbourhoods (hop.hip builds it, tagger.hip asks it)
 constexpr uint32_t HOP_NEAR_LOG2 = 22, HOP_NEAR_SHIFT = 9;
 __host__ __device__ inline uint32_t hop_near_bit(uint32_t scaffold, uint32_t bin) {
     return ((scaffold * 0x9E3779B1u) ^ (bin * 0x85EBCA77u) ^ (bin >> 13)) >> (32 - HOP_NEAR_LOG2);
 }
 constexpr size_t GF_COUNTER_BYTES = 128;   // ctx->counters: [0, 8) screen, [8, 16) assembly / merge, [16, 32) the assembly sweep
+// assemble.hip
 int launch_assemble_sweep(gf_ctx* ctx, const void* d_pool, const void* d_pool_off, size_t n_pools, size_t total_reads, int read_len,
                           int min_count, int min_contig, void* d_contigs, size_t contig_cap, void* d_n_contigs, void* d_seq,
                           size_t seq_cap, void* d_seq_len, void* d_gap_error);

@@ -114,6 +114,7 @@ def _both_forms_agree(gf, d_reads, n, L, k, want_col=True, cap=1 << 21):
     rows = _screen(gf, d_reads, n, L, k, None, None, cap)
     col = _screen(gf, d_reads, n, L, k, d_col, geom, cap)
     assert (COL in col[3]) == want_col and COL not in rows[3], (col[3], rows[3])
+    assert not geom.use or col[3].startswith(COL), col[3]      # `use` and the screen read the same plan: a wanted column, handed over, is streamed
     assert np.array_equal(rows[0], col[0]) and rows[1:3] == col[1:3], (L, k, n, rows[1:3], col[1:3])
     assert (rows[4] is None) == (col[4] is None)
     if rows[4] is not None:      # pass A's pairs and fill history, and the candidate list: the same arrays from both forms
@@ -201,6 +202,28 @@ def test_small_key_set_under_the_automatic_choice_keeps_no_column(gf):
     d_reads = _synth(gf, cfg, n // 2, 150)
     rows, _, _ = _both_forms_agree(gf, d_reads, n, 150, 51, want_col=False)
     assert "pf4_" not in rows[3]
+
+
+def test_sparse_key_set_with_a_large_bitmap_keeps_no_column(gf):
+    """A 2^27-bit level-1 bitmap and 2^20 reads make the partitioned filter eligible, yet a key set this sparse (100 gaps) takes the
+    pipelined kernel all the same.  `use` says so — no column is built for a screen that would never stream it — and a column handed in all
+    the same is not streamed; the hits are those of the rows."""
+    from gappadder_amd import _lib as B
+    from gappadder_amd.hip_api import GapFill
+    gf.set_option("bitmap_log2", 27)
+    try:
+        cfg = GapFill.synth_cfg(seed=20260005, scaffold_len=5_000_000, n_scaffolds=5, gaps_per_scaffold=20, gap_len=2000)
+        gaps, flanks = GapFill.synth_layout(cfg)
+        gf.set_gaps(gaps, 5, flanks)
+        n = (1 << 20) + 130
+        d_reads = _synth(gf, cfg, n // 2, 150)
+        g = B.ProbeColumnGeom()
+        assert B.lib().gf_probe_geometry(gf.handle, n, 150, 51, C.byref(g)) == 0
+        assert g.use == 0 and (g.first, g.stride, g.np, g.ext) == T.geometry(150, 51)
+        rows, _, _ = _both_forms_agree(gf, d_reads, n, 150, 51, want_col=False)
+        assert rows[3].startswith("screen_filter_pipe_kernel<") and rows[1] > 0, rows[3]
+    finally:
+        gf.set_option("bitmap_log2", 0)
 
 
 def test_two_libraries_and_a_column_built_for_another_k(forced):

@@ -90,10 +90,10 @@ def test_column_loads_are_not_touched_before_their_wait(tmp_path):
     n, _, found = CK.check(str(bad), "pf4_scatter_col_kernel")
     assert n == 1 and len(found) == 1 and "v29" in found[0]
     csrc = os.path.join(ROOT, "gappadder_amd", "csrc")
-    out = tmp_path / "screen.s"
+    out = tmp_path / "screen_pf4.s"
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     subprocess.check_call([hipcc, "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "--cuda-device-only", "-S",
-                           os.path.join(csrc, "screen.hip"), "-o", str(out)], stderr=subprocess.DEVNULL)
+                           os.path.join(csrc, "screen_pf4.hip"), "-o", str(out)], stderr=subprocess.DEVNULL)
     n, kernels, found = CK.check(str(out), "pf4_scatter_col_kernel")
     assert len(kernels) == 4 and n == 2 * 2 * (1 + 2 + 3 + 4), (n, kernels)      # prologue + loop, two tiles, G words each
     assert not found, found
