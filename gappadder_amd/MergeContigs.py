@@ -277,8 +277,77 @@ def merge_sets(gf, rec_sets, kmer_len_quick=10, params=None):
             for wi, (nodes, ed) in enumerate(zip(nodes_of, edges))]
 
 
-def merge_contigs(gf, working_folder, id_list, kmer_len_quick=10, params=None):
-    """merge_contigs (MergeContigs.py:66-99) for every gap of id_list.  Returns {gap id: number of NEW_CONTIG_MERGE records}."""
+ENGINES = ("host", "device")
+# engine="device": what the calls of this process did with their sets — merged from the device's export, handed to the host path because the
+# device left them alone (status size / graph), handed to the host path for a host-side rule (the 1 MB rule, an empty record)
+DEVICE_COUNTS = {"calls": 0, "device_sets": 0, "fell_back_sets": 0, "host_rule_sets": 0}
+LAST_FELL_BACK = []               # gap ids of the last engine="device" call that went through the host path (device statuses size / graph)
+
+
+def _write_gap(folder, gid, nodup, m, final, done):
+    """One gap's files behind contigs.fa_no_dup.fa (already written): merge_edges.txt, …merge.info, …merged.fa and the new contigs.fa.
+    m = merge_sets' dict of the gap; final = the second dedup's records, or None: drop_contained here."""
+    nodes, new = m["nodes"], m["new"]
+    with open(folder + "merge_edges.txt", "w") as f:
+        for i, j, mode, ov in m["edges"]:
+            f.write("%s %s %s %s %s %d\n" % (nodes[i // 2][0], "-" if i & 1 else "+", nodes[j // 2][0], "-" if j & 1 else "+", mode, ov))
+    names = [n for n, _ in nodes]
+    with open(folder + "contigs.fa_no_dup.fa.merge.info", "w") as f:
+        for name, _, path in new:
+            f.write("%s   %s\n" % (name, " ".join(_node_name(names, v) for v in path)))
+    merged_recs = [(n, s) for n, s, _ in new] + nodup
+    _write_fasta(folder + "contigs.fa_no_dup.fa.merged.fa", merged_recs, 60)                  # ContigsMerger dumps 60 columns
+    if final is None:
+        final = drop_contained(merged_recs)
+    try:            # per gap: a failed write leaves THIS gap's contigs.fa as it was (the merged set goes to a temporary name first)
+        _write_fasta(folder + "contigs.fa.merged.tmp", final)
+        _swap_in(folder, "contigs.fa.merged.tmp")
+        done[gid] = len(new)
+    except OSError as e:
+        import sys
+        sys.stderr.write("contig merging: gap %s keeps its contigs (%r)\n" % (gid, e))
+        done[gid] = 0
+
+
+def _merge_contigs_device(gf, working_folder, id_list, kmer_len_quick, params):
+    """merge_contigs from ONE GapFill.merge_sets_device call over all gaps of the round: both dedups, the edges, the paths and the
+    merged strings come from the device's export; no per-gap GPU call and no drop_contained here.  The rules that need no GPU stay on
+    the host: a gap whose contigs.fa alone exceeds 1 MB (its de-duplicated file may too: MergeContigs.py:70-74) or holds an empty record
+    takes the host path, as do the sets the device left alone (status size / graph) — the tree is the same whatever the engine."""
+    ids, recs = _sets(working_folder, id_list)
+    dev, host_ids = [], []
+    for gid, r in zip(ids, recs):
+        if sum(len(n) + len(s) + 3 for n, s in r) > 1000000 or any(not s for _, s in r):
+            host_ids.append(gid)
+        else:
+            dev.append((gid, r))
+    DEVICE_COUNTS["calls"] += 1
+    DEVICE_COUNTS["host_rule_sets"] += len(host_ids)
+    del LAST_FELL_BACK[:]
+    done = {}
+    res = gf.merge_sets_device([r for _, r in dev], params, kmer_len_quick) if dev else []
+    for (gid, r), m in zip(dev, res):
+        if m["status"] in ("size", "graph"):
+            LAST_FELL_BACK.append(gid)
+            continue
+        folder = "%svelvet_temp/%s/" % (working_folder, gid)
+        _write_fasta(folder + "contigs.fa_no_dup.fa", m["nodup"])        # (at most the size of contigs.fa: the 1 MB rule cannot apply)
+        _write_gap(folder, gid, m["nodup"], m, m["final"], done)
+    DEVICE_COUNTS["device_sets"] += len(dev) - len(LAST_FELL_BACK)
+    DEVICE_COUNTS["fell_back_sets"] += len(LAST_FELL_BACK)
+    if host_ids or LAST_FELL_BACK:
+        done.update(merge_contigs(gf, working_folder, host_ids + LAST_FELL_BACK, kmer_len_quick, params))
+    return done
+
+
+def merge_contigs(gf, working_folder, id_list, kmer_len_quick=10, params=None, engine="host"):
+    """merge_contigs (MergeContigs.py:66-99) for every gap of id_list.  Returns {gap id: number of NEW_CONTIG_MERGE records}.
+    engine: "host" — batched GPU calls for the edges and the path steps, graph and dedups on the host; "device" — one device call with
+    the graph exported (_merge_contigs_device; DEVICE_COUNTS, LAST_FELL_BACK).  Same files, same return value."""
+    if engine not in ENGINES:
+        raise ValueError("merge_contigs: engine must be 'host' or 'device', not %r" % (engine,))
+    if engine == "device":
+        return _merge_contigs_device(gf, working_folder, id_list, kmer_len_quick, params)
     ids, recs = _sets(working_folder, id_list)
     work = []                                                  # (gid, folder, de-duplicated records)
     done = {}
@@ -296,23 +365,5 @@ def merge_contigs(gf, working_folder, id_list, kmer_len_quick=10, params=None):
             continue
         work.append((gid, folder, nodup))
     for (gid, folder, nodup), m in zip(work, merge_sets(gf, [w[2] for w in work], kmer_len_quick, params)):
-        nodes, new = m["nodes"], m["new"]
-        with open(folder + "merge_edges.txt", "w") as f:
-            for i, j, mode, ov in m["edges"]:
-                f.write("%s %s %s %s %s %d\n" % (nodes[i // 2][0], "-" if i & 1 else "+", nodes[j // 2][0], "-" if j & 1 else "+", mode, ov))
-        names = [n for n, _ in nodes]
-        with open(folder + "contigs.fa_no_dup.fa.merge.info", "w") as f:
-            for name, _, path in new:
-                f.write("%s   %s\n" % (name, " ".join(_node_name(names, v) for v in path)))
-        merged_recs = [(n, s) for n, s, _ in new] + nodup
-        _write_fasta(folder + "contigs.fa_no_dup.fa.merged.fa", merged_recs, 60)                  # ContigsMerger dumps 60 columns
-        final = drop_contained(merged_recs)
-        try:            # per gap: a failed write leaves THIS gap's contigs.fa as it was (the merged set goes to a temporary name first)
-            _write_fasta(folder + "contigs.fa.merged.tmp", final)
-            _swap_in(folder, "contigs.fa.merged.tmp")
-            done[gid] = len(new)
-        except OSError as e:
-            import sys
-            sys.stderr.write("contig merging: gap %s keeps its contigs (%r)\n" % (gid, e))
-            done[gid] = 0
+        _write_gap(folder, gid, nodup, m, None, done)
     return done

@@ -42,6 +42,17 @@ MG_N_PRE, MG_N_SETS, MG_SKIPPED, MG_N_PAIRS, MG_QC_FLAGS, MG_N_JOBS, MG_ERR, MG_
 MG_SKIPPED_GRAPH = 16
 MG_WORDS = 32
 
+# the merge round with its graph exported (gf_merge_sets, merge_export.hip): records, set statuses, statistics words (u32[16]), capacity flags
+MSET = np.dtype([(n, "<u4") for n in ("status", "n_kept", "n_edges", "edge_off", "n_new", "new_off", "final_off", "n_truncated")])
+MEDGE = np.dtype([(n, "<u4") for n in ("i", "j", "mode", "overlap")])
+MNEW = np.dtype([("set", "<u4"), ("n_nodes", "<u4"), ("path_off", "<u4"), ("length", "<u4"), ("seq_off", "<u8")])
+assert MSET.itemsize == 32 and MEDGE.itemsize == 16 and MNEW.itemsize == 24
+MSET_MERGED, MSET_NOTHING, MSET_SIZE, MSET_GRAPH = range(4)
+MSET_NAMES = {MSET_MERGED: "merged", MSET_NOTHING: "nothing", MSET_SIZE: "size", MSET_GRAPH: "graph"}
+(MX_TRIED, MX_NOTHING, MX_SKIPPED_SIZE, MX_SKIPPED_GRAPH, MX_PAIRS, MX_EDGES, MX_PATHS, MX_TRUNCATED, MX_FLAGS, MX_PATH_BYTES, MX_FINALS,
+ MX_ROUND_ERR, MX_SEQ_BYTES) = range(13)
+MX_NEW_RECORDS, MX_EDGE_RECORDS, MX_WORDS = 14, 15, 16
+
 # words of the second round's statistics (round2.hip, u32[16])
 R2_KMERS, R2_TAB_FULL, R2_HITS, R2_UNIQUE, R2_TRIED, R2_WITH, R2_ROWS, R2_FIRST, R2_APPEND_ERR, R2_N2, R2_POOL_OVF = 0, 1, 2, 3, 4, 5, 6, 8, 9, 10, 11
 R2_WORDS, R2_MAX_LIBS = 16, 16
@@ -66,6 +77,11 @@ class ProbeColumnGeom(C.Structure):
     def key(self):
         """What a column depends on (not `use`, which is advice, nor the reserved word)."""
         return (self.n_reads, self.read_len, self.k, self.first, self.stride, self.np, self.ext)
+
+
+class MergeCaps(C.Structure):
+    """gf_mcaps: capacities of gf_merge_sets' output lists."""
+    _fields_ = [(n, C.c_size_t) for n in ("edges", "news", "path_bytes", "seq_bytes", "finals")]
 
 
 class ScreenView(C.Structure):
@@ -165,6 +181,8 @@ def lib():
         "gf_pick_aligned_from_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, vp, vp, vp, vp, vp]),
         "gf_bridging_reads": (i32, [vp, C.c_char_p, vp, vp, C.c_char_p, vp, vp, sz, i32, i32, vp]),
         "gf_merge_open_gaps_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, i32, i32, vp, vp, i32, vp]),
+        "gf_merge_sets_dev": (i32, [vp, vp, sz, sz, vp, vp, sz, sz, vp, i32, i32, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, vp]),
+        "gf_merge_sets": (i32, [vp, C.c_char_p, vp, vp, sz, vp, i32, i32, C.POINTER(MergeCaps), vp, vp, vp, vp, vp, vp, vp, vp]),
         "gf_both_unmapped_reads_dev": (i32, [vp, vp, sz, sz, vp, vp, sz, vp]),
         "gf_contig_kmer_table_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, i32, vp, i32, vp]),
         "gf_recruit_by_contigs_dev": (i32, [vp, vp, vp, sz, i32, vp, vp, sz, i32, i32, vp, i32, vp, sz, vp]),

@@ -277,11 +277,14 @@ def bridging_reads_batch(items, seed_len=30, budget=2):
 
 
 class GapAssembler:
-    def __init__(self, sf_fai, sf_pos, n_jobs, working_space, kmer_list=None, gf=None, bam_list=None, samtools_path=None, flank_anchor="exact"):
-        """flank_anchor: how every ContigsSelection round anchors the flanks on the contigs, "exact" or "align" (pick_contigs.py)."""
+    def __init__(self, sf_fai, sf_pos, n_jobs, working_space, kmer_list=None, gf=None, bam_list=None, samtools_path=None, flank_anchor="exact",
+                 contig_merger="host"):
+        """flank_anchor: how every ContigsSelection round anchors the flanks on the contigs, "exact" or "align" (pick_contigs.py);
+        contig_merger: the engine of every contig-merge round, "host" or "device" (MergeContigs.merge_contigs)."""
         global kmer_len_list, working_folder, _gf
         self.bam_list = list(bam_list or [])
         self.flank_anchor = flank_anchor
+        self.contig_merger = contig_merger
         self.samtools_path = samtools_path
         if kmer_list is not None:
             kmer_len_list = list(kmer_list)
@@ -312,7 +315,7 @@ class GapAssembler:
         from .MergeContigs import merge_contigs
         from ._lib import GapFillError
         try:
-            return merge_contigs(_ctx(), working_folder, fa_list)
+            return merge_contigs(_ctx(), working_folder, fa_list, engine=self.contig_merger)
         except GapFillError:            # a faulted kernel / HIP error: the context is not fit to go on picking and assembling with
             raise
         except (OSError, ValueError) as e:      # host-side trouble with one gap's files: the optional step is skipped, the picks go on

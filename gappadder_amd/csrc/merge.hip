@@ -15,6 +15,7 @@
 #include <cstring>
 
 #include "gf_internal.hpp"
+#include "merge_dev.hpp"
 
 namespace gf {
 
@@ -187,7 +188,6 @@ __global__ __launch_bounds__(1024) void quick_check_kernel(QcParams P) {
 // whenever the indel score is, which the entry point requires); the reference's trace-back table is not needed: all its caller
 // uses of the trace back is whether the path starts on row 0 or on column 0, two bits that travel with the scores; the end cell is
 // kept per thread as (score, rank in the reference's scan order) and reduced at the end.
-constexpr uint32_t OV_MAXLEN = 8190;
 struct OvParams {
     const char* seq;
     const unsigned long long* contig_off;
@@ -367,94 +367,7 @@ __global__ __launch_bounds__(OV_NT) void overlap_eval_kernel(OvParams P) {
 //                                         mode (ov_evaluate above), merged strings appended to the contig list as records with k = kv = 0
 // Everything order-dependent follows the host twin exactly (tests/test_gpu_merge.py compares the two on the reference's own KAT sets and
 // on random sets); capacities that overflow set bits of stats[MG_ERR].
-constexpr uint32_t MG_MAX_IN = 1024;      // contigs of an open gap that the dedup takes (more: the gap is left alone, counted in stats[MG_SKIPPED])
-constexpr uint32_t MG_MAX_NODES = 256;    // nodes of a set (2 x max_set)
-constexpr uint32_t MG_MAX_EDGES = 4096;   // edges of one set's graph
-constexpr uint32_t MG_MAX_PATHS = 2048;   // paths of one set before the twin removal
-constexpr uint32_t MG_PATH_BYTES = 1u << 17;   // their nodes (bytes) per workgroup
-constexpr uint32_t MG_MIN_NODE = 30, MG_MAX_NODE = OV_MAXLEN;
-constexpr uint32_t MG_PER_ROOT = 21;      // MAX_CONTIG_IN_PATH_COUNT + 1 (ContigsCompactor.cpp:34; MergeContigs.find_paths)
-enum { MG_N_PRE = 0, MG_N_SETS = 1, MG_SKIPPED = 2, MG_N_PAIRS = 3, MG_QC_FLAGS = 4, MG_N_JOBS = 5, MG_ERR = 6, MG_N0 = 7, MG_N_EDGES = 8,
-       MG_SETS_WITH_JOBS = 9, MG_Q_JOBS = 10, MG_Q_SETS = 11, MG_JOB_NODES = 12, MG_Q_DEDUP = 13, MG_Q_COPY = 14, MG_N_NODES = 15, MG_SKIPPED_GRAPH = 16,
-       MG_WORDS = 32 };
-// error bits: capacities of this call (the caller sizes them: raise).  A set whose GRAPH outgrows the round's own limits — more than
-// MG_MAX_EDGES edges, MG_MAX_PATHS paths or MG_PATH_BYTES path nodes (the contig graph of a repeat-bearing gap has thousands of paths) —
-// is left alone and counted in stats[MG_SKIPPED_GRAPH], like the sets of more than max_set contigs in stats[MG_SKIPPED]
-constexpr uint32_t MG_E_SEQ = 1, MG_E_PAIRS = 2, MG_E_CONTIGS = 32, MG_E_OUTSEQ = 64;
-constexpr uint32_t MG_SETS_NO_MAX_SET = 0;   // max_set of MG_MODE_SETS: the dedup alone, no set limit applies
-
-struct MgJob { uint32_t set, off, len; };   // path = job_nodes[off .. off + len)
-
-struct MgParams {
-    gf_contig* contigs;
-    uint32_t* n_contigs;
-    uint32_t contig_cap;
-    char* seq;
-    unsigned long long* seq_len;
-    unsigned long long seq_cap;
-    const unsigned long long* gap_best;
-    uint32_t n_gaps, max_set;
-    uint32_t* stats;
-    // workspace
-    uint32_t* cnt;          // [n_gaps] contigs of an open gap, later the fill cursor
-    uint32_t* pre_of_gap;   // [n_gaps]
-    uint32_t* pre_gap;      // [n_gaps]
-    uint32_t* pre_off;      // [n_gaps + 1]
-    uint32_t* ids;          // [contig_cap]
-    uint32_t* kept_n;       // [n_gaps] contigs left by the dedup
-    uint32_t* node_n;       // [n_gaps] ... of node length
-    unsigned long long* node_bytes;   // [n_gaps]
-    uint32_t* set_pre;      // [n_gaps]
-    unsigned long long* set_base;     // [n_gaps] first byte of the set in mseq
-    unsigned long long* contig_off;   // [node_cap + 1]
-    unsigned long long* set_off;      // [n_gaps + 1]
-    uint32_t node_cap;
-    char* mseq;
-    unsigned long long mseq_cap;
-    // graph + paths
-    const gf_qcpair* pairs;
-    const gf_ovl_result* res;
-    uint32_t pair_cap;
-    const uint32_t* set_range;        // [2 * set]
-    uint8_t* path_ws;                 // per workgroup: MG_PATH_BYTES of path nodes
-    int32_t* dp_dist;                 // per workgroup: [MG_MAX_NODES roots][MG_MAX_NODES]
-    uint8_t* dp_pred;                 // ... pred, and 1 byte of flags (bit 0 reached, bit 1 ends with its node twice)
-    uint8_t* dp_flag;
-    MgJob* jobs;
-    uint32_t job_cap;
-    uint8_t* job_nodes;
-    uint32_t job_node_cap;
-    uint32_t* set_jobs;               // [2 * set]: first job, jobs
-    uint32_t* set_rec;                // [set]: contig record of the set's first job
-    char* cur_ws;                     // per workgroup: 2 x 16 384 bytes (the running string and its successor)
-    gf_ovl_params pr;
-    // order of a gap's contigs = the order of its contigs.fa (assemble_gaps.py:124-135): the (k, kv) pairs in list order, inside a pair by
-    // (length descending, sequence) — n_k > 0; n_k == 0: record order (contig index)
-    uint32_t n_k;
-    uint16_t k_list[16], kv_list[16];
-    // the rescue round's two uses of these kernels (gf_merge_rescue_dev, gf_rescue_bridges_dev; MG_MODE_*): which records take part,
-    // and where the rescue set's marker records (k = kv = GF_RESCUE_MARK, the bridges) stand in a gap's order
-    uint32_t mode;
-    const uint32_t* gap_bridges;      // [n_gaps] bridges per gap (MG_MODE_RESCUE: a gap without one takes no part)
-    const uint32_t* merge_n0;         // the first merge round's first record (its stats[MG_N0]) ...
-    const uint32_t* rescue_first;     // ... and the first bridge: [*merge_n0, *rescue_first) = the first merge's records, no part of the rescue set
-};
-
-__device__ __forceinline__ uint32_t mg_block_scan_excl(uint32_t v, uint32_t* s_w, uint32_t* total) {   // blockDim.x a multiple of 64, <= 1024
-    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t x = v;
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d);
-        if ((int)lane >= d) x += y;
-    }
-    __syncthreads();
-    if (lane == 63) s_w[w] = x;
-    __syncthreads();
-    uint32_t base = 0, tot = 0;
-    for (uint32_t q = 0; q < (blockDim.x >> 6); ++q) { const uint32_t t = s_w[q]; if (q < w) base += t; tot += t; }
-    *total = tot;
-    return base + x - v;
-}
+// (the round's limits, statistics words, MgParams and the block scan: merge_dev.hpp, shared with merge_export.hip)
 
 // a list that overflowed before the round (the assembly's counters beyond the capacities): the round is a no-op that keeps the overflow
 // visible — no gap is counted, so no set takes part, stats[MG_ERR] says why, and *n_contigs / *seq_len stay beyond the caps
@@ -787,7 +700,7 @@ __global__ __launch_bounds__(256) void mg_paths_kernel(MgParams P) {
         }
         __syncthreads();
         const uint32_t E = s_n_edges;
-        if (E > MG_MAX_EDGES) { if (tid == 0) atomicAdd(&P.stats[MG_SKIPPED_GRAPH], 1u); continue; }
+        if (E > MG_MAX_EDGES) { if (tid == 0) { atomicAdd(&P.stats[MG_SKIPPED_GRAPH], 1u); if (P.x_graph) P.x_graph[st] = 1; } continue; }
         if (E == 0) continue;
         if (tid == 0) atomicAdd(&P.stats[MG_N_EDGES], E);
         // adjacency lists in the order the reference adds the edges: pairs (i, j) ascending -> sort by (src, i, j)
@@ -967,7 +880,7 @@ __global__ __launch_bounds__(256) void mg_paths_kernel(MgParams P) {
             }
         }
         __syncthreads();
-        if (s_bad) { if (tid == 0) atomicAdd(&P.stats[MG_SKIPPED_GRAPH], 1u); continue; }
+        if (s_bad) { if (tid == 0) { atomicAdd(&P.stats[MG_SKIPPED_GRAPH], 1u); if (P.x_graph) P.x_graph[st] = 1; } continue; }
         const uint32_t NP = s_n_paths;
         if (NP == 0) continue;
         __threadfence_block();
@@ -1008,7 +921,7 @@ __global__ __launch_bounds__(256) void mg_paths_kernel(MgParams P) {
             if (nj) { jb = atomicAdd(&P.stats[MG_N_JOBS], nj); bb = atomicAdd(&P.stats[MG_JOB_NODES], nb); }
             // (no room in the job list — a repeat-bearing draft with thousands of paths per gap: the set is left alone and counted; its
             // reserved slots stay EMPTY and the string kernel passes over them)
-            if (nj && (jb + nj > P.job_cap || bb + nb > P.job_node_cap)) { atomicAdd(&P.stats[MG_SKIPPED_GRAPH], 1u); nj = 0; }
+            if (nj && (jb + nj > P.job_cap || bb + nb > P.job_node_cap)) { atomicAdd(&P.stats[MG_SKIPPED_GRAPH], 1u); nj = 0; if (P.x_graph) P.x_graph[st] = 1; }
             s_n_edges = jb; s_n_comp = bb; s_n_roots = nj;      // (reused as broadcast slots)
             if (nj) { P.set_jobs[2 * st] = jb; P.set_jobs[2 * st + 1] = nj; atomicAdd(&P.stats[MG_SETS_WITH_JOBS], 1u); }
         }
@@ -1081,7 +994,8 @@ __global__ __launch_bounds__(OV_NT) void mg_strings_kernel(MgParams P) {
             for (int i = (int)tid; i < n1; i += OV_NT) { const char ch = src[rc ? n1 - 1 - i : i]; cur[i] = rc ? mg_comp(ch) : ch; }
         }
         __syncthreads();
-        for (uint32_t step = 1; step < job.len; ++step) {
+        uint32_t step = 1;
+        for (; step < job.len; ++step) {
             int n2;
             const char* src2 = node_src(path[step], &n2);
             if (n1 > (int)MG_MAX_NODE || n2 > (int)MG_MAX_NODE) break;      // grown beyond the kernel's reach: the path ends here
@@ -1108,6 +1022,7 @@ __global__ __launch_bounds__(OV_NT) void mg_strings_kernel(MgParams P) {
             char* t = cur; cur = nxt; nxt = t;
             n1 = nn;
         }
+        if (P.x_used && tid == 0) P.x_used[ji] = step;      // (the export: the nodes actually merged — the path may have ended early above)
         // the merged string becomes a contig record of the set's gap (k = kv = 0: a merged contig)
         const uint32_t rec = P.set_rec[st] + (ji - P.set_jobs[2 * st]);
         if (tid == 0) s_out = atomicAdd(P.seq_len, (unsigned long long)n1);
@@ -1136,7 +1051,7 @@ static inline size_t mg_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
 int launch_merge_round(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t contig_cap, void* d_seq, void* d_seq_len, size_t seq_cap,
                        const void* d_gap_best, size_t n_gaps, const gf_ovl_params* params, int kq, int max_set, const int* k_list, const int* kv_list,
-                       int n_k, void* d_stats, const MgRescueArgs* rs = nullptr) {
+                       int n_k, void* d_stats, const MgRescueArgs* rs, MgParams* exported) {
     const unsigned grid = (unsigned)ctx->n_cu;
     const size_t ng = n_gaps;
     const size_t node_cap = contig_cap;
@@ -1153,6 +1068,8 @@ int launch_merge_round(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t c
                  o_dist = take((size_t)grid * MG_MAX_NODES * MG_MAX_NODES * 4), o_pred = take((size_t)grid * MG_MAX_NODES * MG_MAX_NODES),
                  o_flag = take((size_t)grid * MG_MAX_NODES * MG_MAX_NODES), o_jobs = take(job_cap * sizeof(MgJob)), o_jnodes = take(job_node_cap),
                  o_sjobs = take(ng * 8), o_srec = take(ng * 4), o_cur = take((size_t)grid * 32768), o_qcmat = take((size_t)grid * (((size_t)MG_MAX_NODES * MG_MAX_NODES + 31) / 32 + 1) * 4);
+    // (the export alone, behind everything else: the sets left alone for their graph, the nodes every path merged)
+    const size_t o_xgraph = exported ? take(ng * 4) : 0, o_xused = exported ? take(job_cap * 4) : 0;
     int rc;
     if ((rc = ensure(ctx, ctx->merge_ws, at + 256))) return rc;
     if ((rc = ensure(ctx, ctx->counters, GF_COUNTER_BYTES))) return rc;
@@ -1184,8 +1101,10 @@ int launch_merge_round(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t c
             rs->view->pre_of_gap = P.pre_of_gap; rs->view->pre_off = P.pre_off; rs->view->kept_n = P.kept_n; rs->view->ids = P.ids;
         }
     }
+    if (exported) { P.x_graph = (uint32_t*)(W + o_xgraph); P.x_used = (uint32_t*)(W + o_xused); *exported = P; }
     LaunchTimer tm(ctx, GF_KERNEL_MERGE);
     GF_HIP(ctx, hipMemsetAsync(d_stats, 0, MG_WORDS * 4, ctx->stream));
+    if (exported) GF_HIP(ctx, hipMemsetAsync(P.x_graph, 0, ng * 4, ctx->stream));
     GF_HIP(ctx, hipMemsetAsync(P.cnt, 0, ng * 4, ctx->stream));
     GF_HIP(ctx, hipMemsetAsync(P.jobs, 0xFF, job_cap * sizeof(MgJob), ctx->stream));
     uint32_t* d_next_qc = (uint32_t*)ctx->counters.p + 9;
@@ -1247,7 +1166,7 @@ int launch_merge_sets(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t co
                       const void* d_gap_best, size_t n_gaps, const gf_ovl_params* params, void* d_stats, MgSetsView* view) {
     MgRescueArgs rs{MG_MODE_SETS, nullptr, nullptr, nullptr, view};
     return launch_merge_round(ctx, d_contigs, d_n_contigs, contig_cap, d_seq, d_seq_len, seq_cap, d_gap_best, n_gaps, params, 8, MG_SETS_NO_MAX_SET,
-                              nullptr, nullptr, 0, d_stats, &rs);
+                              nullptr, nullptr, 0, d_stats, &rs, nullptr);
 }
 
 }  // namespace gf
@@ -1430,7 +1349,7 @@ int gf_merge_open_gaps_dev(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size
     GF_HIP(ctx, hipSetDevice(ctx->device));
     if (!n_gaps) { GF_HIP(ctx, hipMemsetAsync(d_stats, 0, MG_WORDS * 4, ctx->stream)); return GF_OK; }
     return launch_merge_round(ctx, d_contigs, d_n_contigs, contig_cap, d_seq, d_seq_len, seq_cap, d_gap_best, n_gaps, params, kmer_len_quick, max_set,
-                              k_list, kv_list, n_k, d_stats);
+                              k_list, kv_list, n_k, d_stats, nullptr, nullptr);
 }
 
 int gf_merge_rescue_dev(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t contig_cap, void* d_seq, void* d_seq_len, size_t seq_cap,
@@ -1444,7 +1363,7 @@ int gf_merge_rescue_dev(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t 
     if (!n_gaps) { GF_HIP(ctx, hipMemsetAsync(d_stats, 0, MG_WORDS * 4, ctx->stream)); return GF_OK; }
     MgRescueArgs rs{MG_MODE_RESCUE, (const uint32_t*)d_gap_bridges, (const uint32_t*)d_merge_stats + MG_N0, (const uint32_t*)d_rescue_first, nullptr};
     return launch_merge_round(ctx, d_contigs, d_n_contigs, contig_cap, d_seq, d_seq_len, seq_cap, d_gap_best, n_gaps, params, kmer_len_quick, max_set,
-                              k_list, kv_list, n_k, d_stats, &rs);
+                              k_list, kv_list, n_k, d_stats, &rs, nullptr);
 }
 
 }  // extern "C"

@@ -286,6 +286,80 @@ class GapFill:
                   "gf_overlap_evaluate")
         return out
 
+    def merge_sets_device(self, rec_sets, params=None, kmer_len_quick=10, max_set=128, caps=None):
+        """The contig merger as ONE device call with its graph exported (gf_merge_sets): rec_sets = [[(name, seq)]], one set per gap, as
+        read from contigs.fa (NOT de-duplicated).  One upload, one call, one download for all sets.  Returns per set a dict:
+          "status"  "merged" | "nothing" (fewer than 2 nodes) | "size" | "graph" — the last two: the device left the set alone
+                    (more than 1 024 contigs / more than max_set after the dedup / its graph beyond the round's limits) and only
+                    "nodup" is given (None beyond 1 024 contigs, where no dedup ran); the other keys are None
+          "nodup"   the records MergeContigs.drop_contained keeps (the first dedup)
+          "nodes", "edges", "new"   as MergeContigs.merge_sets(gf, [nodup]): the records that took part (sequences upper-cased),
+                    [(i, j, mode, overlap)], [(NEW_CONTIG_MERGE_n, sequence, path)] — a path that ended early lists the nodes merged
+          "final"   drop_contained([(name, seq) of new] + nodup) (the second dedup)
+        self.last_merge_sets_stats holds the call's statistics.  caps = (edges, new contigs, path bytes, sequence bytes, final flags):
+        the capacities of the output lists (default: sized from the input, and one more call with the reported sizes if they were too
+        small); with caps given, a list that does not fit raises GapFillError (GF_E_NOSPACE) — nothing is returned truncated."""
+        rec_sets = [list(r) for r in rec_sets]
+        flat = [s for r in rec_sets for _, s in r]
+        if any(not s for s in flat):
+            raise ValueError("merge_sets_device: empty contig")
+        blob = "".join(flat).encode()
+        coff = np.zeros(len(flat) + 1, dtype=np.uint64)
+        coff[1:] = np.cumsum([len(c) for c in flat])
+        soff = np.zeros(len(rec_sets) + 1, dtype=np.uint64)
+        soff[1:] = np.cumsum([len(r) for r in rec_sets])
+        pr = np.zeros(1, dtype=B.OVL_PARAMS)
+        p7 = tuple(self.MERGER_PARAMS if params is None else params)
+        pr[0] = p7[:7] + (0.0,)
+        n_c, n_b = len(flat), len(blob)
+        sized = caps is None
+        if sized:
+            caps = (max(4096, 16 * n_c), max(1024, 2 * n_c), max(1 << 16, 32 * n_c), (1 << 20) + 4 * n_b, max(1024, 3 * n_c) + n_c)
+        sets = np.zeros(max(1, len(rec_sets)), dtype=B.MSET)
+        kept = np.zeros(max(1, n_c), dtype=np.uint8)
+        stats = np.zeros(B.MX_WORDS, dtype=np.uint32)
+        while True:
+            mc = B.MergeCaps(*[int(x) for x in caps])
+            edges = np.zeros(max(1, mc.edges), dtype=B.MEDGE)
+            news = np.zeros(max(1, mc.news), dtype=B.MNEW)
+            paths = np.zeros(max(1, mc.path_bytes), dtype=np.uint8)
+            nseq = np.zeros(max(1, mc.seq_bytes), dtype=np.uint8)
+            fin = np.zeros(max(1, mc.finals), dtype=np.uint8)
+            rc = self._L.gf_merge_sets(self._h, blob, B._p(coff), B._p(soff), len(rec_sets), B._p(pr), int(kmer_len_quick), int(max_set), C.byref(mc),
+                                       B._p(sets), B._p(kept), B._p(edges), B._p(news), B._p(paths), B._p(nseq), B._p(fin), B._p(stats))
+            need = (int(stats[B.MX_EDGE_RECORDS]), int(stats[B.MX_NEW_RECORDS]), int(stats[B.MX_PATH_BYTES]),
+                    int(stats[B.MX_SEQ_BYTES]) | (int(stats[B.MX_SEQ_BYTES + 1]) << 32), int(stats[B.MX_FINALS]))
+            if rc == B.GF_E_NOSPACE and sized and not (int(stats[B.MX_FLAGS]) & 32) and any(n > c for n, c in zip(need, caps)):
+                caps, sized = tuple(max(n, c) for n, c in zip(need, caps)), False        # the sizes the call reported: once
+                continue
+            self._chk(rc, "gf_merge_sets")
+            break
+        self.last_merge_sets_stats = {"tried": int(stats[B.MX_TRIED]), "nothing": int(stats[B.MX_NOTHING]), "skipped_size": int(stats[B.MX_SKIPPED_SIZE]),
+                                      "skipped_graph": int(stats[B.MX_SKIPPED_GRAPH]), "pairs": int(stats[B.MX_PAIRS]), "edges": int(stats[B.MX_EDGES]),
+                                      "paths": int(stats[B.MX_PATHS]), "truncated_paths": int(stats[B.MX_TRUNCATED]), "flags": int(stats[B.MX_FLAGS]),
+                                      "round_flags": int(stats[B.MX_ROUND_ERR])}
+        nbytes = nseq.tobytes()
+        out = []
+        for si, recs in enumerate(rec_sets):
+            m = sets[si]
+            c0 = int(soff[si])
+            status = int(m["status"])
+            kf = kept[c0:c0 + len(recs)]
+            d = {"status": B.MSET_NAMES[status], "nodup": None, "nodes": None, "edges": None, "new": None, "final": None}
+            if len(recs) <= 1024:
+                d["nodup"] = [recs[i] for i in np.flatnonzero(kf & 1)]
+            if status in (B.MSET_MERGED, B.MSET_NOTHING):
+                d["nodes"] = [(recs[i][0], recs[i][1].upper()) for i in np.flatnonzero(kf & 2)]
+                eo, no, fo, nn = int(m["edge_off"]), int(m["new_off"]), int(m["final_off"]), int(m["n_new"])
+                d["edges"] = [(int(e["i"]), int(e["j"]), str(int(e["mode"])), int(e["overlap"])) for e in edges[eo:eo + int(m["n_edges"])]]
+                d["new"] = [("NEW_CONTIG_MERGE_%d" % (q + 1), nbytes[int(w["seq_off"]):int(w["seq_off"]) + int(w["length"])].decode(),
+                             tuple(int(v) for v in paths[int(w["path_off"]):int(w["path_off"]) + int(w["n_nodes"])]))
+                            for q, w in enumerate(news[no:no + nn])]
+                both = [(n, s) for n, s, _ in d["new"]] + d["nodup"]
+                d["final"] = [both[i] for i in np.flatnonzero(fin[fo:fo + len(both)])]
+            out.append(d)
+        return out
+
     def merge_round(self, contig_sets, params=None, kmer_len_quick=10, max_set=128, open_gaps=None, k_pairs=None):
         """The contig-merge round of the step (gf_merge_open_gaps_dev) on contig sets given from the host: contig_sets[g] = the contigs
         of gap g; every gap counts as open unless open_gaps (booleans) says otherwise.  Returns (per gap the merged sequences in record

@@ -45,6 +45,11 @@ def parse_configuration(path):
     cfg["flank_anchor"] = str(p.get("flank_anchor", "exact"))
     if cfg["flank_anchor"] not in ("exact", "align"):
         raise SystemExit("parameters.flank_anchor must be 'exact' or 'align', not %r" % (cfg["flank_anchor"],))
+    # extension: the engine of the contig-merge rounds — "host" (default) or "device" (one device call per round with the merger's graph
+    # exported, MergeContigs.merge_contigs); same files either way
+    cfg["contig_merger"] = str(p.get("contig_merger", "host"))
+    if cfg["contig_merger"] not in ("host", "device"):
+        raise SystemExit("parameters.contig_merger must be 'host' or 'device', not %r" % (cfg["contig_merger"],))
     for path_, what in [(cfg["draft"], "draft genome")] + [(a[0], "bam") for a in cfg["alignments"]] + \
                        [(x, "raw reads") for pair in cfg["raw_reads"] for x in pair] + [(cfg["wf"], "working folder")]:
         if not os.path.exists(path_):
@@ -164,7 +169,7 @@ def main_func(command, sf_config):
             os.makedirs(wf + MERGE_FOLDER + s, exist_ok=True)
         ga = assemble_gaps.GapAssembler(sf_fai, sf_gap_pos, cfg["nthreads"], wf + MERGE_FOLDER, cfg["kmers"], gf,
                                         bam_list=[bam for bam, _, _ in cfg["alignments"]], samtools_path=cfg["samtools"],
-                                        flank_anchor=cfg["flank_anchor"])
+                                        flank_anchor=cfg["flank_anchor"], contig_merger=cfg["contig_merger"])
         if first_round is not None:
             assemble_gaps.set_first_round(first_round)
         res = ga.assemble_pipeline()
@@ -174,6 +179,8 @@ def main_func(command, sf_config):
                  res["bridging_reads"], wf + MERGE_FOLDER))
         timings["stages_s"]["assembly_rounds"] = time.perf_counter() - t0
         timings["assembly"] = res
+        from . import MergeContigs
+        timings["contig_merger"] = dict(MergeContigs.DEVICE_COUNTS, engine=cfg["contig_merger"])
     if os.environ.get("GF_TIMINGS"):
         sys.stderr.write("stages: " + ", ".join("%s %.3f s" % kv for kv in timings["stages_s"].items()) +
                          ("; device collect: " + ", ".join("%s %.3f s" % kv for kv in timings["seconds"].items()) if "seconds" in timings else "") + "\n")

@@ -609,6 +609,74 @@ int gf_merge_open_gaps_dev(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size
 int gf_pick_anchored2_from_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
                                int anchor_len, int anchor_len_short, const void* d_first, void* d_gap_best, void* d_n_closed);
 
+/* ---- §8f-3 behind the CLI's merge_contigs: the merge round over contig SETS given as text, with its graph EXPORTED — per set what
+ * MergeContigs.merge_contigs writes into the reference's files (MergeContigs.py:66-99): the de-duplicated set (contigs.fa_no_dup.fa), the
+ * graph's edges (merge_edges.txt), the paths (…merge.info) with their merged strings, and the second dedup over [merged strings in order] +
+ * [survivors in order] (contigs.fa).  Input as gf_quick_check: seq = the contigs' ASCII bases back to back (either case; upper-cased IN
+ * PLACE on the device), contig_off[n_contigs + 1], set_off[n_sets + 1]; no contig may be empty.  The round is gf_merge_open_gaps_dev's
+ * (every set counts as an open gap, its contigs in the order given), the limits are the same: 2 .. 1 024 contigs per set, 2 .. max_set
+ * (<= 128) after the dedup, contigs of 30 .. 8 190 bases are the NODES and the others pass through.
+ * Per set one gf_mset: status (GF_MSET_*), contigs the first dedup kept, its edges [edge_off, + n_edges), its paths [new_off, + n_new),
+ * its final flags [final_off, + n_new + n_kept) and the paths among them that ended early.  A status of GF_MSET_SIZE / GF_MSET_GRAPH means
+ * the set was LEFT ALONE (no edges, paths or final flags; kept flags only where the dedup ran, i.e. up to 1 024 contigs): the caller
+ * handles such a set by other means.
+ *   kept[n_contigs]   bit 0: the first dedup kept the contig (= MergeContigs.drop_contained: exact containment on either strand, longest
+ *                     first, the first of identical copies stays); bit 1: it is a node.  Node n of a set = its n-th kept contig with bit 1.
+ *   edges             {i, j, mode, overlap}: i, j = 2 * node + strand, mode 12 (i then j) or 21; class-2 pairs that are no containment, in
+ *                     the prefilter's (i, j) order = the order of merge_edges.txt
+ *   new               the paths after the reverse-complement twin removal with more than one node, in sorted order (NEW_CONTIG_MERGE_1, _2,
+ *                     ...): n_nodes node bytes at paths[path_off], `length` bases at seq_off.  A path ends early when the running string
+ *                     outgrows 8 190 bases (FormMergedSeqFromPath as restated in MergeContigs.merged_strings): n_nodes is then the number
+ *                     of nodes actually merged, and the path counts in gf_mset.n_truncated / stats[GF_MX_TRUNCATED]
+ *   finals            one flag per record of [the set's paths in order] + [its kept contigs in order]: the second dedup kept it
+ * d_stats: u32[GF_MX_WORDS], see GF_MX_*.  Capacities: a total beyond its capacity sets a bit of stats[GF_MX_FLAGS]; then NOTHING but the
+ * gf_mset records' counts, the kept flags and the statistics is written — no list is ever truncated — and the statistics hold the sizes
+ * needed (GF_MX_EDGE_RECORDS, GF_MX_NEW_RECORDS, GF_MX_PATH_BYTES, GF_MX_SEQ_BYTES, GF_MX_FINALS).
+ * Device variant: d_seq has room for seq_cap bytes, the first n_bytes hold the input; the merged strings are appended behind them
+ * (gf_mnew.seq_off is an offset into d_seq; stats[GF_MX_SEQ_BYTES] = bytes of d_seq in use, as u64).  new_cap is the capacity of d_new AND
+ * the room of the round's own contig list.  Everything is enqueued on the context's stream without a host synchronisation (workspaces
+ * that have to grow synchronise when they are reallocated).
+ * Host variant: one upload, the device call, ONE synchronisation to read the statistics that size the download, one download.
+ * GF_E_NOSPACE when a flag is set (gf_last_error lists the sizes; nothing is returned truncated).  new_seq receives the merged strings,
+ * gf_mnew.seq_off are offsets into it and stats[GF_MX_SEQ_BYTES] its bytes. */
+enum { GF_MSET_MERGED = 0,   /* went through the merger (n_new may be 0) */
+       GF_MSET_NOTHING = 1,  /* nothing to merge: fewer than 2 nodes (all kept contigs are final) */
+       GF_MSET_SIZE = 2,     /* left alone for size: more than 1 024 contigs, or more than max_set after the dedup */
+       GF_MSET_GRAPH = 3 };  /* left alone for the graph's limits: 4 096 edges, 2 048 paths, the job list, 1 024 records in the second dedup */
+enum { GF_MX_TRIED = 0,          /* sets with status MERGED */
+       GF_MX_NOTHING = 1, GF_MX_SKIPPED_SIZE = 2, GF_MX_SKIPPED_GRAPH = 3,   /* ... and with the other three */
+       GF_MX_PAIRS = 4,          /* candidate pairs of the prefilter */
+       GF_MX_EDGES = 5,          /* edges of the MERGED sets */
+       GF_MX_PATHS = 6,          /* new contigs of the MERGED sets = the gf_mnew records their gf_mset point to */
+       GF_MX_TRUNCATED = 7,      /* ... that ended early */
+       GF_MX_FLAGS = 8,          /* capacity flags GF_MX_F_* */
+       GF_MX_PATH_BYTES = 9, GF_MX_FINALS = 10,   /* bytes of d_paths / d_final in use */
+       GF_MX_ROUND_ERR = 11,     /* the round's own flags (gf_merge_open_gaps_dev's word 6, its word 4 << 8) */
+       GF_MX_SEQ_BYTES = 12,     /* u64 in words 12, 13 */
+       GF_MX_NEW_RECORDS = 14, GF_MX_EDGE_RECORDS = 15,   /* records of d_new / d_edges in use */
+       GF_MX_WORDS = 16 };
+enum { GF_MX_F_EDGES = 1, GF_MX_F_NEW = 2, GF_MX_F_PATHS = 4, GF_MX_F_SEQ = 8, GF_MX_F_FINAL = 16,
+       GF_MX_F_ROUND = 32 };     /* the round's pair list or node buffer (sized from the input: not the caller's to raise) */
+typedef struct {
+    uint32_t status, n_kept, n_edges, edge_off, n_new, new_off, final_off, n_truncated;
+} gf_mset;
+typedef struct {
+    uint32_t i, j, mode, overlap;
+} gf_medge;
+typedef struct {
+    uint32_t set, n_nodes, path_off, length;
+    uint64_t seq_off;
+} gf_mnew;
+typedef struct {
+    size_t edges, news, path_bytes, seq_bytes, finals; /* capacities of the host variant's edges / news / paths / new_seq / finals */
+} gf_mcaps;
+int gf_merge_sets_dev(gf_ctx* ctx, void* d_seq, size_t n_bytes, size_t seq_cap, const void* d_contig_off, const void* d_set_off, size_t n_sets,
+                      size_t n_contigs, const gf_ovl_params* params, int kmer_len_quick, int max_set, void* d_sets, void* d_kept, void* d_edges,
+                      size_t edge_cap, void* d_new, size_t new_cap, void* d_paths, size_t path_cap, void* d_final, size_t final_cap, void* d_stats);
+int gf_merge_sets(gf_ctx* ctx, const char* seq, const uint64_t* contig_off, const uint64_t* set_off, size_t n_sets, const gf_ovl_params* params,
+                  int kmer_len_quick, int max_set, const gf_mcaps* caps, gf_mset* sets, uint8_t* kept, gf_medge* edges, gf_mnew* news, uint8_t* paths,
+                  char* new_seq, uint8_t* finals, uint32_t* stats);
+
 /* ---- partial fills of the gaps no pick closed (run_pick_extended_contig, pick_contigs.py:361-539, called at assemble_gaps.py:367-368
  * with score 15; DESIGN.md "Extended fill").  Host twin: gappadder_amd/pick_contigs.py::pick_extended_sequence applied to a gap's
  * contigs in the order of pick_contigs.extension_order.  For every gap with d_gap_best == 0, over its contigs from *d_first on
