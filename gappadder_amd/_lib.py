@@ -179,6 +179,8 @@ def lib():
         "gf_pick_anchored2_from_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, vp, vp, vp]),
         "gf_pick_aligned_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, vp, vp, vp, vp]),
         "gf_pick_aligned_from_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, vp, vp, vp, vp, vp]),
+        "gf_pick_gapped_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, vp, vp, vp, vp]),
+        "gf_pick_gapped_from_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, vp, vp, vp, vp, vp]),
         "gf_bridging_reads": (i32, [vp, C.c_char_p, vp, vp, C.c_char_p, vp, vp, sz, i32, i32, vp]),
         "gf_merge_open_gaps_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, i32, i32, vp, vp, i32, vp]),
         "gf_merge_sets_dev": (i32, [vp, vp, sz, sz, vp, vp, sz, sz, vp, i32, i32, vp, vp, vp, sz, vp, sz, vp, sz, vp, sz, vp]),
@@ -190,6 +192,7 @@ def lib():
         "gf_round2_pools_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, vp, vp, vp, sz, vp, vp, vp, sz, vp]),
         "gf_pick_extended_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_pick_extended_aligned_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
+        "gf_pick_extended_gapped_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_contigs_append_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp]),
         "gf_rescue_work_bytes": (sz, [sz, sz, sz, i32]),
         "gf_rescue_reset_dev": (i32, [vp, vp, sz, sz, sz, i32, vp]),

@@ -279,7 +279,7 @@ def bridging_reads_batch(items, seed_len=30, budget=2):
 class GapAssembler:
     def __init__(self, sf_fai, sf_pos, n_jobs, working_space, kmer_list=None, gf=None, bam_list=None, samtools_path=None, flank_anchor="exact",
                  contig_merger="host"):
-        """flank_anchor: how every ContigsSelection round anchors the flanks on the contigs, "exact" or "align" (pick_contigs.py);
+        """flank_anchor: how every ContigsSelection round anchors the flanks on the contigs, "exact", "align" or "gapped" (pick_contigs.py);
         contig_merger: the engine of every contig-merge round, "host" or "device" (MergeContigs.merge_contigs)."""
         global kmer_len_list, working_folder, _gf
         self.bam_list = list(bam_list or [])

@@ -215,7 +215,7 @@ void zero_regions(gf_ctx* ctx, const ZeroList& z);
 
 // pick.hip: the exact anchors of one length (built once per gf_set_gaps); pick_align.hip: the align-mode hits of the extended fill
 int anchor_table_for(gf_ctx* ctx, int anchor_len, const uint8_t** out);
-int launch_align_ext(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t, const void* d_first,
+int launch_align_ext(gf_ctx* ctx, bool gapped, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t, const void* d_first,
                      const void* d_gap_best, ExtHit* hits, uint32_t* heads, uint32_t* stats);
 
 // merge.hip: MG_MODE_SETS (d_stats: u32[GF_MG_WORDS] of its own)

@@ -2,7 +2,8 @@
 // for `bwa mem -T {score} -a` that aligns through a draft base that differs from the reads near a flank's gap-side end, where the
 // exact anchors of pick.hip lose the gap.  Definition (bwa mem's defaults as constants, written out): the docstring of
 // gappadder_amd/pick_contigs.py, host twin align_hits; the selection after the hits is select_full (pick_contigs.py:97-321), as in
-// pick.hip.  Entry points: gf_pick_aligned_dev / gf_pick_aligned_from_dev (include/gapfill_hip.h).
+// pick.hip.  Entry points: gf_pick_aligned_dev / gf_pick_aligned_from_dev, gf_pick_gapped_dev / gf_pick_gapped_from_dev
+// (include/gapfill_hip.h).
 //
 // One one-wave workgroup per contig.  The four queries of the contig's gap (left, revcomp(left), right, revcomp(right); codes 0-3,
 // 4 = non-ACGT) and a sorted table of their 19-mers are built once per gf_set_gaps.  Seeds: every lane rolls the 19-mers of a
@@ -11,6 +12,16 @@
 // exactly once.  The seeds (<= SEED_MAX per contig) are ranked in LDS by (query, diagonal, query start) — the production order of
 // the definition —, extended one per lane, and lane 0 walks them in that order: the skip rule (a seed inside an alignment already
 // produced on its diagonal), the cap per (query), the per-(side, clip type) best hit of select_full and its seven pairs.
+//
+// The "gapped" mode (gf_pick_gapped_dev, host twin gapped_hits) is the same body with another extension: a banded affine-gap DP
+// (gap of g bases = 6 + g, 31 diagonals either side of the seed's) that aligns THROUGH an indel between flank and contig.  There the
+// wave takes the seeds one after the other in rank order and spreads the BAND over its lanes: lane b holds diagonal i - j = b - 31 and
+// sweeps anti-diagonals t = i + j, so a cell needs (i-1, j) from lane b - 1 and (i, j-1) from lane b + 1 of step t - 1 — two wave
+// shuffles of a packed (H, gap state) word — and (i-1, j-1) from its own step t - 2.  H, E and F stay in registers; the codes of the
+// query and the contig beyond the seed are staged in LDS in the direction of extension.  The maximum and the last-column maximum are
+// kept per lane (a lane meets its cells in ascending i) and reduced over the wave on (score, i, j) keys, so the twin's first-maximum
+// rule holds whatever the sweep order.  The skip rule (a seed inside an alignment kept for its query) and the cap decide whether a seed
+// is extended at all, so they run there, against the query's kept alignments in LDS; the walk reads each seed's outcome.
 #include <algorithm>
 #include <cstring>
 
@@ -22,6 +33,9 @@ constexpr int AL_SEED = 19, AL_MATCH = 1, AL_MISMATCH = -4, AL_NSCORE = -1, AL_Z
 constexpr int AL_FLANK_MAX = 1024, AL_SEED_MAX = 1024, AL_CAP = 64;
 constexpr int AL_TAB_META = -1, AL_TAB_KMERS = -2;      // keys of ctx->anchor_tabs (dropped with the exact anchors by gf_set_gaps)
 constexpr int CT_LEFT = 0, CT_RIGHT = 1, CT_NONE = 2;    // clip types the selection keeps (BOTH is never used, pick_contigs.py:104)
+constexpr int GP_OPEN = 6, GP_EXT = 1, GP_BAND = 31;     // gapped mode: bwa mem -O, -E; 2 * 31 + 1 diagonals = one wave (lane 63 idles)
+constexpr int GP_CTG = AL_FLANK_MAX + GP_BAND + 1;       // contig bases a side can take: the query's and the band's
+constexpr unsigned long long GP_SKIPPED = 1ull << 45, GP_DROPPED = 2ull << 45;   // a seed's outcome word: status above score, M, qb, qe
 
 struct AlignMeta {
     uint32_t kbeg, kn;     // the gap's 19-mer entries: kmer << 12 | query << 10 | query position, ascending
@@ -86,6 +100,56 @@ __device__ uint64_t al_extend(const uint8_t* Q, int n, const char* s, int m, int
     return ((uint64_t)(uint32_t)score << 33) | ((uint64_t)se << 22) | ((uint64_t)qb << 11) | (uint64_t)qe;
 }
 
+// One side of the gapped extension (pick_contigs.py::_gapped_side), by the whole wave: qst[j - 1] / cst[i - 1] = the code of the j-th
+// query / i-th contig base beyond the seed in the direction of extension (LDS), J / I = how many there are (I <= J + GP_BAND), h0 = the
+// score so far.  Returns score << 22 | contig bases taken << 11 | query bases taken (64 bits: a score can be 1 024), the same in every lane.  A value <= 0 is dead and
+// is held as 0; H <= 1 024, so H << 16 | gap state packs in one word.
+__device__ __forceinline__ unsigned long long gp_side(const uint8_t* qst, const uint8_t* cst, int I, int J, int h0, int lane) {
+    uint32_t hf = lane == GP_BAND ? (uint32_t)h0 << 16 : 0u, he = hf;     // H << 16 | F and H << 16 | E of the lane's last cell
+    int best = lane == GP_BAND ? h0 : 0, best_i = 0;
+    int g = (lane == GP_BAND && J == 0) ? h0 : 0, g_i = 0;
+    const int t_end = min(I + J, 2 * min(I, J) + GP_BAND);
+    bool prev_dead = false;
+    for (int t = 1; t <= t_end; ++t) {
+        uint32_t up = __shfl_up(hf, 1), left = __shfl_down(he, 1);       // (i-1, j) from lane b - 1, (i, j-1) from lane b + 1
+        if (lane == 0) up = 0;
+        const int i2 = t + lane - GP_BAND;                                // 2 i: i - j = lane - GP_BAND, i + j = t
+        const bool mine = !(i2 & 1);                                      // (every other step is this lane's)
+        const int i = i2 >> 1, j = t - i;
+        int H = 0, E = 0, F = 0;
+        if (mine && lane < 2 * GP_BAND + 1 && i >= 0 && j >= 0 && i <= I && j <= J) {
+            F = max(max((int)(up >> 16) - (GP_OPEN + GP_EXT), (int)(up & 0xFFFFu) - GP_EXT), 0);
+            E = max(max((int)(left >> 16) - (GP_OPEN + GP_EXT), (int)(left & 0xFFFFu) - GP_EXT), 0);
+            const int diag = (int)(hf >> 16);                             // (i-1, j-1): this lane, two steps ago
+            int M = 0;
+            if (diag > 0 && i >= 1 && j >= 1) M = max(diag + al_score(qst[j - 1], cst[i - 1]), 0);
+            H = max(M, max(E, F));
+            if (H > best) { best = H; best_i = i; }                       // the lane's first maximum: its cells come in ascending i
+            if (j == J && H > 0) { g = H; g_i = i; }                      // (one cell per lane in the last column)
+        }
+        if (mine) {
+            hf = (uint32_t)H << 16 | (uint32_t)F;
+            he = (uint32_t)H << 16 | (uint32_t)E;
+        }
+        const bool dead = !__any(mine && H > 0);
+        if (dead && prev_dead) break;                                     // two dead anti-diagonals: nothing lives on
+        prev_dead = dead;
+    }
+    // the first maximum in (i ascending, j ascending) order = the largest (score, -i, -j) key
+    unsigned long long kb = (unsigned long long)best << 22 | (unsigned long long)(2047 - best_i) << 11 |
+                            (unsigned long long)(2047 - (best_i - (lane - GP_BAND)));
+    uint32_t kg = (uint32_t)g << 11 | (uint32_t)(2047 - g_i);
+    for (int o = 32; o; o >>= 1) {
+        const unsigned long long ob = __shfl_xor(kb, o);
+        const uint32_t og = __shfl_xor(kg, o);
+        kb = ob > kb ? ob : kb;
+        kg = og > kg ? og : kg;
+    }
+    const int bs = (int)(kb >> 22), gs = (int)(kg >> 11);
+    if (gs > 0 && gs > bs - AL_CLIP) return (unsigned long long)gs << 22 | (unsigned long long)(2047u - (kg & 2047u)) << 11 | (unsigned long long)J;
+    return (unsigned long long)bs << 22 | (2047ull - ((kb >> 11) & 2047u)) << 11 | (2047ull - (kb & 2047u));
+}
+
 // the selection of one threshold (pick_contigs.py::select_per_contig): false when no same-strand pair with a span >= 0
 __device__ bool al_select(const AlHit* left, const AlHit* right, uint32_t* lp, uint32_t* rp, uint32_t* lm, uint32_t* rm, uint32_t* rc,
                           int* span) {
@@ -111,11 +175,17 @@ __device__ bool al_select(const AlHit* left, const AlHit* right, uint32_t* lp, u
 // EXT: the hits of the extended fill instead of the pick: per contig of an open gap and side the FIRST hit in align_hits' order (score
 // descending, forward before reverse, pos ascending; production order on full ties) whose clip type is the wanted one — the flank clipped
 // on its far side: LEFT for the left flank forward and rc(right flank), RIGHT for rc(left flank) and the right flank forward
-template <bool EXT>
+// GAPPED: the gapped mode's extension (gp_side) and its skip rule and cap in place of the ungapped ones; everything else is shared
+template <bool EXT, bool GAPPED>
 __device__ __forceinline__ void pick_align_body(const AlignParams& P) {
     __shared__ unsigned long long keys[AL_SEED_MAX];   // seeds as found, then the extension results in rank order
     __shared__ unsigned long long srt[AL_SEED_MAX];    // seeds in (query, diagonal, query start) order
     __shared__ uint32_t cnt;
+    // gapped mode: per seed the first contig base of its alignment; the alignments kept for the current query (query begin | end << 16,
+    // contig begin, contig end) for the skip rule; the staged codes of one side
+    __shared__ uint32_t cbeg[GAPPED ? AL_SEED_MAX : 1];
+    __shared__ uint32_t kept_q[GAPPED ? AL_CAP : 1], kept_cb[GAPPED ? AL_CAP : 1], kept_ce[GAPPED ? AL_CAP : 1];
+    __shared__ uint8_t qst[GAPPED ? AL_FLANK_MAX : 4], cst[GAPPED ? GP_CTG : 4];
     __shared__ AlHit tab[2][2][3];                     // [threshold][side][clip type] (lane 0)
     const uint32_t n_ctg = *P.n_contigs < P.contig_cap ? *P.n_contigs : P.contig_cap;
     const int lane = threadIdx.x;
@@ -174,13 +244,73 @@ __device__ __forceinline__ void pick_align_body(const AlignParams& P) {
             srt[r] = k;
         }
         __syncthreads();
-        // ---- extension, one seed per lane
-        for (uint32_t i = lane; i < n; i += 64) {
-            const unsigned long long k = srt[i];
-            const uint32_t qi = (uint32_t)(k >> 62), q = (uint32_t)k & 2047u;
-            const int d = (int)((k >> 11) & ((1ull << 51) - 1)) - AL_FLANK_MAX;
-            const uint8_t* Q = qb0 + (qi == 0 ? 0 : qi == 1 ? nl : qi == 2 ? 2 * nl : 2 * nl + nr);
-            keys[i] = al_extend(Q, qi < 2 ? nl : nr, s, m, d, (int)q);
+        if constexpr (GAPPED) {
+            // ---- extension, the wave on one seed after the other (everything here is uniform over the wave)
+            uint32_t cur_q = 4, produced = 0;
+            for (uint32_t i = 0; i < n; ++i) {
+                const unsigned long long k = srt[i];
+                const uint32_t qi = (uint32_t)(k >> 62);
+                const int q = (int)((uint32_t)k & 2047u), d = (int)((k >> 11) & ((1ull << 51) - 1)) - AL_FLANK_MAX;
+                const uint8_t* Q = qb0 + (qi == 0 ? 0 : qi == 1 ? nl : qi == 2 ? 2 * nl : 2 * nl + nr);
+                const int nq = qi < 2 ? nl : nr;
+                if (qi != cur_q) { cur_q = qi; produced = 0; }
+                int se = q + AL_SEED;                             // the end of the seed's run of identical ACGT bases
+                for (;;) {
+                    const int x = se + lane;
+                    const bool on = x < nq && x + d < m && Q[x] < 4 && Q[x] == al_code(s[x + d]);
+                    const unsigned long long off = __ballot(!on);
+                    if (off) { se += __ffsll((long long)off) - 1; break; }
+                    se += 64;
+                }
+                const uint32_t n_kept = produced < (uint32_t)AL_CAP ? produced : (uint32_t)AL_CAP;
+                bool inside = false;
+                if ((uint32_t)lane < n_kept) {
+                    const uint32_t kq = kept_q[lane];
+                    inside = (int)(kq & 0xFFFFu) <= q && se <= (int)(kq >> 16) && (int)kept_cb[lane] <= q + d && q + d < (int)kept_ce[lane];
+                }
+                if (__any(inside)) {                              // inside an alignment kept for this query
+                    if (lane == 0) keys[i] = GP_SKIPPED;
+                    continue;
+                }
+                if (++produced > (uint32_t)AL_CAP) {
+                    if (lane == 0) keys[i] = GP_DROPPED;
+                    continue;
+                }
+                // left of the seed: query bases q-1 .. 0 against contig bases q+d-1 .. 0
+                int J = q, I = min(q + d, J + GP_BAND);
+                for (int x = lane; x < J; x += 64) qst[x] = Q[q - 1 - x];
+                for (int x = lane; x < I; x += 64) cst[x] = (uint8_t)al_code(s[q + d - 1 - x]);
+                __syncthreads();
+                const unsigned long long lres = gp_side(qst, cst, I, J, se - q, lane);
+                __syncthreads();
+                const int qb = q - (int)(lres & 2047u), cb = q + d - (int)((lres >> 11) & 2047u);
+                // right of it: query bases se .. against contig bases se+d ..
+                J = nq - se;
+                I = min(m - se - d, J + GP_BAND);
+                for (int x = lane; x < J; x += 64) qst[x] = Q[se + x];
+                for (int x = lane; x < I; x += 64) cst[x] = (uint8_t)al_code(s[se + d + x]);
+                __syncthreads();
+                const unsigned long long rres = gp_side(qst, cst, I, J, (int)(lres >> 22), lane);
+                const int qe = se + (int)(rres & 2047u), ce = se + d + (int)((rres >> 11) & 2047u);
+                if (lane == 0) {
+                    keys[i] = (unsigned long long)(rres >> 22) << 34 | (unsigned long long)(ce - cb) << 22 | (unsigned long long)qb << 11 |
+                              (unsigned long long)qe;
+                    cbeg[i] = (uint32_t)cb;
+                    kept_q[produced - 1] = (uint32_t)qb | (uint32_t)qe << 16;
+                    kept_cb[produced - 1] = (uint32_t)cb;
+                    kept_ce[produced - 1] = (uint32_t)ce;
+                }
+                __syncthreads();
+            }
+        } else {
+            // ---- extension, one seed per lane
+            for (uint32_t i = lane; i < n; i += 64) {
+                const unsigned long long k = srt[i];
+                const uint32_t qi = (uint32_t)(k >> 62), q = (uint32_t)k & 2047u;
+                const int d = (int)((k >> 11) & ((1ull << 51) - 1)) - AL_FLANK_MAX;
+                const uint8_t* Q = qb0 + (qi == 0 ? 0 : qi == 1 ? nl : qi == 2 ? 2 * nl : 2 * nl + nr);
+                keys[i] = al_extend(Q, qi < 2 ? nl : nr, s, m, d, (int)q);
+            }
         }
         __syncthreads();
         if (lane == 0) {
@@ -195,19 +325,31 @@ __device__ __forceinline__ void pick_align_body(const AlignParams& P) {
             for (uint32_t i = 0; i < n; ++i) {
                 const unsigned long long k = srt[i], r = keys[i];
                 const uint32_t qi = (uint32_t)(k >> 62);
-                if ((k >> 11) != last) { last = k >> 11; max_qe = -1; }
-                const int se = (int)((r >> 22) & 2047u), qb = (int)((r >> 11) & 2047u), qe = (int)(r & 2047u);
-                const uint32_t score = (uint32_t)(r >> 33);
-                if (se <= max_qe) continue;                         // inside an alignment already produced on this diagonal
-                max_qe = qe > max_qe ? qe : max_qe;
-                const uint32_t np = qi == 0 ? ++produced[0] : qi == 1 ? ++produced[1] : qi == 2 ? ++produced[2] : ++produced[3];
-                if (np > (uint32_t)AL_CAP) { ++drops; continue; }
+                const int qb = (int)((r >> 11) & 2047u), qe = (int)(r & 2047u);
+                uint32_t score, hm, hpos;                           // the hit: score, contig bases covered, 1-based first contig base
+                if constexpr (GAPPED) {                             // (the skip rule and the cap ran with the extension)
+                    if (r & GP_SKIPPED) continue;
+                    if (r & GP_DROPPED) { ++drops; continue; }
+                    score = (uint32_t)(r >> 34) & 2047u;
+                    hm = (uint32_t)(r >> 22) & 4095u;
+                    hpos = cbeg[i] + 1;
+                } else {
+                    if ((k >> 11) != last) { last = k >> 11; max_qe = -1; }
+                    const int se = (int)((r >> 22) & 2047u);
+                    score = (uint32_t)(r >> 33);
+                    if (se <= max_qe) continue;                     // inside an alignment already produced on this diagonal
+                    max_qe = qe > max_qe ? qe : max_qe;
+                    const uint32_t np = qi == 0 ? ++produced[0] : qi == 1 ? ++produced[1] : qi == 2 ? ++produced[2] : ++produced[3];
+                    if (np > (uint32_t)AL_CAP) { ++drops; continue; }
+                    const int d = (int)((k >> 11) & ((1ull << 51) - 1)) - AL_FLANK_MAX;
+                    hm = (uint32_t)(qe - qb);
+                    hpos = (uint32_t)(d + qb + 1);
+                }
                 const int nq = qi < 2 ? nl : nr;
                 const bool cl = qb > 0, cr = qe < nq;
                 if (cl && cr) continue;                             // BOTH: never selected
                 const int ct = cl ? CT_LEFT : cr ? CT_RIGHT : CT_NONE;
-                const int d = (int)((k >> 11) & ((1ull << 51) - 1)) - AL_FLANK_MAX;
-                const AlHit h{(uint32_t)(qe - qb), score, qi & 1u, (uint32_t)(d + qb + 1)};
+                const AlHit h{hm, score, qi & 1u, hpos};
                 if (EXT) {
                     if (score < P.t_long || ct != ((qi == 0 || qi == 3) ? CT_LEFT : CT_RIGHT)) continue;
                     auto first = [&h](const AlHit& o) {
@@ -268,9 +410,13 @@ __device__ __forceinline__ void pick_align_body(const AlignParams& P) {
     }
 }
 
-__global__ __launch_bounds__(64) void pick_align_kernel(AlignParams P) { pick_align_body<false>(P); }
+__global__ __launch_bounds__(64) void pick_align_kernel(AlignParams P) { pick_align_body<false, false>(P); }
 
-__global__ __launch_bounds__(64) void pick_align_ext_kernel(AlignParams P) { pick_align_body<true>(P); }
+__global__ __launch_bounds__(64) void pick_align_ext_kernel(AlignParams P) { pick_align_body<true, false>(P); }
+
+__global__ __launch_bounds__(64) void pick_gapped_kernel(AlignParams P) { pick_align_body<false, true>(P); }
+
+__global__ __launch_bounds__(64) void pick_gapped_ext_kernel(AlignParams P) { pick_align_body<true, true>(P); }
 
 }  // namespace gf
 
@@ -331,7 +477,7 @@ static int align_tables(gf_ctx* ctx, const AlignMeta** meta, const uint8_t** qby
     return GF_OK;
 }
 
-static int pick_aligned(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t_long,
+static int pick_aligned(gf_ctx* ctx, bool gapped, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t_long,
                         int t_short, const void* d_first, void* d_gap_best, void* d_n_closed, void* d_ctg_pick, void* d_stats) {
     if (!ctx || !d_contigs || !d_n_contigs || !d_seq || !d_gap_best || !d_n_closed || !d_ctg_pick || !d_stats || t_long < 1 ||
         t_long > 255 || contig_cap > 0x7FFFFFFFull || t_short < 0 || (t_short && t_short >= t_long))
@@ -358,27 +504,38 @@ static int pick_aligned(gf_ctx* ctx, const void* d_contigs, const void* d_n_cont
     P.ext_hits = nullptr;
     P.ext_heads = nullptr;
     LaunchTimer tm(ctx, GF_KERNEL_PICK);
-    hipLaunchKernelGGL(pick_align_kernel, dim3(ctx->n_cu * 16), dim3(64), 0, ctx->stream, P);
+    hipLaunchKernelGGL(gapped ? pick_gapped_kernel : pick_align_kernel, dim3(ctx->n_cu * 16), dim3(64), 0, ctx->stream, P);
     GF_HIP(ctx, hipGetLastError());
     return GF_OK;
 }
 
 int gf_pick_aligned_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t_long,
                         int t_short, void* d_gap_best, void* d_n_closed, void* d_ctg_pick, void* d_stats) {
-    return pick_aligned(ctx, d_contigs, d_n_contigs, contig_cap, d_seq, t_long, t_short, nullptr, d_gap_best, d_n_closed, d_ctg_pick, d_stats);
+    return pick_aligned(ctx, false, d_contigs, d_n_contigs, contig_cap, d_seq, t_long, t_short, nullptr, d_gap_best, d_n_closed, d_ctg_pick, d_stats);
 }
 
 int gf_pick_aligned_from_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t_long,
                              int t_short, const void* d_first, void* d_gap_best, void* d_n_closed, void* d_ctg_pick, void* d_stats) {
     if (!d_first) return GF_E_INVAL;
-    return pick_aligned(ctx, d_contigs, d_n_contigs, contig_cap, d_seq, t_long, t_short, d_first, d_gap_best, d_n_closed, d_ctg_pick, d_stats);
+    return pick_aligned(ctx, false, d_contigs, d_n_contigs, contig_cap, d_seq, t_long, t_short, d_first, d_gap_best, d_n_closed, d_ctg_pick, d_stats);
+}
+
+int gf_pick_gapped_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t_long,
+                       int t_short, void* d_gap_best, void* d_n_closed, void* d_ctg_pick, void* d_stats) {
+    return pick_aligned(ctx, true, d_contigs, d_n_contigs, contig_cap, d_seq, t_long, t_short, nullptr, d_gap_best, d_n_closed, d_ctg_pick, d_stats);
+}
+
+int gf_pick_gapped_from_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t_long,
+                            int t_short, const void* d_first, void* d_gap_best, void* d_n_closed, void* d_ctg_pick, void* d_stats) {
+    if (!d_first) return GF_E_INVAL;
+    return pick_aligned(ctx, true, d_contigs, d_n_contigs, contig_cap, d_seq, t_long, t_short, d_first, d_gap_best, d_n_closed, d_ctg_pick, d_stats);
 }
 
 }  // extern "C"
 
 namespace gf {
 
-int launch_align_ext(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t, const void* d_first,
+int launch_align_ext(gf_ctx* ctx, bool gapped, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t, const void* d_first,
                      const void* d_gap_best, ExtHit* hits, uint32_t* heads, uint32_t* stats) {   // (pick_ext.hip; the caller checked the arguments)
     AlignParams P;
     memset(&P, 0, sizeof(P));
@@ -395,7 +552,7 @@ int launch_align_ext(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs
     P.first = (const uint32_t*)d_first;
     P.ext_hits = hits;
     P.ext_heads = heads;
-    hipLaunchKernelGGL(pick_align_ext_kernel, dim3(ctx->n_cu * 16), dim3(64), 0, ctx->stream, P);
+    hipLaunchKernelGGL(gapped ? pick_gapped_ext_kernel : pick_align_ext_kernel, dim3(ctx->n_cu * 16), dim3(64), 0, ctx->stream, P);
     GF_HIP(ctx, hipGetLastError());
     return GF_OK;
 }

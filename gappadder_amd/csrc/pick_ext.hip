@@ -5,7 +5,8 @@
 // "NN".  "First" needs a contig order the device list does not have: the order is (rank of the contig's (k, kv) pair, merged contigs
 // after every pair; length descending; bases ascending; contig index), pick_contigs.extension_order.  Definition and host twin:
 // gappadder_amd/pick_contigs.py::pick_extended_sequence on the contigs in that order.  Entry points: gf_pick_extended_dev (exact
-// anchors) and gf_pick_extended_aligned_dev (the align-mode hits of pick_align.hip), include/gapfill_hip.h.
+// anchors), gf_pick_extended_aligned_dev and gf_pick_extended_gapped_dev (the align- / gapped-mode hits of pick_align.hip),
+// include/gapfill_hip.h.
 //
 // Four launches, no host synchronisation:
 //   hits     one wave per contig of an open gap (exact: here, the leftmost / rightmost anchor positions pick_anchor_kernel reduces,
@@ -232,7 +233,7 @@ using namespace gf;
 
 extern "C" {
 
-static int pick_extended(gf_ctx* ctx, bool align, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int a,
+static int pick_extended(gf_ctx* ctx, bool align, bool gapped, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int a,
                          const int* k_list, const int* kv_list, int n_k, const void* d_first, const void* d_gap_best, void* d_ext, void* d_bases,
                          size_t base_cap, void* d_stats) {
     if (!ctx || !d_contigs || !d_n_contigs || !d_seq || !d_gap_best || !d_ext || !d_stats || (base_cap && !d_bases) ||
@@ -273,7 +274,7 @@ static int pick_extended(gf_ctx* ctx, bool align, const void* d_contigs, const v
     GF_HIP(ctx, hipMemsetAsync(P.heads, 0xFF, ng * 8, ctx->stream));
     LaunchTimer tm(ctx, GF_KERNEL_PICK);
     if (align) {
-        if ((rc = launch_align_ext(ctx, d_contigs, d_n_contigs, contig_cap, d_seq, a, d_first, d_gap_best, P.hits, P.heads,
+        if ((rc = launch_align_ext(ctx, gapped, d_contigs, d_n_contigs, contig_cap, d_seq, a, d_first, d_gap_best, P.hits, P.heads,
                                    P.stats + GF_EXT_ALIGN_DROPPED)))
             return rc;
     } else {
@@ -292,14 +293,21 @@ static int pick_extended(gf_ctx* ctx, bool align, const void* d_contigs, const v
 int gf_pick_extended_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int anchor_len,
                          const int* k_list, const int* kv_list, int n_k, const void* d_first, const void* d_gap_best, void* d_ext,
                          void* d_bases, size_t base_cap, void* d_stats) {
-    return pick_extended(ctx, false, d_contigs, d_n_contigs, contig_cap, d_seq, anchor_len, k_list, kv_list, n_k, d_first, d_gap_best, d_ext,
+    return pick_extended(ctx, false, false, d_contigs, d_n_contigs, contig_cap, d_seq, anchor_len, k_list, kv_list, n_k, d_first, d_gap_best, d_ext,
                          d_bases, base_cap, d_stats);
 }
 
 int gf_pick_extended_aligned_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t,
                                  const int* k_list, const int* kv_list, int n_k, const void* d_first, const void* d_gap_best, void* d_ext,
                                  void* d_bases, size_t base_cap, void* d_stats) {
-    return pick_extended(ctx, true, d_contigs, d_n_contigs, contig_cap, d_seq, t, k_list, kv_list, n_k, d_first, d_gap_best, d_ext, d_bases,
+    return pick_extended(ctx, true, false, d_contigs, d_n_contigs, contig_cap, d_seq, t, k_list, kv_list, n_k, d_first, d_gap_best, d_ext, d_bases,
+                         base_cap, d_stats);
+}
+
+int gf_pick_extended_gapped_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t,
+                                const int* k_list, const int* kv_list, int n_k, const void* d_first, const void* d_gap_best, void* d_ext,
+                                void* d_bases, size_t base_cap, void* d_stats) {
+    return pick_extended(ctx, true, true, d_contigs, d_n_contigs, contig_cap, d_seq, t, k_list, kv_list, n_k, d_first, d_gap_best, d_ext, d_bases,
                          base_cap, d_stats);
 }
 

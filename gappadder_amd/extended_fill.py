@@ -31,9 +31,8 @@ class ExtendedFill:
         if self.d_ext is None:        # a sizing run of one of the rounds: nobody reads its fills
             return
         first = p.round2.first_ptr() if p.round2 is not None else None
-        fn, what = ((p.lib.gf_pick_extended_aligned_dev, "gf_pick_extended_aligned_dev") if p.anchor_mode == "align"
-                    else (p.lib.gf_pick_extended_dev, "gf_pick_extended_dev"))
-        p._chk(fn(p.h, p.d_ctg.data_ptr(), p.ap, p.contig_cap, p.d_seq.data_ptr(), p.anchors[-1], p.k_arr, p.kv_arr, len(p.kk), first,
+        what = P.PICKS[p.anchor_mode][2]
+        p._chk(getattr(p.lib, what)(p.h, p.d_ctg.data_ptr(), p.ap, p.contig_cap, p.d_seq.data_ptr(), p.anchors[-1], p.k_arr, p.kv_arr, len(p.kk), first,
                   p.d_best.data_ptr(), self.d_ext.data_ptr(), self.d_bases.data_ptr(), self.base_cap, self.d_stats.data_ptr()), what)
 
     def fetch(self, r):
@@ -44,7 +43,7 @@ class ExtendedFill:
             raise RuntimeError("extended fill overflow: %d fill bases, buffer of %d (Pipeline(ext_base_cap=...))" % (total, self.base_cap))
         r.extended = {"gaps_extended": int(st[B.EXT_EXTENDED]), "left_only": int(st[B.EXT_LEFT_ONLY]), "right_only": int(st[B.EXT_RIGHT_ONLY]),
                       "both_sides": int(st[B.EXT_BOTH]), "bases": total}
-        if p.anchor_mode == "align":
+        if p.per_contig:
             r.extended["align_dropped"], r.extended["align_seed_overflow"] = int(st[B.EXT_ALIGN_DROPPED]), int(st[B.EXT_ALIGN_SEED_OVERFLOW])
         r.ext = np.frombuffer(self.d_ext[:p.n_gaps * B.EXT_PICK.itemsize].cpu().numpy().tobytes(), dtype=B.EXT_PICK)
         r.ext_bases = self.d_bases[:total].cpu().numpy().tobytes()

@@ -40,11 +40,11 @@ def parse_configuration(path):
     cfg["wf"] = p.get("working_folder", "./GAPPadder_Output/")
     cfg["samtools"] = data.get("software_path", {}).get("samtools", "samtools")
     cfg["kmer_screen"] = int(p.get("kmer_screen", 0))   # extension: flank-k-mer recruitment from the FASTQ files (0 = off)
-    # extension: how the picker anchors the flanks on the contigs — "exact" anchors (default) or "align" (seed-and-extend of the whole
-    # flanks, closer to the reference's bwa mem; pick_contigs.py)
+    # extension: how the picker anchors the flanks on the contigs — "exact" anchors (default), "align" (seed-and-extend of the whole
+    # flanks, closer to the reference's bwa mem) or "gapped" (the same through a draft indel next to the gap); pick_contigs.py
     cfg["flank_anchor"] = str(p.get("flank_anchor", "exact"))
-    if cfg["flank_anchor"] not in ("exact", "align"):
-        raise SystemExit("parameters.flank_anchor must be 'exact' or 'align', not %r" % (cfg["flank_anchor"],))
+    if cfg["flank_anchor"] not in ("exact", "align", "gapped"):
+        raise SystemExit("parameters.flank_anchor must be 'exact', 'align' or 'gapped', not %r" % (cfg["flank_anchor"],))
     # extension: the engine of the contig-merge rounds — "host" (default) or "device" (one device call per round with the merger's graph
     # exported, MergeContigs.merge_contigs); same files either way
     cfg["contig_merger"] = str(p.get("contig_merger", "host"))

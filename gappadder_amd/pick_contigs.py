@@ -30,9 +30,36 @@ hand-derived answers (tests/test_pick_align_host.py), not on bwa's output.  For 
              and counted; a contig with more than SEED_MAX (1024) seeds over both flanks and strands gives no hits and is counted;
   order      within a (contig, side) hits are ordered by score descending, forward before reverse, then pos ascending — so
              select_full's "first on ties" and pick_extended_sequence's "first contig" mean something definite.
-Flanks are limited to FLANK_MAX (1 024) bases.  Indels between flank and contig are out of scope.  The device runs the same rule
-as gf_pick_aligned_dev (csrc/pick_align.hip)."""
+Flanks are limited to FLANK_MAX (1 024) bases.  Indels between flank and contig are out of scope in this mode.  The device runs the
+same rule as gf_pick_aligned_dev (csrc/pick_align.hip).
+
+A third, opt-in stand-in (`mode="gapped"`, `gapped_hits`) aligns THROUGH an indel between flank and contig: a draft base inserted or
+deleted within `score` bases of a flank's gap-side end breaks the exact anchors, and leaves an `align` hit clipped on the gap side.
+Again the definition is this build's own, on bwa mem's defaults (`-O 6 -E 1`), pinned on hand-derived answers
+(tests/test_pick_gapped_host.py).  Queries, seeds, production order (query, diagonal, query start), thresholds, ALIGN_CAP, SEED_MAX,
+FLANK_MAX, the hit order and the clip types are those of `align`; what differs:
+  extension  from each end of the seed run (left end first, then right) a banded affine-gap DP over cells (i, j) = (contig bases, query
+             bases) taken beyond the seed in the direction of extension: H(0, 0) = the score so far (the seed length on the left, the
+             left result on the right); H(i, j) = max(H(i-1, j-1) + s, E, F) with s = match +1, mismatch -4, non-ACGT on either side -1,
+             E(i, j) = max(H(i, j-1) - 7, E(i, j-1) - 1), F(i, j) = max(H(i-1, j) - 7, F(i-1, j) - 1): a gap of g bases costs
+             GAP_OPEN + g * GAP_EXT = 6 + g; only cells with |i - j| <= GAP_BAND (31) exist; a value <= 0 is dead and propagates
+             nothing; there is NO z-drop, so the values do not depend on the order the cells are evaluated in;
+  results    best = the maximum live H, at the first such cell in (i ascending, j ascending) order; g = the maximum live H in the
+             query's last column on that side, first by i; the side runs to the query's end at g's cell when g > 0 and
+             g > best - CLIP_PEN, else it stops at best's cell.  No traceback: the scores and the two end cells are all there is;
+  hit        pos = contig index of the first aligned CONTIG base + 1; M = the number of CONTIG bases the alignment covers (contig
+             end - contig begin).  A stated departure from the reference, whose map_length sums the CIGAR's M columns only
+             (pick_contigs.py:35-62): every consumer (the slices of pick_gap_sequence and pick_extended_sequence, the span of
+             select_per_contig) uses pos + M - 1 as the alignment's last contig base, and with the M-sum an alignment through a
+             deletion would cut the gap sequence at the wrong base.  Ungapped hits are the same under both readings;
+  skip       a seed is skipped when an alignment kept for the same query contains it: the seed run's query interval lies inside the
+             alignment's query interval and the seed's first contig base inside its contig interval (whatever the alignment's score);
+  cap        a seed that is not skipped produces an alignment; the first ALIGN_CAP per (contig, side, strand) are extended and kept
+             (for the hits and for the skip rule), later ones are counted as dropped and neither extended nor kept.
+The device runs the same rule as gf_pick_gapped_dev (the gapped instantiation of csrc/pick_align.hip)."""
 import os
+
+import numpy as np
 
 _COMP = str.maketrans("ACGTacgt", "TGCATGCA")            # gnrt_reverse_complementary, pick_contigs.py:19-33: upper-case output
 _BOTH, _LEFT, _RIGHT, _NONE = 1, 2, 3, 4                 # clip types (pick_contigs.py:9-12)
@@ -228,12 +255,145 @@ def align_hits(contigs, left_flank, right_flank, score, cap=ALIGN_CAP, stats=Non
     return out
 
 
+GAP_OPEN, GAP_EXT, GAP_BAND = 6, 1, 31                   # bwa mem: -O, -E; the band is this build's: 63 diagonals, one wavefront
+_DEAD = -(1 << 20)
+_SUB = np.array([[MATCH if a == b else MISMATCH for b in range(4)] + [N_SCORE] for a in range(4)] + [[N_SCORE] * 5], dtype=np.int64)
+
+
+def _codes(s):
+    return np.array([_CODE.get(x, 4) for x in s], dtype=np.int64)
+
+
+def _gapped_side(qc, cc, h0):
+    """One side of the gapped extension.  qc, cc: the codes of the query / the contig beyond the seed, in the direction of extension;
+    h0: the score so far.  Returns (score, contig bases taken, query bases taken).  Row by row (i = contig bases); in a row the band's
+    cells are indexed by b = j - i + GAP_BAND, so (i-1, j-1) is the previous row's b and (i-1, j) its b + 1; the in-row gap state E is
+    a running maximum: E(i, j) = max over j' < j of max(M, F)(i, j') - GAP_OPEN - (j - j') * GAP_EXT (opening from an E costs more than
+    extending it, and a positive end of such a chain has positive links)."""
+    J, W = len(qc), 2 * GAP_BAND + 1
+    I = min(len(cc), J + GAP_BAND)
+    # column j of the query at index j + GAP_BAND: the substitution scores against each contig code, dead outside 1..J / 0..J
+    prof = np.full((5, J + 3 * GAP_BAND + 2), _DEAD, dtype=np.int64)
+    prof[:, GAP_BAND + 1:GAP_BAND + 1 + J] = _SUB[:, qc] if J else 0
+    col = np.full(J + 3 * GAP_BAND + 2, _DEAD, dtype=np.int64)
+    col[GAP_BAND:GAP_BAND + J + 1] = 0
+    ar = np.arange(W, dtype=np.int64)
+    H, F = np.full(W + 1, _DEAD, dtype=np.int64), np.full(W + 1, _DEAD, dtype=np.int64)
+    H[GAP_BAND] = h0
+    for j in range(1, min(J, GAP_BAND) + 1):                     # row 0: a gap of j query bases
+        if h0 - GAP_OPEN - j * GAP_EXT > 0:
+            H[GAP_BAND + j] = h0 - GAP_OPEN - j * GAP_EXT
+    best, bi, bj = h0, 0, 0
+    g, gi = 0, 0
+    if J <= GAP_BAND and H[GAP_BAND + J] > 0:
+        g = int(H[GAP_BAND + J])
+    for i in range(1, I + 1):
+        Fn = np.maximum(H[1:] - (GAP_OPEN + GAP_EXT), F[1:] - GAP_EXT)
+        Hq = np.maximum(H[:W] + prof[cc[i - 1], i:i + W], Fn)
+        acc = np.maximum.accumulate(Hq + ar * GAP_EXT)
+        Hn = Hq.copy()
+        np.maximum(Hn[1:], acc[:-1] - GAP_OPEN - ar[1:] * GAP_EXT, out=Hn[1:])
+        Hn += col[i:i + W]
+        Hn[Hn <= 0] = _DEAD
+        mx = int(Hn.max())
+        if mx <= 0:                                              # a dead row: no F below it, nothing lives on
+            break
+        if mx > best:
+            best, bi, bj = mx, i, i - GAP_BAND + int(Hn.argmax())
+        b = J - i + GAP_BAND
+        if 0 <= b < W and Hn[b] > g:
+            g, gi = int(Hn[b]), i
+        H[:W], F[:W] = Hn, Fn
+    if g > 0 and g > best - CLIP_PEN:
+        return g, gi, J
+    return best, bi, bj
+
+
+def _gapped_extend(Qc, Cc, d, qs):
+    """One seed -> (query begin, query end, contig begin, contig end, score); Qc, Cc: the codes of the query and the contig."""
+    n, m = len(Qc), len(Cc)
+    se = qs
+    while se < n and se + d < m and Qc[se] == Cc[se + d] and Qc[se] < 4:
+        se += 1
+    score, ci, qj = _gapped_side(Qc[:qs][::-1], Cc[:qs + d][::-1], se - qs)
+    qb, cb = qs - qj, qs + d - ci
+    score, ci, qj = _gapped_side(Qc[se:], Cc[se + d:], score)
+    return qb, se + qj, cb, se + d + ci, score
+
+
+_GAPPED_CACHE = {}       # the rounds ask for one gap's contigs at score 30, then 15: the alignments do not depend on the score
+
+
+def _gapped_alignments(contig, queries, index, cap, stats):
+    """Per query id the alignments kept, in production order: [(query begin, query end, contig begin, contig end, score)]."""
+    key = (contig, queries, cap)
+    if key not in _GAPPED_CACHE:
+        if len(_GAPPED_CACHE) >= 4096:
+            _GAPPED_CACHE.clear()
+        own = {}
+        _GAPPED_CACHE[key] = (_gapped_alignments_of(contig, queries, index, cap, own), own)
+    out, own = _GAPPED_CACHE[key]
+    for k, v in own.items():
+        stats[k] = stats.get(k, 0) + v
+    return out
+
+
+def _gapped_alignments_of(contig, queries, index, cap, stats):
+    seeds = _seeds(queries, contig, index)
+    out = [[], [], [], []]
+    if len(seeds) > SEED_MAX:
+        stats["seed_overflow"] = stats.get("seed_overflow", 0) + 1
+        return out
+    Cc, Qc = _codes(contig), [_codes(q) for q in queries]
+    produced = [0, 0, 0, 0]
+    for qi, d, q in sorted(seeds):
+        Q, se = Qc[qi], q
+        while se < len(Q) and se + d < len(Cc) and Q[se] == Cc[se + d] and Q[se] < 4:
+            se += 1
+        if any(qb <= q and se <= qe and cb <= q + d < ce for qb, qe, cb, ce, _ in out[qi]):
+            continue
+        produced[qi] += 1
+        if produced[qi] > cap:
+            stats["dropped"] = stats.get("dropped", 0) + 1
+            continue
+        out[qi].append(_gapped_extend(Q, Cc, d, q))
+    return out
+
+
+def gapped_hits(contigs, left_flank, right_flank, score, cap=ALIGN_CAP, stats=None):
+    """The `gapped` stand-in for `bwa mem -T {score} -a` (the definition: this module's docstring): align_hits' hit tuples in
+    align_hits' order, from alignments that may run through an indel; the matched bases are the CONTIG bases covered.  stats as for
+    align_hits."""
+    stats = {} if stats is None else stats
+    qs, index = _queries(left_flank, right_flank)
+    out = []
+    for ci, (_, seq) in enumerate(contigs):
+        per_q = _gapped_alignments(seq, qs, index, int(cap), stats)
+        for side, q0 in (("left", 0), ("right", 2)):
+            hits = []
+            for rev in (False, True):
+                n = len(qs[q0 + rev])
+                for qb, qe, cb, ce, sc in per_q[q0 + rev]:
+                    if sc < score:
+                        continue
+                    ct = _BOTH if qb > 0 and qe < n else _LEFT if qb > 0 else _RIGHT if qe < n else _NONE
+                    hits.append((-sc, rev, cb + 1, ct, ce - cb))
+            hits.sort(key=lambda h: h[:3])
+            out += [(side, rev, ci, pos, ct, m) for _, rev, pos, ct, m in hits]
+    return out
+
+
+ANCHOR_MODES = ("exact", "align", "gapped")
+
+
 def stand_in_hits(mode, contigs, left_flank, right_flank, score):
     if mode == "exact":
         return anchor_hits(contigs, left_flank, right_flank, score)
     if mode == "align":
         return align_hits(contigs, left_flank, right_flank, score)
-    raise ValueError("flank anchor mode %r: 'exact' or 'align'" % (mode,))
+    if mode == "gapped":
+        return gapped_hits(contigs, left_flank, right_flank, score)
+    raise ValueError("flank anchor mode %r: 'exact', 'align' or 'gapped'" % (mode,))
 
 
 _PAIRS = ((_NONE, _NONE), (_NONE, _LEFT), (_NONE, _RIGHT), (_LEFT, _NONE), (_LEFT, _RIGHT), (_RIGHT, _NONE), (_RIGHT, _LEFT))
@@ -278,7 +438,8 @@ def select_per_contig(hits):
 
 def pick_gap_sequence(contigs, left_flank, right_flank, anchor_len, mode="exact"):
     """contigs: [(name, seq)].  Returns (name, gap_seq, contig as written to picked_contigs.fa) or None (pick_contigs.py:331-358).
-    mode: the stand-in for bwa's hits, "exact" (anchor_hits) or "align" (align_hits; anchor_len is then the score threshold)."""
+    mode: the stand-in for bwa's hits, "exact" (anchor_hits), "align" (align_hits; anchor_len is then the score threshold) or "gapped"
+    (gapped_hits, likewise)."""
     sel = select_full(stand_in_hits(mode, contigs, left_flank, right_flank, anchor_len))
     if sel is None:
         return None
@@ -296,7 +457,7 @@ def pick_extended_sequence(contigs, left_flank, right_flank, anchor_len, mode="e
     the anchors all match `anchor_len` bases and the reference's tie test is constant (int > str, :444, :457), so the FIRST contig
     with a hit; when both sides pick the same contig only the right side is used, and its slice then keeps the first anchor base
     (:480-486 vs :509-512); reverse-strand slices keep one anchor base as well (:496, :474).  In "align" mode the hits carry real
-    match lengths, but the tie test stays constant, so it is still the first hit in align_hits' order.  Returns (left_name,
+    match lengths, but the tie test stays constant, so it is still the first hit in align_hits' order ("gapped": the same order).  Returns (left_name,
     right_name, sequence or None, picked_contigs text or None)."""
     first = {"left": None, "right": None}
     for side, rev, ci, pos, ct, m in stand_in_hits(mode, contigs, left_flank, right_flank, anchor_len):
@@ -366,9 +527,9 @@ def decode_extended(rec, contig_seq):
 
 class ContigsSelection:
     def __init__(self, working_space, mode="exact"):
-        """mode: how the flanks are anchored on the contigs, "exact" (anchor_hits) or "align" (align_hits)."""
-        if mode not in ("exact", "align"):
-            raise ValueError("flank anchor mode %r: 'exact' or 'align'" % (mode,))
+        """mode: how the flanks are anchored on the contigs, "exact" (anchor_hits), "align" (align_hits) or "gapped" (gapped_hits)."""
+        if mode not in ANCHOR_MODES:
+            raise ValueError("flank anchor mode %r: 'exact', 'align' or 'gapped'" % (mode,))
         self.working_folder, self.mode = working_space, mode
 
     def _pick_one(self, gid, anchor_len):

@@ -21,7 +21,7 @@ What the reference does with files between processes —
       + gf_contigs_append_dev + gf_pick_*_from_dev             = round-1 rows + recruits, assembled and picked again
     gf_rescue_hq_keys_dev + gf_rescue_bridges_dev              rescue round for the gaps still open after the merge pick (rescue_round.py):
       + gf_merge_rescue_dev + gf_pick_*_from_dev               high-quality reads clipped at two contigs join the own contigs, merge, pick at 15
-    gf_pick_extended[_aligned]_dev                             partial fills of the gaps every pick left open (extended_fill.py)
+    gf_pick_extended[_aligned|_gapped]_dev                             partial fills of the gaps every pick left open (extended_fill.py)
 
 `Pipeline` owns the sizing pass (capacities follow what the libraries actually recruit), every buffer of the core step, the stream
 wiring and — in a multi-rank run — the one exchange step; an optional round keeps its buffers, sizing, launches and
@@ -75,6 +75,13 @@ class Results:
     merge = rescue = rescue_first = round2 = round2_first = round2_reads = extended = ext = ext_bases = None
 
 
+# anchor mode -> its pick, its pick over the contigs from an index on, its extended fill; do its picks leave a selection per contig
+# (gf_ctg_pick) and two statistics words?
+PICKS = {"exact": ("gf_pick_anchored2_dev", "gf_pick_anchored2_from_dev", "gf_pick_extended_dev", False),
+         "align": ("gf_pick_aligned_dev", "gf_pick_aligned_from_dev", "gf_pick_extended_aligned_dev", True),
+         "gapped": ("gf_pick_gapped_dev", "gf_pick_gapped_from_dev", "gf_pick_extended_gapped_dev", True)}
+
+
 class Pipeline:
     def __init__(self, gf, n_gaps, read_len, k_pairs, device=None, world=1, rank=0, backend="nccl", force_exchange=False,
                  min_count=2, min_contig=40, anchors=(30, 15), clip_dist=250, anchor_mapq=30, k_screen=None, keep_read_ids=False,
@@ -93,15 +100,16 @@ class Pipeline:
         pass streams THEM; only where 4 * np is at most half a packed read and the column fits (else nothing is built and the pass reads
         the rows).  A column built for another geometry (k, read length, read count) is rebuilt before it is used.
         anchor_mode: how every pick of the step anchors the flanks on the contigs — "exact" anchors (gf_pick_anchored2_dev) or "align",
-        seed-and-extend of the whole flanks (gf_pick_aligned_dev; `anchors` are then the score thresholds); with "align" the Results
-        carry `ctg_pick` (gf_ctg_pick per contig) and `align_dropped` / `align_seed_overflow` (gf_pick_aligned_dev's d_stats).
+        seed-and-extend of the whole flanks (gf_pick_aligned_dev; `anchors` are then the score thresholds), or "gapped", the same with a
+        banded affine-gap extension that aligns through a draft indel next to the gap (gf_pick_gapped_dev); with "align" and "gapped" the
+        Results carry `ctg_pick` (gf_ctg_pick per contig) and `align_dropped` / `align_seed_overflow` (the pick's d_stats).
         second_round (second_round.py), rescue_round (rescue_round.py), extended_fill with ext_base_cap (extended_fill.py): the
         reference's later stages inside the step, each described in its module; in the step they run in this order after the merge
         round's pick."""
         # what the options exclude, before anything touches gf or the library
         single_rank = int(world) == 1 and not force_exchange
         k_round2 = min([int(a) for a, _ in k_pairs if 16 <= int(a) <= 64], default=None)
-        for bad, why in ((anchor_mode not in ("exact", "align"), "anchor_mode %r: 'exact' or 'align'" % (anchor_mode,)),
+        for bad, why in ((anchor_mode not in PICKS, "anchor_mode %r: 'exact', 'align' or 'gapped'" % (anchor_mode,)),
                          (rescue_round and not merge_in_step, "rescue_round needs merge_in_step: the reads are aligned to the merged contigs"),
                          (rescue_round and not single_rank, "rescue_round runs on a single rank"),
                          (rescue_round and second_round, "rescue_round with second_round: the order of the rounds is not settled"),
@@ -113,6 +121,7 @@ class Pipeline:
             if bad:
                 raise ValueError(why)
         self.anchor_mode = anchor_mode
+        self.per_contig = PICKS[anchor_mode][3]      # the mode's picks leave a selection per contig and two statistics words
         # the optional rounds, in the order the step runs them; None: off
         self.round2 = R2.SecondRound(self, k_round2) if second_round else None
         self.rescue = RS.RescueRound(self) if rescue_round else None
@@ -459,7 +468,7 @@ class Pipeline:
         self.d_acnt = torch.zeros(8, dtype=torch.int32, device=dev)
         self.ap = self.d_acnt.data_ptr()
         self.d_mstats = torch.zeros(B.MG_WORDS, dtype=torch.int32, device=dev)      # statistics of the merge round (gf_merge_open_gaps_dev)
-        if self.anchor_mode == "align":        # the align-mode picks' two statistics words (their selection per contig: _alloc_contig_list)
+        if self.per_contig:        # the picks' two statistics words (their selection per contig: _alloc_contig_list)
             self.d_pstats = torch.zeros(2, dtype=torch.int32, device=dev)
         pr = np.zeros(1, dtype=B.OVL_PARAMS)
         pr[0] = tuple(self.gf.MERGER_PARAMS)[:7] + (0.0,)       # ContigsMerger's options as GAPPadder sets them (MergeContigs.py:75)
@@ -485,11 +494,11 @@ class Pipeline:
         return (64 * self.n_gaps + 4096 + rows // 4) * nk, (24576 * self.n_gaps + (1 << 20) + 32 * rows) * nk
 
     def _alloc_contig_list(self, contig_cap, seq_cap):
-        """The step's contig list: records, bases and (align mode) the picks' selection per contig."""
+        """The step's contig list: records, bases and (align and gapped mode) the picks' selection per contig."""
         self.contig_cap, self.seq_cap = int(contig_cap), int(seq_cap)
         self.d_ctg = self._u8(self.contig_cap * 32)
         self.d_seq = self._u8(self.seq_cap)
-        if self.anchor_mode == "align":
+        if self.per_contig:
             self.d_ctg_pick = self._u8(self.contig_cap * B.CTG_PICK.itemsize)
 
     def _size_round(self, name, grow):
@@ -556,7 +565,7 @@ class Pipeline:
         # (zeroed through the library = on its stream; a torch op here would run on torch's stream)
         self._chk(lib.gf_memset_dev(h, self.d_xerr.data_ptr(), 0, 16) or lib.gf_memset_dev(h, self.d_best.data_ptr(), 0, 8 * max(1, n_gaps))
                   or lib.gf_memset_dev(h, self.ap + 16, 0, 16), "gf_memset_dev")
-        if self.anchor_mode == "align":
+        if self.per_contig:
             self._chk(lib.gf_memset_dev(h, self.d_ctg_pick.data_ptr(), 0, self.contig_cap * B.CTG_PICK.itemsize)
                       or lib.gf_memset_dev(h, self.d_pstats.data_ptr(), 0, 8), "gf_memset_dev")
         if not self.need_merge:
@@ -603,17 +612,12 @@ class Pipeline:
     def _pick(self, a_long, a_short, first=None, own=None):
         """One pick in the Pipeline's anchor mode over the contigs from index *first on (a device address; None: all of them) of the step's
         list — read when the call is enqueued: a caller may have changed the capacities — or of `own` = (contigs, their counter, capacity,
-        bases, pick words, closed counter, selection per contig, statistics: the last two in align mode) device addresses."""
-        lib, align = self.lib, self.anchor_mode == "align"
+        bases, pick words, closed counter, selection per contig, statistics: the last two in align and gapped mode) device addresses."""
         if own is None:
             own = (self.d_ctg.data_ptr(), self.ap, self.contig_cap, self.d_seq.data_ptr(), self.d_best.data_ptr(), self.ap + 16) \
-                + ((self.d_ctg_pick.data_ptr(), self.d_pstats.data_ptr()) if align else ())
-        if first is None:
-            fn, what = (lib.gf_pick_aligned_dev, "gf_pick_aligned_dev") if align else (lib.gf_pick_anchored2_dev, "gf_pick_anchored2_dev")
-        else:
-            fn, what = ((lib.gf_pick_aligned_from_dev, "gf_pick_aligned_from_dev") if align
-                        else (lib.gf_pick_anchored2_from_dev, "gf_pick_anchored2_from_dev"))
-        self._chk(fn(self.h, *own[:4], a_long, a_short, *(() if first is None else (first,)), *own[4:]), what)
+                + ((self.d_ctg_pick.data_ptr(), self.d_pstats.data_ptr()) if self.per_contig else ())
+        what = PICKS[self.anchor_mode][0 if first is None else 1]
+        self._chk(getattr(self.lib, what)(self.h, *own[:4], a_long, a_short, *(() if first is None else (first,)), *own[4:]), what)
 
     def step(self, n=1):
         assert self.prepared, "Pipeline.prepare() first"
@@ -673,7 +677,7 @@ class Pipeline:
         r.seq = self.d_seq[:r.n_seq].cpu().numpy().tobytes()
         r.best = self.d_best[:self.n_gaps].cpu().numpy().view(np.uint64)
         r.anchor_mode, r.ctg_pick, r.align_dropped, r.align_seed_overflow = self.anchor_mode, None, 0, 0
-        if self.anchor_mode == "align":
+        if self.per_contig:
             r.ctg_pick = np.frombuffer(self.d_ctg_pick[:r.n_contigs * B.CTG_PICK.itemsize].cpu().numpy().tobytes(), dtype=B.CTG_PICK)
             r.align_dropped, r.align_seed_overflow = (int(x) for x in self.d_pstats.cpu().numpy())
         if self.rescue is not None:
@@ -754,7 +758,7 @@ class Pipeline:
         d_n2 = torch.tensor([len(new), 0, 0, 0], dtype=torch.int32, device=self.dev)
         torch.cuda.synchronize()
         own = (d_c2.data_ptr(), d_n2.data_ptr(), len(new), d_s2.data_ptr(), d_b2.data_ptr(), d_n2.data_ptr() + 8)
-        if self.anchor_mode == "align":
+        if self.per_contig:
             d_p2 = torch.zeros(len(new) * B.CTG_PICK.itemsize, dtype=torch.uint8, device=self.dev)
             d_st2 = torch.zeros(2, dtype=torch.int32, device=self.dev)
             torch.cuda.synchronize()
@@ -763,7 +767,7 @@ class Pipeline:
         self.gf.sync()
         b2 = d_b2[:self.n_gaps].cpu().numpy().view(np.uint64)
         out["closed"] = {int(g): decode_best(b2[g]) for g in np.nonzero(b2)[0]}
-        if self.anchor_mode == "align":       # (the selections of the merged contigs, indexed like "contigs")
+        if self.per_contig:       # (the selections of the merged contigs, indexed like "contigs")
             out["ctg_pick"] = np.frombuffer(d_p2.cpu().numpy().tobytes(), dtype=B.CTG_PICK)
             out["align_dropped"], out["align_seed_overflow"] = (int(x) for x in d_st2.cpu().numpy())
         out["arrays"] = (c2, "".join(s for _, s in new).encode(), b2)       # the second pick's contig table, bases and pick words
@@ -771,7 +775,7 @@ class Pipeline:
 
     def picked_sequences(self, res):
         """The gap sequence of every gap the step closed, cut from its winning contig as ContigsSelection writes it to picked_seqs.fa
-        (pick_contigs.py:341-349): {gap: (contig index, gap sequence, reverse?)}.  "align": from the contig's selection in
+        (pick_contigs.py:341-349): {gap: (contig index, gap sequence, reverse?)}.  "align" and "gapped": from the contig's selection in
         res.ctg_pick; "exact": the host picker (pick_contigs.pick_gap_sequence) on the winning contig alone, at the word's anchor
         length, with the flanks given to gf_set_gaps."""
         from .pick_contigs import pick_gap_sequence, revcomp
@@ -779,7 +783,7 @@ class Pipeline:
         for g in np.nonzero(res.best)[0]:
             a_len, span1, ci, rev = decode_best(res.best[g])
             seq = contig_text(res, ci)
-            if res.anchor_mode == "align":
+            if res.ctg_pick is not None:
                 p = res.ctg_pick[ci]
                 lp, rp, lm, rm = int(p["lp"]), int(p["rp"]), int(p["lm"]), int(p["rm"])
                 assert int(p["threshold"]) == a_len and int(p["reverse"]) == rev, (int(g), p, a_len, rev)

@@ -535,6 +535,19 @@ int gf_pick_aligned_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_cont
 /* gf_pick_aligned_dev over the contigs from *d_first (u32, device) on: the second pick after gf_merge_open_gaps_dev */
 int gf_pick_aligned_from_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t_long,
                              int t_short, const void* d_first, void* d_gap_best, void* d_n_closed, void* d_ctg_pick, void* d_stats);
+/* ---- flank anchoring in "gapped" mode: gf_pick_aligned[_from]_dev with a banded affine-gap extension, so that a flank aligns THROUGH
+ * a draft indel next to the gap.  Queries, seeds, production order, thresholds, the hit order, the selection, every argument, the
+ * d_gap_best words, gf_ctg_pick and the two d_stats words are those of gf_pick_aligned_dev.  What differs (the definition in full:
+ * gappadder_amd/pick_contigs.py's docstring, host twin gapped_hits): from each end of the seed run, left first, a DP over (contig
+ * bases, query bases) beyond the seed with match +1, mismatch -4, non-ACGT -1, a gap of g bases 6 + g, 31 diagonals either side of the
+ * seed's, values <= 0 dead, no z-drop; per side the first maximum in (contig, query) order, and the end rule of the align mode on the
+ * maximum of the query's last column; pos = the first aligned CONTIG base + 1 and M (gf_ctg_pick's lm / rm) = the CONTIG bases covered;
+ * a seed is skipped when an alignment kept for its query contains it (query interval and first contig base); the first 64 alignments
+ * per (contig, side, strand) are extended and kept, later ones counted in d_stats[0] and not extended. */
+int gf_pick_gapped_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t_long,
+                       int t_short, void* d_gap_best, void* d_n_closed, void* d_ctg_pick, void* d_stats);
+int gf_pick_gapped_from_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t_long,
+                            int t_short, const void* d_first, void* d_gap_best, void* d_n_closed, void* d_ctg_pick, void* d_stats);
 
 /* ---- §8f-3, first piece: the all-pairs k-mer prefilter of the reference's ContigsMerger (QuickCheckerContigsMatch,
  * ContigsCompactor.cpp:1982-2095, applied by CompactVer3 :836-853 / threadQuickCheck :1073-1098).  A contig SET (one per gap: its
@@ -716,6 +729,10 @@ int gf_pick_extended_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_con
 int gf_pick_extended_aligned_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t,
                                  const int* k_list, const int* kv_list, int n_k, const void* d_first, const void* d_gap_best, void* d_ext,
                                  void* d_bases, size_t base_cap, void* d_stats);
+/* the same with the gapped mode's hits (gf_pick_gapped_dev at threshold t; host twin pick_extended_sequence(mode="gapped")) */
+int gf_pick_extended_gapped_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t,
+                                const int* k_list, const int* kv_list, int n_k, const void* d_first, const void* d_gap_best, void* d_ext,
+                                void* d_bases, size_t base_cap, void* d_stats);
 
 /* ---- the second assembly round inside the step (assemble_gaps.py:328-368 with collect_both_unmapped_reads.py's recruitment; DESIGN.md
  * "Second round").  Predicate (the CLI's kmer_recruit_unmapped): a both-unmapped pair is recruited for an open gap when one of its reads shares

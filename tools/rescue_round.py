@@ -22,7 +22,7 @@ def main():
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--reads", type=int, default=0, help="read records of the short-insert library (default: the preset's)")
     ap.add_argument("--mp-reads", type=int, default=0, help="read records of the mate-pair library (default: no mate-pair library)")
-    ap.add_argument("--anchor-mode", default="exact", choices=("exact", "align"))
+    ap.add_argument("--anchor-mode", default="exact", choices=("exact", "align", "gapped"))
     ap.add_argument("--modes", default="off,on")
     args = ap.parse_args()
     s = preset_setup(args.config, reads=args.reads, mp_reads=args.mp_reads)
