@@ -35,7 +35,7 @@ assert CONTIG.itemsize == 32 and EXT_PICK.itemsize == 40 and GAP.itemsize == 16 
 GF_OK, GF_E_INVAL, GF_E_NODEV, GF_E_NOMEM, GF_E_NOSPACE, GF_E_STATE, GF_E_UNSUPPORTED, GF_E_FORMAT = 0, -1, -2, -3, -4, -5, -6, -7
 KIND_CLIP, KIND_DISCORDANT, KIND_UNMAP, KIND_LOWMAPQ = 0, 1, 2, 3
 KIND_NAMES = {KIND_CLIP: "clip", KIND_DISCORDANT: "discordant", KIND_UNMAP: "unmap"}
-KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE = range(11)
+KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT = range(12)
 
 # words of the merge round's statistics (gf_merge_open_gaps_dev, u32[32])
 MG_N_PRE, MG_N_SETS, MG_SKIPPED, MG_N_PAIRS, MG_QC_FLAGS, MG_N_JOBS, MG_ERR, MG_N0, MG_N_EDGES, MG_SETS_WITH_JOBS = range(10)
@@ -65,6 +65,13 @@ RS_WORDS = 16
 # words of the extended fill's statistics (gf_pick_extended_dev, u32[12]): fills (left only, right only, both sides), u64 bases, overflow flag
 EXT_EXTENDED, EXT_LEFT_ONLY, EXT_RIGHT_ONLY, EXT_BOTH, EXT_BASES, EXT_OVERFLOW, EXT_ALIGN_DROPPED, EXT_ALIGN_SEED_OVERFLOW = 0, 1, 2, 3, 4, 6, 8, 9
 EXT_WORDS, EXT_MAX_PAIRS = 12, 32
+
+# the read support of the closed gaps (gf_fill_support_dev): the record per gap and the words of its statistics (u32[4]): gaps evaluated,
+# closed gaps whose contig does not carry the word's pick, u64 windows evaluated
+FILL_SUPPORT = np.dtype([("n_windows", "<u4"), ("n_zero", "<u4"), ("n_below", "<u4"), ("min", "<u4"), ("max", "<u4"), ("zero_run", "<u4"),
+                         ("sum", "<u8")])
+assert FILL_SUPPORT.itemsize == 32
+FS_GAPS, FS_MISMATCH, FS_WINDOWS, FS_WORDS = 0, 1, 2, 4
 
 _lib = None
 
@@ -193,6 +200,7 @@ def lib():
         "gf_pick_extended_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_pick_extended_aligned_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_pick_extended_gapped_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
+        "gf_fill_support_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
         "gf_contigs_append_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp]),
         "gf_rescue_work_bytes": (sz, [sz, sz, sz, i32]),
         "gf_rescue_reset_dev": (i32, [vp, vp, sz, sz, sz, i32, vp]),

@@ -20,6 +20,14 @@ _gf = None
 _first_round = None  # `-c All` on resident libraries: {gap id: {(k, kv): [(seq, n_nodes, cov_sum)]}} of the device pipeline (set_first_round)
 
 
+def first_round_order(res):
+    """Contig indices of a device step's Results in the order the gaps' contigs.fa list them: by gap and (k, kv), then the host entry
+    point's order — length descending, then sequence.  A contig's NODE number is its 1-based place among those of its (gap, k, kv)."""
+    ctg, seq = res.contigs, res.seq
+    return sorted(range(len(ctg)), key=lambda i: (int(ctg[i]["gap"]), int(ctg[i]["k"]), int(ctg[i]["kv"]), -int(ctg[i]["length"]),
+                                                   seq[int(ctg[i]["seq_off"]):int(ctg[i]["seq_off"]) + int(ctg[i]["length"])]))
+
+
 def set_first_round(res):
     """The first assembly round already ran on the device, on the pools the Collect stage left in HBM (device_collect.py): the next
     assemble_ids call writes ITS contigs instead of reading the per-gap FASTQ files back and assembling them again.  Later rounds
@@ -28,9 +36,7 @@ def set_first_round(res):
     global _first_round
     per = {}
     ctg, seq = res.contigs, res.seq
-    order = sorted(range(len(ctg)), key=lambda i: (int(ctg[i]["gap"]), int(ctg[i]["k"]), int(ctg[i]["kv"]), -int(ctg[i]["length"]),
-                                                    seq[int(ctg[i]["seq_off"]):int(ctg[i]["seq_off"]) + int(ctg[i]["length"])]))
-    for i in order:          # the host entry point's order: length descending, then sequence
+    for i in first_round_order(res):
         c = ctg[i]
         per.setdefault(res.keys[int(c["gap"])], {}).setdefault((int(c["k"]), int(c["kv"])), []).append(
             (seq[int(c["seq_off"]):int(c["seq_off"]) + int(c["length"])].decode(), int(c["n_nodes"]), int(c["cov_sum"])))

@@ -93,6 +93,42 @@ class ResidentLibrary(DeviceLibrary):
     pass
 
 
+def picked_names(res, kmers):
+    """{gap: the header ContigsSelection gives the gap's sequence in picked_seqs.fa} for the gaps the device step closed: `{gap id}_{k}_{kv}_`
+    + the winning contig's Velvet-style name in the gap's contigs.fa (its NODE number from assemble_gaps.first_round_order, the order
+    set_first_round hands the step's contigs to the file writer in; kv as the configuration spells it)."""
+    from .assemble_gaps import first_round_order, velvet_kv
+    from .pipeline import decode_best
+    spelled = {}
+    for k, kv in kmers:
+        spelled.setdefault((int(k), velvet_kv(int(kv))), int(kv))
+    ctg, out = res.contigs, {}
+    winners = {decode_best(res.best[g])[2]: int(g) for g in np.nonzero(res.best)[0]}
+    last, node = None, 0
+    for i in first_round_order(res):          # one pass over the list: a winner's NODE number is its place in its (gap, k, kv) group
+        c = ctg[i]
+        group = (int(c["gap"]), int(c["k"]), int(c["kv"]))
+        node = node + 1 if group == last else 1
+        last = group
+        if winners.get(i) == group[0]:
+            out[group[0]] = "%s_%d_%d_NODE_%d_length_%d_cov_%.6f" % (res.keys[group[0]], group[1], spelled.get(group[1:], group[2]), node,
+                                                                    int(c["n_nodes"]), int(c["cov_sum"]) / float(int(c["n_nodes"])))
+    return out
+
+
+SUPPORT_FIELDS = ("n_windows", "n_zero", "n_below", "min", "max", "zero_run", "sum")
+
+
+def fill_support_tsv(res, kmers):
+    """fill_support.tsv: a header line, then one row per gap the device step closed — its picked_seqs.fa name and the fields of its
+    gf_fill_support record (Results.support), in gap order."""
+    names = picked_names(res, kmers)
+    rows = ["\t".join(("name",) + SUPPORT_FIELDS) + "\n"]
+    for g in sorted(names):
+        rows.append("\t".join([names[g]] + [str(int(res.support[g][f])) for f in SUPPORT_FIELDS]) + "\n")
+    return "".join(rows)
+
+
 class DeviceCollector:
     def __init__(self, gf, cfg, sf_fai, sf_gap_pos, anchor_mapq=30, clip_dist=250, kmers=None, chunk_bytes=256 << 20, log=None):
         """cfg: main.parse_configuration's dictionary.  kmers: the (k, k_velvet) pairs to assemble right away (`-c All`), or None
@@ -429,7 +465,8 @@ class DeviceCollector:
                 torch.cuda.empty_cache()
         kk = self._usable_pairs(L)
         pipe = Pipeline(gf, len(gaps), L, kk, device=self.dev, anchor_mapq=self.anchor_mapq, clip_dist=self.clip_dist,
-                        k_screen=k_screen or None, keep_read_ids=True, probe_column=False)
+                        k_screen=k_screen or None, keep_read_ids=True, probe_column=False,
+                        read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"))
         # (no probe column on the file path: a file-born library is screened once, and until the packing kernels write the column while
         # they hold the bases, building it is a pass of its own — 38 B read + 4 np written per read — that costs more than pass A saves)
         pipe.assemble_in_step = False
@@ -459,6 +496,9 @@ class DeviceCollector:
             t0 = time.perf_counter()
             self._write_files(pipe, libs, names, gaps, keys, folders, merge_folder)
             self.t["write_files"] = time.perf_counter() - t0
+        if res.support is not None:
+            with open(cfg["wf"] + "fill_support.tsv", "w") as f:
+                f.write(fill_support_tsv(res, cfg["kmers"]))
         return res
 
     def footprint_bytes(self, L):
@@ -673,6 +713,7 @@ class DeviceCollector:
         if not n:
             return {}
         hits = np.frombuffer(lb.d_hits[:n * 8].cpu().numpy().tobytes(), dtype=B.HIT)
+        hits = hits[np.lexsort((hits["gap"], hits["read"]))]      # the screen appends in no fixed order; the lists' line order follows this map
         pair_of = hits["read"].astype(np.int64) >> 1
         pairs, inv = np.unique(pair_of, return_inverse=True)
         b, e = self._offsets(lb, 0, pairs)

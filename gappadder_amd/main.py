@@ -50,6 +50,12 @@ def parse_configuration(path):
     cfg["contig_merger"] = str(p.get("contig_merger", "host"))
     if cfg["contig_merger"] not in ("host", "device"):
         raise SystemExit("parameters.contig_merger must be 'host' or 'device', not %r" % (cfg["contig_merger"],))
+    # extension: read support of the fills the device step closes (read_support.py): {wf}fill_support.tsv, one row per closed gap —
+    # how the gap's own reads back the k-mers of the sequence about to be inserted; fill_support_k: its k (default: the smallest usable k)
+    cfg["fill_support"] = bool(p.get("fill_support", False))
+    cfg["fill_support_k"] = int(p["fill_support_k"]) if p.get("fill_support_k") is not None else None
+    if cfg["fill_support_k"] is not None and not 16 <= cfg["fill_support_k"] <= 64:
+        raise SystemExit("parameters.fill_support_k must be in 16..64, not %r" % (cfg["fill_support_k"],))
     for path_, what in [(cfg["draft"], "draft genome")] + [(a[0], "bam") for a in cfg["alignments"]] + \
                        [(x, "raw reads") for pair in cfg["raw_reads"] for x in pair] + [(cfg["wf"], "working folder")]:
         if not os.path.exists(path_):
@@ -162,6 +168,8 @@ def main_func(command, sf_config):
                     timings.pop(key, None)
         if not done:
             collect_per_scaffold(cfg, gf, sf_fai, sf_gap_pos, folders, anchor_mapq, clip_dist, wf)
+        if cfg["fill_support"] and (first_round is None or first_round.support is None):
+            sys.stderr.write("fill_support: only the first assembly round of the device-resident Collect (-c All) computes it: no fill_support.tsv\n")
         timings["stages_s"]["collect" + ("_and_first_assembly_round" if first_round is not None else "")] = time.perf_counter() - t0
     if command in ("Assembly", "All"):
         t0 = time.perf_counter()

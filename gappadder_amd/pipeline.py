@@ -22,6 +22,7 @@ What the reference does with files between processes —
     gf_rescue_hq_keys_dev + gf_rescue_bridges_dev              rescue round for the gaps still open after the merge pick (rescue_round.py):
       + gf_merge_rescue_dev + gf_pick_*_from_dev               high-quality reads clipped at two contigs join the own contigs, merge, pick at 15
     gf_pick_extended[_aligned|_gapped]_dev                             partial fills of the gaps every pick left open (extended_fill.py)
+    gf_fill_support_dev                                        how the pool of every closed gap backs the k-mers of its fill (read_support.py)
 
 `Pipeline` owns the sizing pass (capacities follow what the libraries actually recruit), every buffer of the core step, the stream
 wiring and — in a multi-rank run — the one exchange step; an optional round keeps its buffers, sizing, launches and
@@ -37,6 +38,7 @@ import torch
 
 from . import _lib as B
 from . import extended_fill as EXT
+from . import read_support as SUP
 from . import rescue_round as RS
 from . import second_round as R2
 from . import sharding as SH
@@ -72,7 +74,7 @@ class DeviceLibrary:
 class Results:
     """What one step left on the device, fetched once (contigs, their bases, the pick words, the pools when asked for).  The fields of
     the merge round and of the optional rounds are None unless the round ran."""
-    merge = rescue = rescue_first = round2 = round2_first = round2_reads = extended = ext = ext_bases = None
+    merge = rescue = rescue_first = round2 = round2_first = round2_reads = extended = ext = ext_bases = support = support_stats = None
 
 
 # anchor mode -> its pick, its pick over the contigs from an index on, its extended fill; do its picks leave a selection per contig
@@ -86,7 +88,7 @@ class Pipeline:
     def __init__(self, gf, n_gaps, read_len, k_pairs, device=None, world=1, rank=0, backend="nccl", force_exchange=False,
                  min_count=2, min_contig=40, anchors=(30, 15), clip_dist=250, anchor_mapq=30, k_screen=None, keep_read_ids=False,
                  key_column=True, probe_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False,
-                 extended_fill=False, ext_base_cap=None, rescue_round=False):
+                 extended_fill=False, ext_base_cap=None, rescue_round=False, read_support=False, support_k=None):
         """gf: a GapFill whose gaps (and flanks, when a library is screened) are set.  k_pairs: [(k, k_velvet)] of
         assemble_gaps.py:87-122.  The screen runs at the SMALLEST k of the list: a read that shares a 51-mer with a flank shares
         its 31-mers too, so this is the superset every assembly k needs (the reference recruits once, then assembles at every k).
@@ -105,7 +107,8 @@ class Pipeline:
         Results carry `ctg_pick` (gf_ctg_pick per contig) and `align_dropped` / `align_seed_overflow` (the pick's d_stats).
         second_round (second_round.py), rescue_round (rescue_round.py), extended_fill with ext_base_cap (extended_fill.py): the
         reference's later stages inside the step, each described in its module; in the step they run in this order after the merge
-        round's pick."""
+        round's pick.  read_support with support_k (read_support.py; default: the smallest k of k_pairs in 16..64): after all of them,
+        a record per closed gap of how its pool backs the k-mers of its fill (Results.support)."""
         # what the options exclude, before anything touches gf or the library
         single_rank = int(world) == 1 and not force_exchange
         k_round2 = min([int(a) for a, _ in k_pairs if 16 <= int(a) <= 64], default=None)
@@ -116,6 +119,10 @@ class Pipeline:
                          (second_round and not single_rank, "second_round runs on a single rank"),
                          (second_round and merge_in_step, "second_round with merge_in_step: the order of the merge and the second round is not settled"),
                          (second_round and k_round2 is None, "second_round needs a k in 16..64 among k_pairs"),
+                         (read_support and not single_rank, "read_support runs on a single rank"),
+                         (read_support and second_round, "read_support with second_round: the second round assembles a pool of its own, "
+                                                         "not the step's, and the support is defined on the step's pool"),
+                         (read_support and support_k is None and k_round2 is None, "read_support needs support_k, or a k in 16..64 among k_pairs"),
                          (extended_fill and not single_rank, "extended_fill runs on a single rank"),
                          (extended_fill and len(k_pairs) > B.EXT_MAX_PAIRS, "extended_fill: at most %d (k, kv) pairs" % B.EXT_MAX_PAIRS)):
             if bad:
@@ -126,6 +133,7 @@ class Pipeline:
         self.round2 = R2.SecondRound(self, k_round2) if second_round else None
         self.rescue = RS.RescueRound(self) if rescue_round else None
         self.ext = EXT.ExtendedFill(self, int(ext_base_cap) if ext_base_cap is not None else None) if extended_fill else None
+        self.support = SUP.ReadSupport(self, k_round2 if support_k is None else support_k) if read_support else None
         self.gf, self.lib, self.h = gf, B.lib(), gf.handle
         self.n_gaps, self.L, self.kk = int(n_gaps), int(read_len), [(int(a), int(b)) for a, b in k_pairs]
         self.rb = self.lib.gf_packed_read_bytes(self.L)
@@ -482,6 +490,8 @@ class Pipeline:
             self.rescue.prepare()
         if self.ext is not None:        # (after the rounds: either may have grown the contig list its buffer is sized by)
             self.ext.prepare()
+        if self.support is not None:
+            self.support.prepare()
         if self.tag_ahead:          # the first step's tagger pass (untimed, like a warm-up step's)
             assert all(lb.second_stream for lb in self.libs), "tag_ahead needs DeviceLibrary(tag_ctx=...)"
             self._on_stream(lambda: [self.tagger(lb) for lb in self.libs])
@@ -608,6 +618,8 @@ class Pipeline:
             self.rescue.enqueue()
         if self.ext is not None:
             self.ext.enqueue()
+        if self.support is not None:      # (neither the rescue's nor the extension's launches change d_best after the rescue's pick)
+            self.support.enqueue(d_nmask)
 
     def _pick(self, a_long, a_short, first=None, own=None):
         """One pick in the Pipeline's anchor mode over the contigs from index *first on (a device address; None: all of them) of the step's
@@ -690,6 +702,8 @@ class Pipeline:
             self.round2.fetch(r)
         if self.ext is not None and self.kk:
             self.ext.fetch(r)
+        if self.support is not None and self.kk:
+            self.support.fetch(r)
         if pools:
             r.pool_off = r.asm_off_t.cpu().numpy().astype(np.int64)
             r.pool_rows = r.asm_pool_t[:r.asm_rows_total * self.rb].cpu().numpy().reshape(-1, self.rb)

@@ -734,6 +734,37 @@ int gf_pick_extended_gapped_dev(gf_ctx* ctx, const void* d_contigs, const void* 
                                 const int* k_list, const int* kv_list, int n_k, const void* d_first, const void* d_gap_best, void* d_ext,
                                 void* d_bases, size_t base_cap, void* d_stats);
 
+/* ---- read support of the closed gaps (csrc/fill_support.hip; definition and host twin: gappadder_amd/read_support.py).
+ * For every gap with d_gap_best != 0 one record that says how the k-mers of the gap's fill are backed by the gap's own pool: the
+ * evaluated windows are the k-windows of the winning contig (as stored) that hold at least one base strictly between the two flank hits
+ * of the pick — the windows over the junction when nothing lies between them —, starts max(0, b0 - k + 1) .. min(length - k,
+ * max(b1, b0) - 1) for the body [b0, b1); a window's support = the read windows of the pool (rows d_pool_off[g] .. d_pool_off[g + 1],
+ * offsets 0 .. read_len - k, both strands, windows over a base of d_nmask_or_null skipped as the assembly's count phase skips them) whose
+ * canonical k-mer is the window's; a window with a byte other than A, C, G, T has support 0.  The hits: with d_ctg_pick_or_null the
+ * winning contig's gf_ctg_pick (the align and gapped modes); without it the exact anchors re-located by gf_pick_anchored_dev's rule at
+ * the anchor length the word carries (anchor_long or anchor_short, the lengths the pick ran at; anchor_short 0: one length) — and a
+ * closed gap whose contig does not carry that pick with the word's (unsaturated) span is counted in d_stats[GF_FS_MISMATCH] and gets
+ * the zero record, as does an open gap.  16 <= k <= 64 (GF_E_UNSUPPORTED otherwise); the contig list is read as every consumer reads
+ * it ([0, min(*d_n_contigs, contig_cap)), winners only).  A fill of any length is evaluated, in chunks that stream the pool again.
+ * d_support: gf_fill_support per gap (every record is written); d_stats: u32[GF_FS_WORDS] (set by the call).  pool_rows: rows of the
+ * pool array.  GF_E_STATE without flanks. */
+typedef struct {
+    uint32_t n_windows;   /* evaluated windows */
+    uint32_t n_zero;      /* ... with support 0 */
+    uint32_t n_below;     /* ... with support < min_count (the zero ones included) */
+    uint32_t min, max;    /* smallest and largest support */
+    uint32_t zero_run;    /* longest run of consecutive windows with support 0 */
+    uint64_t sum;         /* of the supports: mean = sum / n_windows */
+} gf_fill_support;
+#define GF_FS_GAPS 0      /* gaps evaluated */
+#define GF_FS_MISMATCH 1  /* closed gaps whose winning contig does not carry the word's pick */
+#define GF_FS_WINDOWS 2   /* u64: windows evaluated */
+#define GF_FS_WORDS 4
+int gf_fill_support_dev(gf_ctx* ctx, const void* d_pool_packed, const void* d_nmask_or_null, const void* d_pool_off, size_t pool_rows,
+                        int read_len, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
+                        const void* d_gap_best, const void* d_ctg_pick_or_null, int anchor_long, int anchor_short, int k, int min_count,
+                        void* d_support, void* d_stats);
+
 /* ---- the second assembly round inside the step (assemble_gaps.py:328-368 with collect_both_unmapped_reads.py's recruitment; DESIGN.md
  * "Second round").  Predicate (the CLI's kmer_recruit_unmapped): a both-unmapped pair is recruited for an open gap when one of its reads shares
  * a canonical k-mer with one of the gap's round-1 contigs; k-mers touching a non-ACGT contig base or an N-masked read base do not count.
@@ -849,6 +880,7 @@ int gf_memset_dev(gf_ctx* ctx, void* d_ptr, int value, size_t bytes);
 #define GF_KERNEL_INGEST 8  /* FASTQ text -> packed reads */
 #define GF_KERNEL_PICK 9    /* flank anchoring */
 #define GF_KERNEL_MERGE 10  /* contig-merge prefilter */
+#define GF_KERNEL_SUPPORT 11  /* read support of the closed gaps */
 int gf_timing_enable(gf_ctx* ctx, int on);
 int gf_timing_read(gf_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int gf_timing_reset(gf_ctx* ctx);
