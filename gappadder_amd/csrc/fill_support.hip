@@ -3,7 +3,7 @@
 // The reference has no such check: it writes whatever the first anchored contig carries.
 //
 // One workgroup of 256 threads per closed gap, grid-stride over the gaps.  The gap's body [b0, b1) on its winning contig comes from the
-// contig's gf_ctg_pick (align / gapped) or from re-locating the exact anchors by pick.hip's rule; the evaluated windows (every k-window
+// contig's gf_ctg_pick (align / gapped) or from re-locating the exact anchors by pick.hip's rule (fill_body.hpp); the evaluated windows (every k-window
 // with a body base) are taken in chunks of FS_CHUNK, and per chunk:
 //   build    the chunk's contig bytes are staged in LDS; every window's canonical k-mer goes into an exact-key open-addressed table in
 //            LDS (FS_SLOTS = 2 x FS_CHUNK slots: load <= 1/2).  A slot is claimed by a 32-bit CAS on its OWNER word (window + 1); keys
@@ -19,6 +19,7 @@
 // A fill longer than a chunk costs one more pass over the pool per chunk, never a result.  Static LDS: 52.1 KB (k > 32: three workgroups per CU) / 36.1 KB (four).
 #include <cstring>
 
+#include "fill_body.hpp"
 #include "gf_internal.hpp"
 
 namespace gf {
@@ -27,7 +28,6 @@ constexpr uint32_t FS_THREADS = 256, FS_CHUNK = 1024, FS_PER = FS_CHUNK / FS_THR
 constexpr int FS_LOG2 = 11;
 constexpr uint32_t FS_SLOTS = 1u << FS_LOG2, FS_SLOT_MASK = FS_SLOTS - 1;
 constexpr uint32_t FS_ROW_BYTES = 2000, FS_ROW_WORDS = FS_ROW_BYTES / 4 + 8;   // a batch of rows (a row has at most 250 bytes) + misalignment + over-read
-constexpr int FS_ANCHOR_MAX = 32, FS_ANCHOR_ROW = 5 * FS_ANCHOR_MAX;          // the anchor rows of pick.hip (left, right, rc(left), rc(right), flags)
 static_assert(FS_SLOTS == 2 * FS_CHUNK && FS_PER == 4, "fill support geometry");
 
 struct FsParams {
@@ -36,30 +36,15 @@ struct FsParams {
     const uint64_t* pool_off;
     uint64_t pool_rows;
     uint32_t rb, L, nmw, batch_rows;
-    const gf_contig* contigs;
+    FillBodyArgs body;           // the contig list, its bases, the picks
     const uint32_t* n_contigs;
     uint32_t contig_cap;
     const char* seq;
     const unsigned long long* gap_best;
-    const gf_ctg_pick* ctg_pick; // or null: exact anchors
-    const uint8_t* anc_l;        // exact: table of anchor length a_l, and of a_s (or null)
-    const uint8_t* anc_s;
-    uint32_t a_l, a_s;
     uint32_t n_gaps, k, min_count;
     gf_fill_support* out;
     uint32_t* stats;
 };
-
-// the assembly's window rule (assemble.hip window_masked): does the window [p, p + len) touch a masked base of the row?
-__device__ __forceinline__ bool fs_window_masked(const uint32_t* row, uint32_t nmw, uint32_t p, uint32_t len) {
-    const uint32_t w = p >> 5, sh = p & 31;
-    const uint64_t lo = (uint64_t)row[w] | ((uint64_t)(w + 1 < nmw ? row[w + 1] : 0u) << 32);
-    const uint64_t hi = w + 2 < nmw ? row[w + 2] : 0u;
-    const uint64_t a = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
-    return (len >= 64 ? a : a & ((1ull << len) - 1)) != 0;
-}
-
-__device__ __forceinline__ uint32_t fs_code(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
 
 template <bool W>
 __global__ __launch_bounds__(FS_THREADS) void fill_support_kernel(FsParams P) {
@@ -85,56 +70,12 @@ __global__ __launch_bounds__(FS_THREADS) void fill_support_kernel(FsParams P) {
             if (t == 0) P.out[g] = rec;
             continue;
         }
-        // ---- the body [b0, b1) on the winning contig (every value below is the same in all threads)
-        const uint32_t ci = 0x7FFFFFFFu - (uint32_t)((word >> 1) & 0x7FFFFFFFu), rev = (uint32_t)(word & 1u);
-        const uint32_t a = (uint32_t)(word >> 56), span1 = (uint32_t)((word >> 32) & 0xFFFFFFu);
-        bool ok = ci < n;
-        gf_contig c;
-        c.length = 0;
-        c.seq_off = 0;
-        if (ok) {
-            c = P.contigs[ci];
-            ok = c.gap == g && c.length > 0;
-        }
+        // ---- the body [b0, b1) on the winning contig (fill_body.hpp; every value below is the same in all threads)
+        const FillBody fb = fill_body<FS_THREADS>(P.body, n, g, word, s_loc);
+        const bool ok = fb.ok;
+        const gf_contig c = fb.c;
         const char* s = P.seq + c.seq_off;
-        int64_t b0 = 0, b1 = 0;
-        if (ok && P.ctg_pick) {
-            const gf_ctg_pick p = P.ctg_pick[ci];
-            ok = p.threshold != 0 && p.lp >= 1 && p.rp >= 1;
-            b0 = rev ? (int64_t)p.rp - 1 + p.rm : (int64_t)p.lp - 1 + p.lm;
-            b1 = rev ? (int64_t)p.lp - 1 : (int64_t)p.rp - 1;
-            if (b1 < b0) b1 = b0;
-            ok = ok && b1 <= (int64_t)c.length;
-        } else if (ok) {
-            const uint8_t* tab = a == P.a_l ? P.anc_l : (P.anc_s && a == P.a_s) ? P.anc_s : nullptr;
-            const uint8_t* row = tab ? tab + (uint64_t)g * FS_ANCHOR_ROW : nullptr;
-            ok = row && row[0] != 0 && row[FS_ANCHOR_MAX] != 0 && c.length >= a;
-            __syncthreads();                     // (the previous gap's readers of s_loc)
-            if (t == 0) { s_loc[0] = EMPTY32; s_loc[1] = 0; }
-            __syncthreads();
-            if (ok) {
-                // forward: leftmost left anchor, rightmost right anchor; reverse word: leftmost rc(right), rightmost rc(left)
-                const uint8_t* pa = row + (rev ? 3 : 0) * FS_ANCHOR_MAX;
-                const uint8_t* pb = row + (rev ? 2 : 1) * FS_ANCHOR_MAX;
-                for (uint32_t p = t; p + a <= c.length; p += FS_THREADS) {
-                    uint32_t i = 0;
-                    while (i < a && (uint8_t)s[p + i] == pa[i]) ++i;
-                    if (i == a) atomicMin(&s_loc[0], p);
-                    i = 0;
-                    while (i < a && (uint8_t)s[p + i] == pb[i]) ++i;
-                    if (i == a) atomicMax(&s_loc[1], p + 1);
-                }
-            }
-            __syncthreads();
-            const uint32_t first = s_loc[0], last1 = s_loc[1];
-            ok = ok && first != EMPTY32 && last1 != 0 && last1 - 1 >= first + a;
-            if (ok) {
-                b0 = (int64_t)first + a;
-                b1 = (int64_t)last1 - 1;
-                const uint64_t sp1 = (uint64_t)(b1 - b0) + 1;
-                ok = span1 < 0xFFFFFFu ? sp1 == span1 : sp1 >= span1;
-            }
-        }
+        const int64_t b0 = fb.b0, b1 = fb.b1;
         if (!ok) {
             if (t == 0) {
                 P.out[g] = rec;
@@ -176,7 +117,7 @@ __global__ __launch_bounds__(FS_THREADS) void fill_support_kernel(FsParams P) {
                 uint64_t hi = 0, lo = 0;
                 bool good = true;
                 for (uint32_t b = 0; b < k; ++b) {
-                    const uint32_t code = fs_code(s_ctg[i + b]);
+                    const uint32_t code = base_code4(s_ctg[i + b]);
                     good = good && code < 4;
                     if (b < 32) hi |= (uint64_t)(code & 3) << (62 - 2 * b);
                     else lo |= (uint64_t)(code & 3) << (62 - 2 * (b - 32));
@@ -227,7 +168,7 @@ __global__ __launch_bounds__(FS_THREADS) void fill_support_kernel(FsParams P) {
                 const uint32_t total = nb * nwin;
                 for (uint32_t idx = t; idx < total; idx += FS_THREADS) {
                     const uint32_t r = idx / nwin, p = idx - r * nwin;
-                    if (P.nmask && fs_window_masked(P.nmask + (row0 + r) * P.nmw, P.nmw, p, k)) continue;
+                    if (P.nmask && row_window_masked(P.nmask + (row0 + r) * P.nmw, P.nmw, p, k)) continue;
                     const uint32_t bit = (mis + r * P.rb) * 8 + 2 * p;
                     K128 q;
                     if constexpr (W) {
@@ -339,7 +280,7 @@ extern "C" int gf_fill_support_dev(gf_ctx* ctx, const void* d_pool_packed, const
     if (!ctx || !d_pool_off || (pool_rows && !d_pool_packed) || !d_contigs || !d_n_contigs || !d_seq || !d_gap_best || !d_support || !d_stats ||
         read_len < 1 || read_len > 1000 || contig_cap > 0x7FFFFFFFull || min_count < 0)
         return GF_E_INVAL;
-    if (!d_ctg_pick_or_null && (anchor_long < 8 || anchor_long > FS_ANCHOR_MAX || (anchor_short && (anchor_short < 8 || anchor_short >= anchor_long))))
+    if (!d_ctg_pick_or_null && (anchor_long < 8 || anchor_long > FB_ANCHOR_MAX || (anchor_short && (anchor_short < 8 || anchor_short >= anchor_long))))
         return GF_E_INVAL;
     if (k < 16 || k > 64) return GF_E_UNSUPPORTED;
     const size_t ng = ctx->gaps.size();
@@ -351,10 +292,10 @@ extern "C" int gf_fill_support_dev(gf_ctx* ctx, const void* d_pool_packed, const
     memset(&P, 0, sizeof(P));
     int rc;
     if (!d_ctg_pick_or_null) {
-        if ((rc = anchor_table_for(ctx, anchor_long, &P.anc_l))) return rc;
-        if (anchor_short && (rc = anchor_table_for(ctx, anchor_short, &P.anc_s))) return rc;
-        P.a_l = (uint32_t)anchor_long;
-        P.a_s = (uint32_t)anchor_short;
+        if ((rc = anchor_table_for(ctx, anchor_long, &P.body.anc_l))) return rc;
+        if (anchor_short && (rc = anchor_table_for(ctx, anchor_short, &P.body.anc_s))) return rc;
+        P.body.a_l = (uint32_t)anchor_long;
+        P.body.a_s = (uint32_t)anchor_short;
     }
     P.pool = (const uint8_t*)d_pool_packed;
     P.nmask = (const uint32_t*)d_nmask_or_null;
@@ -364,12 +305,12 @@ extern "C" int gf_fill_support_dev(gf_ctx* ctx, const void* d_pool_packed, const
     P.L = (uint32_t)read_len;
     P.nmw = (uint32_t)((read_len + 31) / 32);
     P.batch_rows = FS_ROW_BYTES / P.rb;
-    P.contigs = (const gf_contig*)d_contigs;
+    P.body.contigs = (const gf_contig*)d_contigs;
     P.n_contigs = (const uint32_t*)d_n_contigs;
     P.contig_cap = (uint32_t)contig_cap;
-    P.seq = (const char*)d_seq;
+    P.seq = P.body.seq = (const char*)d_seq;
     P.gap_best = (const unsigned long long*)d_gap_best;
-    P.ctg_pick = (const gf_ctg_pick*)d_ctg_pick_or_null;
+    P.body.ctg_pick = (const gf_ctg_pick*)d_ctg_pick_or_null;
     P.n_gaps = (uint32_t)ng;
     P.k = (uint32_t)k;
     P.min_count = (uint32_t)min_count;

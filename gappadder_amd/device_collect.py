@@ -129,6 +129,22 @@ def fill_support_tsv(res, kmers):
     return "".join(rows)
 
 
+POLISH_FIELDS = ("len", "flags", "n_cols", "n_changed", "n_uncovered", "reads_placed", "reads_ambiguous")
+
+
+def fill_polish_files(pipe, res, kmers):
+    """(polished_seqs.fa, fill_polish.tsv) of a step with the polish round on, in gap order, one record / row per gap the device step
+    closed, named as in picked_seqs.fa: the polished gap sequence (Pipeline.polished_sequences) in lines of 60, and the fields of the
+    gap's gf_fill_polish record (Results.polish) under a header line."""
+    names, seqs = picked_names(res, kmers), pipe.polished_sequences(res)
+    fa, rows = [], ["\t".join(("name",) + POLISH_FIELDS) + "\n"]
+    for g in sorted(names):
+        seq = seqs[g][1]
+        fa.append(">" + names[g] + "\n" + "".join(seq[i:i + 60] + "\n" for i in range(0, len(seq), 60)))
+        rows.append("\t".join([names[g]] + [str(int(res.polish[g][f])) for f in POLISH_FIELDS]) + "\n")
+    return "".join(fa), "".join(rows)
+
+
 class DeviceCollector:
     def __init__(self, gf, cfg, sf_fai, sf_gap_pos, anchor_mapq=30, clip_dist=250, kmers=None, chunk_bytes=256 << 20, log=None):
         """cfg: main.parse_configuration's dictionary.  kmers: the (k, k_velvet) pairs to assemble right away (`-c All`), or None
@@ -464,9 +480,18 @@ class DeviceCollector:
                 libs = None
                 torch.cuda.empty_cache()
         kk = self._usable_pairs(L)
+        polish = {}
+        if cfg.get("fill_polish") and kk:
+            from . import polish as POL
+            polish = {"polish_" + x: cfg["fill_polish_" + x] for x in ("seed", "max_mismatch", "min_overlap", "min_votes") if ("fill_polish_" + x) in cfg}
+            try:
+                POL.check_params(L, **{x[len("polish_"):]: v for x, v in polish.items()})
+            except ValueError as e:
+                raise SystemExit("parameters.fill_polish_*: %s" % e)
+            polish["polish"] = True
         pipe = Pipeline(gf, len(gaps), L, kk, device=self.dev, anchor_mapq=self.anchor_mapq, clip_dist=self.clip_dist,
                         k_screen=k_screen or None, keep_read_ids=True, probe_column=False,
-                        read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"))
+                        read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"), **polish)
         # (no probe column on the file path: a file-born library is screened once, and until the packing kernels write the column while
         # they hold the bases, building it is a pass of its own — 38 B read + 4 np written per read — that costs more than pass A saves)
         pipe.assemble_in_step = False
@@ -499,6 +524,12 @@ class DeviceCollector:
         if res.support is not None:
             with open(cfg["wf"] + "fill_support.tsv", "w") as f:
                 f.write(fill_support_tsv(res, cfg["kmers"]))
+        if res.polish is not None:
+            fa, tsv = fill_polish_files(pipe, res, cfg["kmers"])
+            with open(cfg["wf"] + "polished_seqs.fa", "w") as f:
+                f.write(fa)
+            with open(cfg["wf"] + "fill_polish.tsv", "w") as f:
+                f.write(tsv)
         return res
 
     def footprint_bytes(self, L):

@@ -23,6 +23,7 @@ What the reference does with files between processes —
       + gf_merge_rescue_dev + gf_pick_*_from_dev               high-quality reads clipped at two contigs join the own contigs, merge, pick at 15
     gf_pick_extended[_aligned|_gapped]_dev                             partial fills of the gaps every pick left open (extended_fill.py)
     gf_fill_support_dev                                        how the pool of every closed gap backs the k-mers of its fill (read_support.py)
+    gf_fill_polish_dev                                         the pool of every closed gap piled up on its fill: a vote per column (polish.py)
 
 `Pipeline` owns the sizing pass (capacities follow what the libraries actually recruit), every buffer of the core step, the stream
 wiring and — in a multi-rank run — the one exchange step; an optional round keeps its buffers, sizing, launches and
@@ -38,6 +39,7 @@ import torch
 
 from . import _lib as B
 from . import extended_fill as EXT
+from . import polish as POL
 from . import read_support as SUP
 from . import rescue_round as RS
 from . import second_round as R2
@@ -75,6 +77,7 @@ class Results:
     """What one step left on the device, fetched once (contigs, their bases, the pick words, the pools when asked for).  The fields of
     the merge round and of the optional rounds are None unless the round ran."""
     merge = rescue = rescue_first = round2 = round2_first = round2_reads = extended = ext = ext_bases = support = support_stats = None
+    polish = polish_bases = polish_stats = None
 
 
 # anchor mode -> its pick, its pick over the contigs from an index on, its extended fill; do its picks leave a selection per contig
@@ -88,7 +91,8 @@ class Pipeline:
     def __init__(self, gf, n_gaps, read_len, k_pairs, device=None, world=1, rank=0, backend="nccl", force_exchange=False,
                  min_count=2, min_contig=40, anchors=(30, 15), clip_dist=250, anchor_mapq=30, k_screen=None, keep_read_ids=False,
                  key_column=True, probe_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False,
-                 extended_fill=False, ext_base_cap=None, rescue_round=False, read_support=False, support_k=None):
+                 extended_fill=False, ext_base_cap=None, rescue_round=False, read_support=False, support_k=None, polish=False,
+                 polish_seed=16, polish_max_mismatch=4, polish_min_overlap=48, polish_min_votes=2):
         """gf: a GapFill whose gaps (and flanks, when a library is screened) are set.  k_pairs: [(k, k_velvet)] of
         assemble_gaps.py:87-122.  The screen runs at the SMALLEST k of the list: a read that shares a 51-mer with a flank shares
         its 31-mers too, so this is the superset every assembly k needs (the reference recruits once, then assembles at every k).
@@ -108,7 +112,10 @@ class Pipeline:
         second_round (second_round.py), rescue_round (rescue_round.py), extended_fill with ext_base_cap (extended_fill.py): the
         reference's later stages inside the step, each described in its module; in the step they run in this order after the merge
         round's pick.  read_support with support_k (read_support.py; default: the smallest k of k_pairs in 16..64): after all of them,
-        a record per closed gap of how its pool backs the k-mers of its fill (Results.support)."""
+        a record per closed gap of how its pool backs the k-mers of its fill (Results.support).  polish with polish_seed,
+        polish_max_mismatch, polish_min_overlap, polish_min_votes (polish.py): last of all, the pool of every closed gap is piled up on
+        its winning contig and every column of the fill takes a vote (Results.polish, .polish_bases, .polish_stats;
+        polished_sequences); the step's contigs and picks stay as they are, and read_support keeps describing the UNPOLISHED fill."""
         # what the options exclude, before anything touches gf or the library
         single_rank = int(world) == 1 and not force_exchange
         k_round2 = min([int(a) for a, _ in k_pairs if 16 <= int(a) <= 64], default=None)
@@ -123,6 +130,9 @@ class Pipeline:
                          (read_support and second_round, "read_support with second_round: the second round assembles a pool of its own, "
                                                          "not the step's, and the support is defined on the step's pool"),
                          (read_support and support_k is None and k_round2 is None, "read_support needs support_k, or a k in 16..64 among k_pairs"),
+                         (polish and not single_rank, "polish runs on a single rank"),
+                         (polish and second_round, "polish with second_round: the second round assembles a pool of its own, not the step's, "
+                                                   "and the polish is defined on the step's pool"),
                          (extended_fill and not single_rank, "extended_fill runs on a single rank"),
                          (extended_fill and len(k_pairs) > B.EXT_MAX_PAIRS, "extended_fill: at most %d (k, kv) pairs" % B.EXT_MAX_PAIRS)):
             if bad:
@@ -134,6 +144,7 @@ class Pipeline:
         self.rescue = RS.RescueRound(self) if rescue_round else None
         self.ext = EXT.ExtendedFill(self, int(ext_base_cap) if ext_base_cap is not None else None) if extended_fill else None
         self.support = SUP.ReadSupport(self, k_round2 if support_k is None else support_k) if read_support else None
+        self.polish = POL.FillPolish(self, polish_seed, polish_max_mismatch, polish_min_overlap, polish_min_votes, read_len) if polish else None
         self.gf, self.lib, self.h = gf, B.lib(), gf.handle
         self.n_gaps, self.L, self.kk = int(n_gaps), int(read_len), [(int(a), int(b)) for a, b in k_pairs]
         self.rb = self.lib.gf_packed_read_bytes(self.L)
@@ -492,6 +503,8 @@ class Pipeline:
             self.ext.prepare()
         if self.support is not None:
             self.support.prepare()
+        if self.polish is not None:     # (after the rounds: its base buffer takes what the contig bases take)
+            self.polish.prepare()
         if self.tag_ahead:          # the first step's tagger pass (untimed, like a warm-up step's)
             assert all(lb.second_stream for lb in self.libs), "tag_ahead needs DeviceLibrary(tag_ctx=...)"
             self._on_stream(lambda: [self.tagger(lb) for lb in self.libs])
@@ -620,6 +633,8 @@ class Pipeline:
             self.ext.enqueue()
         if self.support is not None:      # (neither the rescue's nor the extension's launches change d_best after the rescue's pick)
             self.support.enqueue(d_nmask)
+        if self.polish is not None:       # (reads the step's contigs and picks, writes buffers of its own)
+            self.polish.enqueue(d_nmask)
 
     def _pick(self, a_long, a_short, first=None, own=None):
         """One pick in the Pipeline's anchor mode over the contigs from index *first on (a device address; None: all of them) of the step's
@@ -704,6 +719,8 @@ class Pipeline:
             self.ext.fetch(r)
         if self.support is not None and self.kk:
             self.support.fetch(r)
+        if self.polish is not None and self.kk:
+            self.polish.fetch(r)
         if pools:
             r.pool_off = r.asm_off_t.cpu().numpy().astype(np.int64)
             r.pool_rows = r.asm_pool_t[:r.asm_rows_total * self.rb].cpu().numpy().reshape(-1, self.rb)
@@ -787,30 +804,53 @@ class Pipeline:
         out["arrays"] = (c2, "".join(s for _, s in new).encode(), b2)       # the second pick's contig table, bases and pick words
         return out
 
+    def _pick_cut(self, res, g):
+        """(contig index, first, end, reverse-complement the cut?, the word's strand) of the gap sequence of closed gap g on its winning
+        contig as stored: contig[first:end], reverse-complemented for a reverse selection, is what ContigsSelection writes (pick_contigs.py:341-349).  "align" and "gapped": from
+        the contig's selection in res.ctg_pick; "exact": the host picker's selection (pick_contigs.select_full over the exact anchors' hits)
+        on the winning contig alone, at the word's anchor length, with the flanks given to gf_set_gaps."""
+        from .pick_contigs import select_full, stand_in_hits
+        a_len, span1, ci, rev = decode_best(res.best[g])
+        if res.ctg_pick is not None:
+            p = res.ctg_pick[ci]
+            lp, rp, lm, rm = int(p["lp"]), int(p["rp"]), int(p["lm"]), int(p["rm"])
+            assert int(p["threshold"]) == a_len and int(p["reverse"]) == rev, (int(g), p, a_len, rev)
+        else:
+            if self.gf.flanks is None:
+                raise ValueError("picked_sequences in exact mode needs the flanks given to gf_set_gaps")
+            l, r = self.gf.flanks[g]
+            sel = select_full(stand_in_hits("exact", [("c", contig_text(res, ci))], l, r, a_len))
+            if sel is None:
+                raise RuntimeError("gap %d: the host picker does not confirm the device's pick" % g)
+            _, lp, rp, lm, rm, cut_rev = sel
+            return (int(ci), rp + rm - 1, lp, True, bool(rev)) if cut_rev else (int(ci), lp + lm - 1, rp, False, bool(rev))
+        return (int(ci), rp + rm - 1, lp, True, True) if rev else (int(ci), lp + lm - 1, rp, False, False)
+
     def picked_sequences(self, res):
         """The gap sequence of every gap the step closed, cut from its winning contig as ContigsSelection writes it to picked_seqs.fa
-        (pick_contigs.py:341-349): {gap: (contig index, gap sequence, reverse?)}.  "align" and "gapped": from the contig's selection in
-        res.ctg_pick; "exact": the host picker (pick_contigs.pick_gap_sequence) on the winning contig alone, at the word's anchor
-        length, with the flanks given to gf_set_gaps."""
-        from .pick_contigs import pick_gap_sequence, revcomp
+        (_pick_cut): {gap: (contig index, gap sequence, reverse?)}."""
+        from .pick_contigs import revcomp
         out = {}
         for g in np.nonzero(res.best)[0]:
-            a_len, span1, ci, rev = decode_best(res.best[g])
-            seq = contig_text(res, ci)
-            if res.ctg_pick is not None:
-                p = res.ctg_pick[ci]
-                lp, rp, lm, rm = int(p["lp"]), int(p["rp"]), int(p["lm"]), int(p["rm"])
-                assert int(p["threshold"]) == a_len and int(p["reverse"]) == rev, (int(g), p, a_len, rev)
-                body = revcomp(seq[rp + rm - 1:lp]) if rev else seq[lp + lm - 1:rp]
-            else:
-                if self.gf.flanks is None:
-                    raise ValueError("picked_sequences in exact mode needs the flanks given to gf_set_gaps")
-                l, r = self.gf.flanks[g]
-                picked = pick_gap_sequence([("c", seq)], l, r, a_len)
-                if picked is None:
-                    raise RuntimeError("gap %d: the host picker does not confirm the device's pick" % g)
-                body = picked[1]
-            out[int(g)] = (int(ci), body, bool(rev))
+            ci, first, end, flip, rev = self._pick_cut(res, g)
+            body = contig_text(res, ci)[first:end]
+            out[int(g)] = (ci, revcomp(body) if flip else body, rev)
+        return out
+
+    def polished_sequences(self, res):
+        """picked_sequences after the polish round: {gap: (contig index, polished gap sequence, reverse?)} — the same cut, taken at the
+        coordinates the UNPOLISHED contig gives (_pick_cut) and applied to the polished contig, which has the same length; the cut is
+        not searched again on the polished text."""
+        from .pick_contigs import revcomp
+        if res.polish is None:
+            raise ValueError("polished_sequences needs the Results of a Pipeline(polish=True) step")
+        out = {}
+        for g in np.nonzero(res.best)[0]:
+            ci, first, end, flip, rev = self._pick_cut(res, g)
+            text = POL.polished_text(res, g)
+            if len(text) != int(res.contigs[ci]["length"]):
+                raise RuntimeError("gap %d: the polished contig has %d bases, the contig %d" % (g, len(text), int(res.contigs[ci]["length"])))
+            out[int(g)] = (ci, revcomp(text[first:end]) if flip else text[first:end], rev)
         return out
 
     def fixed_ms(self, steps):

@@ -765,6 +765,52 @@ int gf_fill_support_dev(gf_ctx* ctx, const void* d_pool_packed, const void* d_nm
                         const void* d_gap_best, const void* d_ctg_pick_or_null, int anchor_long, int anchor_short, int k, int min_count,
                         void* d_support, void* d_stats);
 
+/* ---- consensus polish of the closed gaps (csrc/fill_polish.hip; definition and host twin: gappadder_amd/polish.py).
+ * For every gap with d_gap_best != 0: the rows of the gap's pool (d_pool_off[g] .. d_pool_off[g + 1], bases of d_nmask_or_null masked), each
+ * as stored and reverse-complemented, are placed without gaps on the winning contig c (as stored, n bases) — a diagonal d puts read
+ * base i on c[d + i]; it is accepted with an overlap of at least min_overlap bases, at most max_mismatch unmasked read bases that differ
+ * from the contig, and one of the read's seed windows [j * seed, (j + 1) * seed), j < read_len / seed, wholly inside the overlap, free
+ * of masked bases and equal to the contig.  A row whose accepted (strand, diagonal) pairs have ONE best (fewest mismatches, then longest
+ * overlap) is placed there and votes its unmasked bases on the columns of the body [b0, b1) — located exactly as gf_fill_support_dev
+ * locates it, with the same arguments and the same GF_PL_MISMATCH rule —; a row with several best pairs is ambiguous and does not vote.
+ * A body column becomes the base with the most votes (the smaller code on a tie) when that base has at least min_votes votes and
+ * strictly more than the column's own base; nothing outside the body changes.  The polished contig (stored orientation) goes to
+ * d_bases at an offset taken from the u64 counter d_stats[GF_PL_BASES] (any order), and the gap's record says where.  A contig of more
+ * than GF_PL_MAX_CONTIG bases, or with a byte other than A, C, G, T, is copied unchanged and flagged (n_cols set, the other counts 0).  An
+ * open gap and a mismatch get the zero record.  A contig that does not fit below base_cap sets GF_PL_F_OVERFLOW (off = len = 0) and
+ * counts in d_stats[GF_PL_OVERFLOW].  seed 12..32, max_mismatch 0..15, seed <= min_overlap <= read_len, min_votes >= 1 and
+ * read_len / seed > max_mismatch (then every placement inside the contig within the budget has a clean seed): GF_E_UNSUPPORTED otherwise.
+ * d_polish: gf_fill_polish per gap (every record is written); d_stats: u32[GF_PL_WORDS] (set by the call).  GF_E_STATE without flanks. */
+typedef struct {
+    uint64_t off;              /* of the polished contig in d_bases */
+    uint32_t len;              /* its bases = the contig's */
+    uint32_t flags;            /* GF_PL_F_* */
+    uint32_t n_cols;           /* body columns */
+    uint32_t n_changed;        /* ... that the vote changed */
+    uint32_t n_uncovered;      /* ... without any vote */
+    uint32_t reads_placed;     /* rows placed (anywhere on the contig) */
+    uint32_t reads_ambiguous;  /* rows with more than one best placement */
+    uint32_t reserved;
+} gf_fill_polish;
+#define GF_PL_F_LONG 1         /* skipped: more than GF_PL_MAX_CONTIG bases */
+#define GF_PL_F_NON_ACGT 2     /* skipped: a byte other than A, C, G, T */
+#define GF_PL_F_OVERFLOW 4     /* d_bases is full: nothing was written */
+#define GF_PL_MAX_CONTIG 8192
+#define GF_PL_GAPS 0           /* gaps polished (not skipped) */
+#define GF_PL_MISMATCH 1       /* closed gaps whose winning contig does not carry the word's pick */
+#define GF_PL_SKIPPED_LONG 2
+#define GF_PL_SKIPPED_NON_ACGT 3
+#define GF_PL_CHANGED 4        /* u64: columns changed */
+#define GF_PL_PLACED 6         /* u64: rows placed */
+#define GF_PL_AMBIGUOUS 8      /* u64: rows ambiguous */
+#define GF_PL_BASES 10         /* u64: bases handed out in d_bases (beyond base_cap: overflow) */
+#define GF_PL_OVERFLOW 12      /* contigs that did not fit */
+#define GF_PL_WORDS 16
+int gf_fill_polish_dev(gf_ctx* ctx, const void* d_pool_packed, const void* d_nmask_or_null, const void* d_pool_off, size_t pool_rows,
+                       int read_len, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
+                       const void* d_gap_best, const void* d_ctg_pick_or_null, int anchor_long, int anchor_short, int seed, int max_mismatch,
+                       int min_overlap, int min_votes, void* d_polish, void* d_bases, size_t base_cap, void* d_stats);
+
 /* ---- the second assembly round inside the step (assemble_gaps.py:328-368 with collect_both_unmapped_reads.py's recruitment; DESIGN.md
  * "Second round").  Predicate (the CLI's kmer_recruit_unmapped): a both-unmapped pair is recruited for an open gap when one of its reads shares
  * a canonical k-mer with one of the gap's round-1 contigs; k-mers touching a non-ACGT contig base or an N-masked read base do not count.
@@ -881,6 +927,7 @@ int gf_memset_dev(gf_ctx* ctx, void* d_ptr, int value, size_t bytes);
 #define GF_KERNEL_PICK 9    /* flank anchoring */
 #define GF_KERNEL_MERGE 10  /* contig-merge prefilter */
 #define GF_KERNEL_SUPPORT 11  /* read support of the closed gaps */
+#define GF_KERNEL_POLISH 12  /* consensus polish of the closed gaps */
 int gf_timing_enable(gf_ctx* ctx, int on);
 int gf_timing_read(gf_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int gf_timing_reset(gf_ctx* ctx);
