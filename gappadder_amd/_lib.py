@@ -35,7 +35,7 @@ assert CONTIG.itemsize == 32 and EXT_PICK.itemsize == 40 and GAP.itemsize == 16 
 GF_OK, GF_E_INVAL, GF_E_NODEV, GF_E_NOMEM, GF_E_NOSPACE, GF_E_STATE, GF_E_UNSUPPORTED, GF_E_FORMAT = 0, -1, -2, -3, -4, -5, -6, -7
 KIND_CLIP, KIND_DISCORDANT, KIND_UNMAP, KIND_LOWMAPQ = 0, 1, 2, 3
 KIND_NAMES = {KIND_CLIP: "clip", KIND_DISCORDANT: "discordant", KIND_UNMAP: "unmap"}
-KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT, KERNEL_POLISH = range(13)
+KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT, KERNEL_POLISH, KERNEL_PAIRS = range(14)
 
 # words of the merge round's statistics (gf_merge_open_gaps_dev, u32[32])
 MG_N_PRE, MG_N_SETS, MG_SKIPPED, MG_N_PAIRS, MG_QC_FLAGS, MG_N_JOBS, MG_ERR, MG_N0, MG_N_EDGES, MG_SETS_WITH_JOBS = range(10)
@@ -82,6 +82,16 @@ assert FILL_POLISH.itemsize == 40
 PL_F_LONG, PL_F_NON_ACGT, PL_F_OVERFLOW = 1, 2, 4
 PL_MAX_CONTIG = 8192
 PL_GAPS, PL_MISMATCH, PL_SKIPPED_LONG, PL_SKIPPED_NON_ACGT, PL_CHANGED, PL_PLACED, PL_AMBIGUOUS, PL_BASES, PL_OVERFLOW, PL_WORDS = 0, 1, 2, 3, 4, 6, 8, 10, 12, 16
+
+# the pair-span check of the closed gaps (gf_fill_pairs_dev): the record per (library, gap), its flags and the words of its statistics
+# (u32[16]): gaps examined, closed gaps whose contig does not carry the word's pick, gaps skipped for a contig too long / with a byte
+# that is no base, examined gaps with a body column no in-range pair covers, then u64 each: complete, placed, proper, in-range, spanning pairs
+FILL_PAIRS = np.dtype([("flags", "<u4"), ("rows", "<u4"), ("pairs_complete", "<u4"), ("pairs_placed", "<u4"), ("n_proper", "<u4"),
+                       ("n_misoriented", "<u4"), ("n_in_range", "<u4"), ("n_short", "<u4"), ("n_long", "<u4"), ("n_span", "<u4"),
+                       ("span_insert_sum", "<i8"), ("n_cols", "<u4"), ("min_cover", "<u4"), ("min_col", "<u4"), ("n_unspanned", "<u4")])
+assert FILL_PAIRS.itemsize == 64
+PS_F_LONG, PS_F_NON_ACGT = 1, 2
+PS_GAPS, PS_MISMATCH, PS_SKIPPED_LONG, PS_SKIPPED_NON_ACGT, PS_UNSPANNED, PS_COMPLETE, PS_PLACED, PS_PROPER, PS_IN_RANGE, PS_SPAN, PS_WORDS = 0, 1, 2, 3, 4, 6, 8, 10, 12, 14, 16
 
 _lib = None
 
@@ -212,6 +222,7 @@ def lib():
         "gf_pick_extended_gapped_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_fill_support_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
         "gf_fill_polish_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
+        "gf_fill_pairs_dev": (i32, [vp, vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
         "gf_contigs_append_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp]),
         "gf_rescue_work_bytes": (sz, [sz, sz, sz, i32]),
         "gf_rescue_reset_dev": (i32, [vp, vp, sz, sz, sz, i32, vp]),

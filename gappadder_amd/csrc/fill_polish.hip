@@ -4,18 +4,8 @@
 //
 // One workgroup of 256 threads per closed gap, grid-stride over the gaps.  The body [b0, b1) comes from fill_body.hpp, as in
 // fill_support.hip.  Per gap:
-//   stage    the contig, 2 bits a base, twice in LDS: as stored and reverse-complemented, each between PL_LEAD bases of padding, so
-//            that a read that overhangs either end is compared without a branch (the overlap mask removes the padding).  A read as
-//            stored on the reverse-complemented contig at diagonal D is the reverse-complemented read on the contig at n - D - L: no
-//            read is ever reverse-complemented
-//   index    an open-addressed multimap in LDS from the contig's s-mers to their positions: PL_SLOTS 16-bit slots (position + 1,
-//            0 = free; load <= 1/2), claimed by a 32-bit CAS on the word that holds the slot; a key is compared through its position
-//            (the contig's own bases), so there is no key array and no sentinel key
-//   place    the pool's packed rows are staged a batch at a time, one row per thread: each of the floor(L / s) unmasked seeds per strand
-//            is looked up (the stored window for strand 0, its reverse complement for strand 1), every hit gives a diagonal, which
-//            is verified on the 2-bit words — XOR, pair-fold, popcount under the overlap and N masks — and counted once: only from
-//            its FIRST clean seed inside the overlap (the earlier seeds are compared again).  Kept per row: the best key
-//            (mismatches, then overlap) with its multiplicity and its diagonal
+//   stage, index, place   fill_place.hpp: the contig 2-bit packed on both strands and the multimap of its s-mers in LDS, the pool's packed
+//            rows staged a batch at a time, one row per thread, each row's best (strand, diagonal) with its multiplicity
 //   vote     a row with one best placement adds its unmasked bases to the columns' four counters (LDS atomics) — PL_VCHUNK body
 //            columns per pass; a longer body costs another pass over the pool (the placement is computed again), never a result
 //   decide   per column, integer comparisons of the four counters: independent of the order of the atomics.  The polished contig goes
@@ -24,68 +14,28 @@
 #include <cstring>
 
 #include "fill_body.hpp"
+#include "fill_place.hpp"
 #include "gf_internal.hpp"
 
 namespace gf {
 
-constexpr uint32_t PL_THREADS = 256, PL_MAX = GF_PL_MAX_CONTIG, PL_VCHUNK = 1024;
-constexpr int PL_LOG2 = 14;
-constexpr uint32_t PL_SLOTS = 1u << PL_LOG2, PL_SLOT_MASK = PL_SLOTS - 1;
-constexpr uint32_t PL_LEAD = 1024;                                           // padding bases on either side of a staged contig (read_len <= 1000)
-constexpr uint32_t PL_CTG_WORDS = (PL_LEAD + PL_MAX + PL_LEAD) / 16 + 2;     // 16 bases a word + the bit stream's over-read
-constexpr uint32_t PL_ROW_BYTES = 9728, PL_ROW_WORDS = PL_ROW_BYTES / 4 + 10; // a batch of rows (256 rows of 150 bases) + misalignment + over-read
-static_assert(PL_SLOTS >= 2 * PL_MAX && PL_MAX < 0xFFFFu && PL_LEAD % 16 == 0, "polish geometry");
+constexpr uint32_t PL_VCHUNK = 1024;
 
 struct PlParams {
-    const uint8_t* pool;
-    const uint32_t* nmask;       // or null
+    PlPlaceArgs place;
     const uint64_t* pool_off;
     uint64_t pool_rows;
-    uint32_t rb, L, nmw, batch_rows;
     FillBodyArgs body;
     const uint32_t* n_contigs;
     uint32_t contig_cap;
     const char* seq;
     const unsigned long long* gap_best;
-    uint32_t n_gaps, s, n_seeds, max_mm, min_ov, min_votes;
+    uint32_t n_gaps, min_votes;
     gf_fill_polish* out;
     uint8_t* bases;
     uint64_t base_cap;
     uint32_t* stats;
 };
-
-__device__ __forceinline__ uint32_t pl_slot(const uint32_t* idx, uint32_t h) { return (idx[h >> 1] >> ((h & 1u) * 16)) & 0xFFFFu; }
-
-// 32 bits -> the even bits of 64 (bit b -> bit 2 b)
-__device__ __forceinline__ uint64_t pl_spread(uint32_t v) {
-    uint64_t x = v;
-    x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
-    x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
-    x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
-    x = (x | (x << 2)) & 0x3333333333333333ull;
-    x = (x | (x << 1)) & 0x5555555555555555ull;
-    return x;
-}
-
-__device__ __forceinline__ uint64_t pl_bits64(const uint32_t* words, uint32_t bit) {
-    return ((uint64_t)stream32(words, bit) << 32) | stream32(words, bit + 32);
-}
-
-// mismatches of the row (bit offset rbit in s_rows, N-mask words nm or null) on the staged contig `ctg` at diagonal D, over the read
-// positions [i0, i1); stops counting beyond `limit`
-__device__ __forceinline__ uint32_t pl_mismatches(const uint32_t* s_rows, uint32_t rbit, const uint32_t* nm, const uint32_t* ctg, int32_t D,
-                                                  uint32_t i0, uint32_t i1, uint32_t limit) {
-    uint32_t mm = 0;
-    for (uint32_t w = i0 >> 5; 32 * w < i1 && mm <= limit; ++w) {
-        const uint32_t lo = i0 > 32 * w ? i0 - 32 * w : 0u, hi = i1 - 32 * w < 32u ? i1 - 32 * w : 32u;
-        uint32_t vm = (hi == 32u ? 0xFFFFFFFFu : (1u << hi) - 1u) & ~((1u << lo) - 1u);       // bit b: read base 32 w + b is compared
-        if (nm) vm &= ~nm[w];
-        const uint64_t x = pl_bits64(s_rows, rbit + 64 * w) ^ pl_bits64(ctg, 2u * (uint32_t)((int32_t)PL_LEAD + D + (int32_t)(32 * w)));
-        const uint64_t m = (x | (x >> 1)) & 0x5555555555555555ull;                            // base b of the word: bit 62 - 2 b
-        mm += (uint32_t)__popcll(m & pl_spread(__brev(vm)));
-    }
-    return mm;
-}
 
 __global__ __launch_bounds__(PL_THREADS) void fill_polish_kernel(PlParams P) {
     __shared__ uint32_t s_idx[PL_SLOTS / 2];
@@ -96,7 +46,7 @@ __global__ __launch_bounds__(PL_THREADS) void fill_polish_kernel(PlParams P) {
     __shared__ uint32_t s_loc[2];
     __shared__ uint32_t s_acc[5];               // a byte that is no base, columns changed, columns uncovered, rows placed, rows ambiguous
     __shared__ unsigned long long s_off;
-    const uint32_t t = threadIdx.x, s = P.s, L = P.L;
+    const uint32_t t = threadIdx.x, L = P.place.L;
     const uint32_t n_list = *P.n_contigs < P.contig_cap ? *P.n_contigs : P.contig_cap;
     for (uint32_t g = blockIdx.x; g < P.n_gaps; g += gridDim.x) {
         const unsigned long long word = P.gap_best[g];
@@ -125,28 +75,8 @@ __global__ __launch_bounds__(PL_THREADS) void fill_polish_kernel(PlParams P) {
             s_off = atomicAdd((unsigned long long*)(P.stats + GF_PL_BASES), (unsigned long long)n);
         }
         __syncthreads();
-        // ---- stage: word w of either array holds the bases 16 w - PL_LEAD .. + 15 of the contig / of its reverse complement
-        if (!is_long) {
-            uint32_t bad = 0;
-            for (uint32_t w = t; w < PL_CTG_WORDS; w += PL_THREADS) {
-                uint32_t vf = 0, vr = 0;
-                const int32_t x0 = (int32_t)(16 * w) - (int32_t)PL_LEAD;
-                if (x0 + 16 > 0 && x0 < (int32_t)n) {
-                    for (int32_t b = 0; b < 16; ++b) {
-                        const int32_t x = x0 + b;
-                        if (x < 0 || x >= (int32_t)n) continue;
-                        const uint32_t cf = base_code4((uint8_t)ctg[x]), cr = base_code4((uint8_t)ctg[n - 1 - (uint32_t)x]);
-                        bad |= cf >> 2;
-                        vf |= (cf & 3u) << (30 - 2 * b);
-                        vr |= (3u - (cr & 3u)) << (30 - 2 * b);
-                    }
-                }
-                s_fwd[w] = bswap32(vf);
-                s_rc[w] = bswap32(vr);
-            }
-            for (uint32_t i = t; i < PL_SLOTS / 2; i += PL_THREADS) s_idx[i] = 0;
-            if (bad) atomicOr(&s_acc[0], 1u);
-        }
+        // ---- stage (fill_place.hpp)
+        if (!is_long && pl_stage_contig(ctg, n, s_fwd, s_rc, s_idx)) atomicOr(&s_acc[0], 1u);
         __syncthreads();
         const uint64_t off = s_off;
         const bool fits = off + n <= P.base_cap;
@@ -166,24 +96,8 @@ __global__ __launch_bounds__(PL_THREADS) void fill_polish_kernel(PlParams P) {
             }
             continue;
         }
-        // ---- index: every s-mer position into the first free slot from its hash on
-        for (uint32_t p = t; p + s <= n; p += PL_THREADS) {
-            const uint64_t key = stream_kmer64(s_fwd, 2 * (PL_LEAD + p), (int)s);
-            uint32_t h = hash_kmer(K128{key, 0}, PL_LOG2);
-            for (;;) {
-                uint32_t* wp = &s_idx[h >> 1];
-                const uint32_t sh = (h & 1u) * 16;
-                uint32_t old = *wp;
-                bool mine = false;
-                while (((old >> sh) & 0xFFFFu) == 0) {
-                    const uint32_t prev = atomicCAS(wp, old, old | ((p + 1) << sh));
-                    if (prev == old) { mine = true; break; }
-                    old = prev;
-                }
-                if (mine) break;
-                h = (h + 1) & PL_SLOT_MASK;
-            }
-        }
+        // ---- index
+        pl_build_index(s_fwd, s_idx, n, P.place.s);
         uint64_t r0 = P.pool_off[g], r1 = P.pool_off[g + 1];
         if (r1 > P.pool_rows) r1 = P.pool_rows;
         if (r0 > r1) r0 = r1;
@@ -192,57 +106,14 @@ __global__ __launch_bounds__(PL_THREADS) void fill_polish_kernel(PlParams P) {
             const uint32_t c_hi = b1 - c_lo < PL_VCHUNK ? b1 : c_lo + PL_VCHUNK;
             for (uint32_t i = t; i < PL_VCHUNK * 4; i += PL_THREADS) s_votes[i] = 0;
             __syncthreads();                     // (also: the index is built)
-            for (uint64_t row0 = r0; row0 < r1; row0 += P.batch_rows) {
-                const uint32_t nb = r1 - row0 < P.batch_rows ? (uint32_t)(r1 - row0) : P.batch_rows;
-                const uint8_t* gp = P.pool + row0 * P.rb;
-                const uint32_t mis = (uint32_t)((uintptr_t)gp & 3u);
-                const uint32_t* gw = (const uint32_t*)(gp - mis);
-                const uint32_t n_words = (mis + nb * P.rb + 3) >> 2;
-                for (uint32_t w = t; w < n_words; w += PL_THREADS) s_rows[w] = gw[w];
-                if (t < 8) s_rows[n_words + t] = 0;
-                __syncthreads();
+            for (uint64_t row0 = r0; row0 < r1; row0 += P.place.batch_rows) {
+                const uint32_t nb = r1 - row0 < P.place.batch_rows ? (uint32_t)(r1 - row0) : P.place.batch_rows;
+                const uint32_t mis = pl_stage_rows(P.place, row0, nb, s_rows);
                 if (t < nb) {
-                    const uint32_t rbit = (mis + t * P.rb) * 8;
-                    const uint32_t* nm = P.nmask ? P.nmask + (row0 + t) * P.nmw : nullptr;
-                    uint32_t best = EMPTY32, cnt = 0, bstrand = 0;
-                    int32_t bD = 0;
-                    for (uint32_t strand = 0; strand < 2; ++strand) {
-                        const uint32_t* A = strand ? s_rc : s_fwd;
-                        for (uint32_t j = 0; j < P.n_seeds; ++j) {
-                            const uint32_t ws = strand ? L - (j + 1) * s : j * s;
-                            if (nm && row_window_masked(nm, P.nmw, ws, s)) continue;
-                            const uint64_t kmer = stream_kmer64(s_rows, rbit + 2 * ws, (int)s);
-                            const uint64_t key = strand ? revpairs64(~kmer) << (64 - 2 * s) : kmer;
-                            uint32_t h = hash_kmer(K128{key, 0}, PL_LOG2);
-                            for (uint32_t e; (e = pl_slot(s_idx, h)) != 0; h = (h + 1) & PL_SLOT_MASK) {
-                                const uint32_t p = e - 1;
-                                if (stream_kmer64(s_fwd, 2 * (PL_LEAD + p), (int)s) != key) continue;
-                                const int32_t D = (strand ? (int32_t)(n - p - s) : (int32_t)p) - (int32_t)ws;
-                                const uint32_t i0 = D < 0 ? (uint32_t)(-D) : 0u, i1 = (int32_t)L < (int32_t)n - D ? L : (uint32_t)((int32_t)n - D);
-                                const uint32_t ov = i1 - i0;
-                                if (ov < P.min_ov) continue;
-                                bool seen = false;                   // an earlier seed of this strand that is clean on this diagonal has counted it
-                                for (uint32_t j2 = 0; j2 < j && !seen; ++j2) {
-                                    const uint32_t w2 = strand ? L - (j2 + 1) * s : j2 * s;
-                                    if (w2 < i0 || w2 + s > i1 || (nm && row_window_masked(nm, P.nmw, w2, s))) continue;
-                                    seen = stream_kmer64(s_rows, rbit + 2 * w2, (int)s) ==
-                                           stream_kmer64(A, 2u * (uint32_t)((int32_t)PL_LEAD + D + (int32_t)w2), (int)s);
-                                }
-                                if (seen) continue;
-                                const uint32_t mm = pl_mismatches(s_rows, rbit, nm, A, D, i0, i1, P.max_mm);
-                                if (mm > P.max_mm) continue;
-                                const uint32_t k2 = (mm << 12) | (4095u - ov);
-                                if (k2 < best) {
-                                    best = k2;
-                                    cnt = 1;
-                                    bstrand = strand;
-                                    bD = D;
-                                } else if (k2 == best) {
-                                    ++cnt;
-                                }
-                            }
-                        }
-                    }
+                    const uint32_t* nm = P.place.nmask ? P.place.nmask + (row0 + t) * P.place.nmw : nullptr;
+                    const PlPlacement pm = pl_place_row(P.place, s_rows, (mis + t * P.place.rb) * 8, nm, s_fwd, s_rc, s_idx, n);
+                    const uint32_t cnt = pm.cnt, bstrand = pm.strand;
+                    const int32_t bD = pm.D;
                     if (pass == 0 && cnt) atomicAdd(&s_acc[cnt == 1 ? 3 : 4], 1u);
                     if (cnt == 1 && c_hi > c_lo) {
                         // strand 0: read base i on column D + i; strand 1: its complement on column n - 1 - D - i
@@ -251,7 +122,7 @@ __global__ __launch_bounds__(PL_THREADS) void fill_polish_kernel(PlParams P) {
                         int32_t hi = bstrand ? (int32_t)n - bD - (int32_t)c_lo : (int32_t)c_hi - bD;
                         lo = lo > i0 ? lo : i0;
                         hi = hi < i1 ? hi : i1;
-                        const uint8_t* rowb = (const uint8_t*)s_rows + mis + t * P.rb;
+                        const uint8_t* rowb = (const uint8_t*)s_rows + mis + t * P.place.rb;
                         for (int32_t i = lo; i < hi; ++i) {
                             if (nm && ((nm[i >> 5] >> (i & 31)) & 1u)) continue;
                             const uint32_t code = (rowb[i >> 2] >> (6 - 2 * (i & 3))) & 3u;
@@ -334,14 +205,14 @@ extern "C" int gf_fill_polish_dev(gf_ctx* ctx, const void* d_pool_packed, const 
         P.body.a_l = (uint32_t)anchor_long;
         P.body.a_s = (uint32_t)anchor_short;
     }
-    P.pool = (const uint8_t*)d_pool_packed;
-    P.nmask = (const uint32_t*)d_nmask_or_null;
+    P.place.pool = (const uint8_t*)d_pool_packed;
+    P.place.nmask = (const uint32_t*)d_nmask_or_null;
     P.pool_off = (const uint64_t*)d_pool_off;
     P.pool_rows = pool_rows;
-    P.rb = (uint32_t)gf_packed_read_bytes(read_len);
-    P.L = (uint32_t)read_len;
-    P.nmw = (uint32_t)((read_len + 31) / 32);
-    P.batch_rows = PL_ROW_BYTES / P.rb < PL_THREADS ? PL_ROW_BYTES / P.rb : PL_THREADS;
+    P.place.rb = (uint32_t)gf_packed_read_bytes(read_len);
+    P.place.L = (uint32_t)read_len;
+    P.place.nmw = (uint32_t)((read_len + 31) / 32);
+    P.place.batch_rows = pl_batch_rows(P.place.rb);
     P.body.contigs = (const gf_contig*)d_contigs;
     P.body.seq = P.seq = (const char*)d_seq;
     P.body.ctg_pick = (const gf_ctg_pick*)d_ctg_pick_or_null;
@@ -349,10 +220,10 @@ extern "C" int gf_fill_polish_dev(gf_ctx* ctx, const void* d_pool_packed, const 
     P.contig_cap = (uint32_t)contig_cap;
     P.gap_best = (const unsigned long long*)d_gap_best;
     P.n_gaps = (uint32_t)ng;
-    P.s = (uint32_t)seed;
-    P.n_seeds = (uint32_t)(read_len / seed);
-    P.max_mm = (uint32_t)max_mismatch;
-    P.min_ov = (uint32_t)min_overlap;
+    P.place.s = (uint32_t)seed;
+    P.place.n_seeds = (uint32_t)(read_len / seed);
+    P.place.max_mm = (uint32_t)max_mismatch;
+    P.place.min_ov = (uint32_t)min_overlap;
     P.min_votes = (uint32_t)min_votes;
     P.out = (gf_fill_polish*)d_polish;
     P.bases = (uint8_t*)d_bases;

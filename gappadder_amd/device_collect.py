@@ -145,6 +145,21 @@ def fill_polish_files(pipe, res, kmers):
     return "".join(fa), "".join(rows)
 
 
+def fill_pairs_tsv(pipe, res, kmers):
+    """fill_pairs.tsv of a step with the pair-span round on: under a header line one row per gap the device step closed and library, in
+    gap order and, per gap, library order: the library's index, the gap's name as in picked_seqs.fa, the fields of the gf_fill_pairs
+    record (Results.pairs) and span_mean_minus_is = span_insert_sum // n_span - the library's insert size (empty without a spanning pair)."""
+    from . import pair_span as PSP
+    names, fields = picked_names(res, kmers), B.FILL_PAIRS.names
+    rows = ["\t".join(("library", "name") + fields + ("span_mean_minus_is",)) + "\n"]
+    for g in sorted(names):
+        for l, lb in enumerate(pipe.libs):
+            rec = res.pairs[l, g]
+            d = PSP.span_mean_minus_is(rec, lb.is_mean)
+            rows.append("\t".join([str(l), names[g]] + [str(int(rec[f])) for f in fields] + ["" if d is None else str(d)]) + "\n")
+    return "".join(rows)
+
+
 class DeviceCollector:
     def __init__(self, gf, cfg, sf_fai, sf_gap_pos, anchor_mapq=30, clip_dist=250, kmers=None, chunk_bytes=256 << 20, log=None):
         """cfg: main.parse_configuration's dictionary.  kmers: the (k, k_velvet) pairs to assemble right away (`-c All`), or None
@@ -489,9 +504,18 @@ class DeviceCollector:
             except ValueError as e:
                 raise SystemExit("parameters.fill_polish_*: %s" % e)
             polish["polish"] = True
+        pairs = {}
+        if cfg.get("fill_pairs") and kk:
+            from . import pair_span as PSP
+            pairs = {"pair_" + x: cfg["fill_pairs_" + x] for x in ("seed", "max_mismatch", "min_overlap", "z") if ("fill_pairs_" + x) in cfg}
+            try:
+                PSP.check_params(L, **{x[len("pair_"):]: v for x, v in pairs.items()})
+            except ValueError as e:
+                raise SystemExit("parameters.fill_pairs_*: %s" % e)
+            pairs["pair_span"] = True
         pipe = Pipeline(gf, len(gaps), L, kk, device=self.dev, anchor_mapq=self.anchor_mapq, clip_dist=self.clip_dist,
                         k_screen=k_screen or None, keep_read_ids=True, probe_column=False,
-                        read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"), **polish)
+                        read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"), **polish, **pairs)
         # (no probe column on the file path: a file-born library is screened once, and until the packing kernels write the column while
         # they hold the bases, building it is a pass of its own — 38 B read + 4 np written per read — that costs more than pass A saves)
         pipe.assemble_in_step = False
@@ -530,6 +554,9 @@ class DeviceCollector:
                 f.write(fa)
             with open(cfg["wf"] + "fill_polish.tsv", "w") as f:
                 f.write(tsv)
+        if res.pairs is not None:
+            with open(cfg["wf"] + "fill_pairs.tsv", "w") as f:
+                f.write(fill_pairs_tsv(pipe, res, cfg["kmers"]))
         return res
 
     def footprint_bytes(self, L):

@@ -71,6 +71,20 @@ def parse_configuration(path):
     if cfg["fill_polish_min_overlap"] < cfg["fill_polish_seed"]:
         raise SystemExit("parameters.fill_polish_min_overlap must be at least fill_polish_seed (%d), not %d"
                          % (cfg["fill_polish_seed"], cfg["fill_polish_min_overlap"]))
+    # extension: pair-span check of the fills the device step closes (pair_span.py): {wf}fill_pairs.tsv, one row per closed gap and library
+    cfg["fill_pairs"] = bool(p.get("fill_pairs", False))
+    for name, default, lo, hi in (("seed", 16, 12, 32), ("max_mismatch", 4, 0, 15), ("min_overlap", 48, 12, None), ("z", 3, 1, None)):
+        key = "fill_pairs_" + name
+        try:
+            v = int(p[key]) if p.get(key) is not None else default
+        except (TypeError, ValueError):
+            raise SystemExit("parameters.%s must be an integer, not %r" % (key, p[key]))
+        if v < lo or (hi is not None and v > hi):
+            raise SystemExit("parameters.%s must be %s, not %r" % (key, "in %d..%d" % (lo, hi) if hi is not None else "at least %d" % lo, v))
+        cfg[key] = v
+    if cfg["fill_pairs_min_overlap"] < cfg["fill_pairs_seed"]:
+        raise SystemExit("parameters.fill_pairs_min_overlap must be at least fill_pairs_seed (%d), not %d"
+                         % (cfg["fill_pairs_seed"], cfg["fill_pairs_min_overlap"]))
     for path_, what in [(cfg["draft"], "draft genome")] + [(a[0], "bam") for a in cfg["alignments"]] + \
                        [(x, "raw reads") for pair in cfg["raw_reads"] for x in pair] + [(cfg["wf"], "working folder")]:
         if not os.path.exists(path_):
@@ -188,6 +202,8 @@ def main_func(command, sf_config):
         if cfg["fill_polish"] and (first_round is None or first_round.polish is None):
             sys.stderr.write("fill_polish: only the first assembly round of the device-resident Collect (-c All) computes it: "
                              "no polished_seqs.fa, no fill_polish.tsv\n")
+        if cfg["fill_pairs"] and (first_round is None or first_round.pairs is None):
+            sys.stderr.write("fill_pairs: only the first assembly round of the device-resident Collect (-c All) computes it: no fill_pairs.tsv\n")
         timings["stages_s"]["collect" + ("_and_first_assembly_round" if first_round is not None else "")] = time.perf_counter() - t0
     if command in ("Assembly", "All"):
         t0 = time.perf_counter()

@@ -24,6 +24,7 @@ What the reference does with files between processes —
     gf_pick_extended[_aligned|_gapped]_dev                             partial fills of the gaps every pick left open (extended_fill.py)
     gf_fill_support_dev                                        how the pool of every closed gap backs the k-mers of its fill (read_support.py)
     gf_fill_polish_dev                                         the pool of every closed gap piled up on its fill: a vote per column (polish.py)
+    gf_fill_pairs_dev                                          per library: the read pairs of every closed gap placed on its fill (pair_span.py)
 
 `Pipeline` owns the sizing pass (capacities follow what the libraries actually recruit), every buffer of the core step, the stream
 wiring and — in a multi-rank run — the one exchange step; an optional round keeps its buffers, sizing, launches and
@@ -39,6 +40,7 @@ import torch
 
 from . import _lib as B
 from . import extended_fill as EXT
+from . import pair_span as PSP
 from . import polish as POL
 from . import read_support as SUP
 from . import rescue_round as RS
@@ -77,7 +79,7 @@ class Results:
     """What one step left on the device, fetched once (contigs, their bases, the pick words, the pools when asked for).  The fields of
     the merge round and of the optional rounds are None unless the round ran."""
     merge = rescue = rescue_first = round2 = round2_first = round2_reads = extended = ext = ext_bases = support = support_stats = None
-    polish = polish_bases = polish_stats = None
+    polish = polish_bases = polish_stats = pairs = pair_stats = lib_pool_off = lib_pool_rows = lib_pool_ids = None
 
 
 # anchor mode -> its pick, its pick over the contigs from an index on, its extended fill; do its picks leave a selection per contig
@@ -92,7 +94,8 @@ class Pipeline:
                  min_count=2, min_contig=40, anchors=(30, 15), clip_dist=250, anchor_mapq=30, k_screen=None, keep_read_ids=False,
                  key_column=True, probe_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False,
                  extended_fill=False, ext_base_cap=None, rescue_round=False, read_support=False, support_k=None, polish=False,
-                 polish_seed=16, polish_max_mismatch=4, polish_min_overlap=48, polish_min_votes=2):
+                 polish_seed=16, polish_max_mismatch=4, polish_min_overlap=48, polish_min_votes=2, pair_span=False, pair_seed=16,
+                 pair_max_mismatch=4, pair_min_overlap=48, pair_z=3):
         """gf: a GapFill whose gaps (and flanks, when a library is screened) are set.  k_pairs: [(k, k_velvet)] of
         assemble_gaps.py:87-122.  The screen runs at the SMALLEST k of the list: a read that shares a 51-mer with a flank shares
         its 31-mers too, so this is the superset every assembly k needs (the reference recruits once, then assembles at every k).
@@ -115,7 +118,10 @@ class Pipeline:
         a record per closed gap of how its pool backs the k-mers of its fill (Results.support).  polish with polish_seed,
         polish_max_mismatch, polish_min_overlap, polish_min_votes (polish.py): last of all, the pool of every closed gap is piled up on
         its winning contig and every column of the fill takes a vote (Results.polish, .polish_bases, .polish_stats;
-        polished_sequences); the step's contigs and picks stay as they are, and read_support keeps describing the UNPOLISHED fill."""
+        polished_sequences); the step's contigs and picks stay as they are, and read_support keeps describing the UNPOLISHED fill.
+        pair_span with pair_seed, pair_max_mismatch, pair_min_overlap, pair_z (pair_span.py): after them, per library, the read pairs of
+        every closed gap placed on its (unpolished) winning contig: inserts against is_mean -/+ pair_z * is_sd and the physical coverage
+        of the fill (Results.pairs [n_lib, n_gaps], .pair_stats); it keeps the pools' read ids (keep_read_ids)."""
         # what the options exclude, before anything touches gf or the library
         single_rank = int(world) == 1 and not force_exchange
         k_round2 = min([int(a) for a, _ in k_pairs if 16 <= int(a) <= 64], default=None)
@@ -133,6 +139,9 @@ class Pipeline:
                          (polish and not single_rank, "polish runs on a single rank"),
                          (polish and second_round, "polish with second_round: the second round assembles a pool of its own, not the step's, "
                                                    "and the polish is defined on the step's pool"),
+                         (pair_span and not single_rank, "pair_span runs on a single rank"),
+                         (pair_span and second_round, "pair_span with second_round: the second round assembles a pool of its own, not the step's, "
+                                                      "and the pairs are looked up in the step's pools"),
                          (extended_fill and not single_rank, "extended_fill runs on a single rank"),
                          (extended_fill and len(k_pairs) > B.EXT_MAX_PAIRS, "extended_fill: at most %d (k, kv) pairs" % B.EXT_MAX_PAIRS)):
             if bad:
@@ -145,6 +154,7 @@ class Pipeline:
         self.ext = EXT.ExtendedFill(self, int(ext_base_cap) if ext_base_cap is not None else None) if extended_fill else None
         self.support = SUP.ReadSupport(self, k_round2 if support_k is None else support_k) if read_support else None
         self.polish = POL.FillPolish(self, polish_seed, polish_max_mismatch, polish_min_overlap, polish_min_votes, read_len) if polish else None
+        self.pairs = PSP.PairSpan(self, pair_seed, pair_max_mismatch, pair_min_overlap, pair_z, read_len) if pair_span else None
         self.gf, self.lib, self.h = gf, B.lib(), gf.handle
         self.n_gaps, self.L, self.kk = int(n_gaps), int(read_len), [(int(a), int(b)) for a, b in k_pairs]
         self.rb = self.lib.gf_packed_read_bytes(self.L)
@@ -156,7 +166,7 @@ class Pipeline:
         self.anchor_pair = (self.anchors[0], self.anchors[1] if len(self.anchors) > 1 else 0)       # a pick's two rounds; 0: no second one
         self.clip_dist, self.anchor_mapq = int(clip_dist), int(anchor_mapq)
         self.k_screen = int(k_screen) if k_screen else (min(a for a, _ in self.kk) if self.kk else 31)
-        self.keep_read_ids = bool(keep_read_ids)
+        self.keep_read_ids = bool(keep_read_ids) or bool(pair_span)
         self.key_column = bool(key_column)
         self.probe_column = bool(probe_column)
         # merge_in_step: the contig-merge round (assemble_gaps.py:301-306 run_contigs_merge: dedup + ContigsMerger per gap) runs INSIDE the
@@ -505,6 +515,8 @@ class Pipeline:
             self.support.prepare()
         if self.polish is not None:     # (after the rounds: its base buffer takes what the contig bases take)
             self.polish.prepare()
+        if self.pairs is not None:
+            self.pairs.prepare()
         if self.tag_ahead:          # the first step's tagger pass (untimed, like a warm-up step's)
             assert all(lb.second_stream for lb in self.libs), "tag_ahead needs DeviceLibrary(tag_ctx=...)"
             self._on_stream(lambda: [self.tagger(lb) for lb in self.libs])
@@ -635,6 +647,8 @@ class Pipeline:
             self.support.enqueue(d_nmask)
         if self.polish is not None:       # (reads the step's contigs and picks, writes buffers of its own)
             self.polish.enqueue(d_nmask)
+        if self.pairs is not None:        # (per library, on the libraries' own pools, ids and masks)
+            self.pairs.enqueue()
 
     def _pick(self, a_long, a_short, first=None, own=None):
         """One pick in the Pipeline's anchor mode over the contigs from index *first on (a device address; None: all of them) of the step's
@@ -721,9 +735,16 @@ class Pipeline:
             self.support.fetch(r)
         if self.polish is not None and self.kk:
             self.polish.fetch(r)
+        if self.pairs is not None and self.kk:
+            self.pairs.fetch(r)
         if pools:
             r.pool_off = r.asm_off_t.cpu().numpy().astype(np.int64)
             r.pool_rows = r.asm_pool_t[:r.asm_rows_total * self.rb].cpu().numpy().reshape(-1, self.rb)
+            if self.pairs is not None:        # the libraries' own pools and read ids: what pair_span_of_results reads
+                r.lib_pool_off = [lb.d_pool_off.cpu().numpy().astype(np.int64) for lb in self.libs]
+                r.lib_pool_rows = [self.d_pools[l * self.lib_cap * self.rb:(l * self.lib_cap + int(o[-1])) * self.rb].cpu().numpy().reshape(-1, self.rb)
+                                   for l, o in enumerate(r.lib_pool_off)]
+                r.lib_pool_ids = [lb.d_ids[:int(o[-1])].cpu().numpy().view(np.uint32) for lb, o in zip(self.libs, r.lib_pool_off)]
         return r
 
     def extended_sequences(self, res):

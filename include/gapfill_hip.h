@@ -811,6 +811,57 @@ int gf_fill_polish_dev(gf_ctx* ctx, const void* d_pool_packed, const void* d_nma
                        const void* d_gap_best, const void* d_ctg_pick_or_null, int anchor_long, int anchor_short, int seed, int max_mismatch,
                        int min_overlap, int min_votes, void* d_polish, void* d_bases, size_t base_cap, void* d_stats);
 
+/* ---- pair-span check of the closed gaps (csrc/fill_pairs.hip; definition and host twin: gappadder_amd/pair_span.py).
+ * One call per library, on THAT library's pool (gf_build_pools_dev: d_pool_packed, d_pool_off, d_pool_read_ids — read = 2 * pair + mate,
+ * per gap ordered by (mate, pair), every read at most once per gap).  For every gap with d_gap_best != 0 the rows of the gap's slice are
+ * placed on the winning contig c (as stored, n bases) by gf_fill_polish_dev's rule with the same seed / max_mismatch / min_overlap: a
+ * row is PLACED (one best (strand, diagonal d)), ambiguous or unplaced.  Rows with the ids r and r ^ 1 both in the slice are a complete
+ * pair; it is placed when both rows are; a placed pair is proper when its mates lie on opposite strands and the strand-0 mate's
+ * diagonal d_f <= the strand-1 mate's d_r, and misoriented otherwise.  insert = d_r + read_len - d_f (signed).  With lo = is_mean -
+ * z * is_sd and hi = is_mean + z * is_sd a proper pair is in range when lo < insert < hi, short when insert <= lo, long when insert >= hi.
+ * A proper pair of any class spans the body [b0, b1) — located as gf_fill_support_dev locates it, same arguments, same mismatch rule —
+ * when d_f <= b0 and b1 <= d_r + read_len.  Every in-range pair covers the columns [max(0, d_f), min(n, d_r + read_len)): min_cover,
+ * min_col (the smallest column with that cover) and n_unspanned (columns with cover 0) are taken over the body; all 0 for an empty body.
+ * A contig of more than GF_PL_MAX_CONTIG bases, or with a byte other than A, C, G, T, is flagged and counted (rows set, everything else 0).
+ * An open gap and a mismatch get the zero record.  seed, max_mismatch, min_overlap as for gf_fill_polish_dev, z >= 1, is_sd >= 0:
+ * GF_E_UNSUPPORTED otherwise.  d_nmask_or_null: mask rows aligned with the pool's rows.  d_place_scratch: u32 per pool row
+ * (pool_cap_rows of them; the rows' placements, overwritten).  d_rec: gf_fill_pairs per gap (every record is written: the plane of this
+ * library in a [n_lib][n_gaps] array); d_stats: u32[GF_PS_WORDS] (set by the call).  GF_E_STATE without flanks. */
+typedef struct {
+    uint32_t flags;            /* GF_PS_F_* */
+    uint32_t rows;             /* rows of the library's pool for the gap */
+    uint32_t pairs_complete;   /* both mates in the pool */
+    uint32_t pairs_placed;     /* ... and both placed */
+    uint32_t n_proper;         /* placed pairs facing each other (FR) */
+    uint32_t n_misoriented;    /* placed pairs that do not */
+    uint32_t n_in_range;       /* proper pairs by insert size */
+    uint32_t n_short;
+    uint32_t n_long;
+    uint32_t n_span;           /* proper pairs that span the body */
+    int64_t span_insert_sum;   /* the sum of their inserts */
+    uint32_t n_cols;           /* body columns */
+    uint32_t min_cover;        /* the fewest in-range pairs over a body column */
+    uint32_t min_col;          /* the first column with that few */
+    uint32_t n_unspanned;      /* body columns no in-range pair covers */
+} gf_fill_pairs;
+#define GF_PS_F_LONG 1         /* skipped: more than GF_PL_MAX_CONTIG bases */
+#define GF_PS_F_NON_ACGT 2     /* skipped: a byte other than A, C, G, T */
+#define GF_PS_GAPS 0           /* gaps examined (not skipped) */
+#define GF_PS_MISMATCH 1       /* closed gaps whose winning contig does not carry the word's pick */
+#define GF_PS_SKIPPED_LONG 2
+#define GF_PS_SKIPPED_NON_ACGT 3
+#define GF_PS_UNSPANNED 4      /* examined gaps with n_unspanned > 0 */
+#define GF_PS_COMPLETE 6       /* u64 each: complete, placed, proper, in-range, spanning pairs */
+#define GF_PS_PLACED 8
+#define GF_PS_PROPER 10
+#define GF_PS_IN_RANGE 12
+#define GF_PS_SPAN 14
+#define GF_PS_WORDS 16
+int gf_fill_pairs_dev(gf_ctx* ctx, const void* d_pool_packed, const void* d_nmask_or_null, const void* d_pool_off, const void* d_pool_read_ids,
+                      size_t pool_cap_rows, int read_len, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
+                      const void* d_gap_best, const void* d_ctg_pick_or_null, int anchor_long, int anchor_short, int seed, int max_mismatch,
+                      int min_overlap, int is_mean, int is_sd, int z, void* d_place_scratch, void* d_rec, void* d_stats);
+
 /* ---- the second assembly round inside the step (assemble_gaps.py:328-368 with collect_both_unmapped_reads.py's recruitment; DESIGN.md
  * "Second round").  Predicate (the CLI's kmer_recruit_unmapped): a both-unmapped pair is recruited for an open gap when one of its reads shares
  * a canonical k-mer with one of the gap's round-1 contigs; k-mers touching a non-ACGT contig base or an N-masked read base do not count.
@@ -928,6 +979,7 @@ int gf_memset_dev(gf_ctx* ctx, void* d_ptr, int value, size_t bytes);
 #define GF_KERNEL_MERGE 10  /* contig-merge prefilter */
 #define GF_KERNEL_SUPPORT 11  /* read support of the closed gaps */
 #define GF_KERNEL_POLISH 12  /* consensus polish of the closed gaps */
+#define GF_KERNEL_PAIRS 13  /* pair-span check of the closed gaps */
 int gf_timing_enable(gf_ctx* ctx, int on);
 int gf_timing_read(gf_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int gf_timing_reset(gf_ctx* ctx);
