@@ -1,7 +1,7 @@
 // fill_body.hpp — where the fill of a closed gap lies on its winning contig: the body [b0, b1) between the two flank hits of the pick
 // word (gappadder_amd/read_support.py: locate).  One rule for the rounds that look at a fill after the last pick of the
-// step: fill_support.hip, fill_polish.hip and fill_pairs.hip (the latter two also through fill_place.hpp, which uses the window-mask
-// and base-code helpers below).  With a gf_ctg_pick per contig (the align and gapped modes) the body lies between the two
+// step — fill_support.hip, fill_polish.hip and fill_pairs.hip —, which reach it through fill_round.hpp's gap prologue (the latter two
+// also use fill_place.hpp, which uses the window-mask and base-code helpers below).  With a gf_ctg_pick per contig (the align and gapped modes) the body lies between the two
 // alignments; without it the exact anchors are re-located by pick.hip's rule at the anchor length the word carries, and a span that
 // is not the word's (unsaturated) span field is a mismatch.
 #pragma once

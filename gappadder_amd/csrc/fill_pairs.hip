@@ -3,9 +3,10 @@
 // library's insert size (gf_fill_pairs_dev, include/gapfill_hip.h; definition and host twin: gappadder_amd/pair_span.py).
 // The reference has no such stage.
 //
-// One workgroup of 256 threads per closed gap, grid-stride over the gaps.  The body [b0, b1) comes from fill_body.hpp, the staging, the
-// index and the placement of a row from fill_place.hpp: both exactly as in fill_polish.hip.  Per gap:
-//   stage, index   fill_place.hpp
+// One workgroup of 256 threads per closed gap, grid-stride over the gaps.  A gap is opened by fill_round.hpp (open / mismatch / ok, the
+// body [b0, b1) of fill_body.hpp, the gap's pool rows); the staging, the index and the placement of a row are fill_place.hpp's, and the
+// launch is set up by fill_round_setup and pl_place_setup.  Per gap:
+//   stage, index   fill_place.hpp (pl_stage_or_skip: a long or non-ACGT contig gets its flag and `rows`)
 //   place    the pool's rows a batch at a time, one row per thread; a row's result — status, strand, diagonal on the contig as stored +
 //            PS_BIAS — goes to one u32 of the caller's scratch array (global memory: a pool has no row bound).  ONE pass over the pool
 //   pair     after a workgroup barrier (the scratch words are written and read by the same workgroup: workgroup scope is enough) every
@@ -20,6 +21,7 @@
 
 #include "fill_body.hpp"
 #include "fill_place.hpp"
+#include "fill_round.hpp"
 #include "gf_internal.hpp"
 
 namespace gf {
@@ -31,19 +33,11 @@ enum { PS_A_BAD, PS_A_COMPLETE, PS_A_PLACED, PS_A_PROPER, PS_A_MISORIENTED, PS_A
 
 struct PsParams {
     PlPlaceArgs place;
-    const uint64_t* pool_off;
+    FillRoundArgs round;         // (pool_off, pool_rows: the library's pool)
     const uint32_t* ids;
-    uint64_t pool_rows;
-    FillBodyArgs body;
-    const uint32_t* n_contigs;
-    uint32_t contig_cap;
-    const char* seq;
-    const unsigned long long* gap_best;
-    uint32_t n_gaps;
     int64_t lo, hi;              // is_mean -/+ z * is_sd
     uint32_t* scratch;
     gf_fill_pairs* out;
-    uint32_t* stats;
 };
 
 // the order of a gap's id slice: mate side, then pair
@@ -60,47 +54,41 @@ __global__ __launch_bounds__(PL_THREADS) void fill_pairs_kernel(PsParams P) {
     __shared__ unsigned long long s_sum, s_min;
     int32_t* s_diff = (int32_t*)s_idx;
     const uint32_t t = threadIdx.x, L = P.place.L;
-    const uint32_t n_list = *P.n_contigs < P.contig_cap ? *P.n_contigs : P.contig_cap;
-    for (uint32_t g = blockIdx.x; g < P.n_gaps; g += gridDim.x) {
-        const unsigned long long word = P.gap_best[g];
+    const uint32_t n_list = fill_round_contigs(P.round);
+    for (uint32_t g = blockIdx.x; g < P.round.n_gaps; g += gridDim.x) {
         gf_fill_pairs rec;
         memset(&rec, 0, sizeof(rec));
-        if (!word) {
+        const FillGap fg = fill_gap_open<PL_THREADS>(P.round, n_list, g, s_loc);        // (fill_round.hpp; the same in all threads)
+        if (fg.state == FILL_GAP_OPEN) {
             if (t == 0) P.out[g] = rec;
             continue;
         }
-        const FillBody fb = fill_body<PL_THREADS>(P.body, n_list, g, word, s_loc);      // (the same in all threads)
-        if (!fb.ok) {
+        if (fg.state == FILL_GAP_MISMATCH) {
             if (t == 0) {
                 P.out[g] = rec;
-                atomicAdd(P.stats + GF_PS_MISMATCH, 1u);
+                atomicAdd(P.round.stats + GF_PS_MISMATCH, 1u);
             }
             continue;
         }
-        const uint32_t n = fb.c.length;
-        const char* ctg = P.seq + fb.c.seq_off;
-        const uint32_t b0 = (uint32_t)fb.b0, b1 = (uint32_t)fb.b1;
-        const bool is_long = n > PL_MAX;
-        uint64_t r0 = P.pool_off[g], r1 = P.pool_off[g + 1];
-        if (r1 > P.pool_rows) r1 = P.pool_rows;
-        if (r0 > r1) r0 = r1;
+        const uint32_t n = fg.fb.c.length;
+        const char* ctg = P.round.body.seq + fg.fb.c.seq_off;
+        const uint32_t b0 = (uint32_t)fg.fb.b0, b1 = (uint32_t)fg.fb.b1;
+        const FillRows rows = fill_gap_rows(P.round, g);
+        const uint64_t r0 = rows.r0, r1 = rows.r1;
         rec.rows = (uint32_t)(r1 - r0);
-        __syncthreads();                         // (the previous gap's record is written)
         if (t < PS_A_N) s_acc[t] = 0;
         if (t == 0) {
             s_sum = 0;
             s_min = ~0ull;
         }
         __syncthreads();
-        // ---- stage (fill_place.hpp)
-        if (!is_long && pl_stage_contig(ctg, n, s_fwd, s_rc, s_idx)) atomicOr(&s_acc[PS_A_BAD], 1u);
-        __syncthreads();
-        const uint32_t skip = is_long ? (uint32_t)GF_PS_F_LONG : s_acc[PS_A_BAD] ? (uint32_t)GF_PS_F_NON_ACGT : 0u;
+        // ---- stage, or skip (fill_place.hpp)
+        const uint32_t skip = pl_stage_or_skip(ctg, n, s_fwd, s_rc, s_idx, &s_acc[PS_A_BAD], GF_PS_F_LONG, GF_PS_F_NON_ACGT);
         if (skip) {
             if (t == 0) {
                 rec.flags = skip;
                 P.out[g] = rec;
-                atomicAdd(P.stats + (is_long ? GF_PS_SKIPPED_LONG : GF_PS_SKIPPED_NON_ACGT), 1u);
+                atomicAdd(P.round.stats + (skip == GF_PS_F_LONG ? GF_PS_SKIPPED_LONG : GF_PS_SKIPPED_NON_ACGT), 1u);
             }
             continue;
         }
@@ -222,13 +210,13 @@ __global__ __launch_bounds__(PL_THREADS) void fill_pairs_kernel(PsParams P) {
                 rec.n_unspanned = s_acc[PS_A_ZERO];
             }
             P.out[g] = rec;
-            atomicAdd(P.stats + GF_PS_GAPS, 1u);
-            if (rec.n_unspanned) atomicAdd(P.stats + GF_PS_UNSPANNED, 1u);
-            atomicAdd((unsigned long long*)(P.stats + GF_PS_COMPLETE), (unsigned long long)rec.pairs_complete);
-            atomicAdd((unsigned long long*)(P.stats + GF_PS_PLACED), (unsigned long long)rec.pairs_placed);
-            atomicAdd((unsigned long long*)(P.stats + GF_PS_PROPER), (unsigned long long)rec.n_proper);
-            atomicAdd((unsigned long long*)(P.stats + GF_PS_IN_RANGE), (unsigned long long)rec.n_in_range);
-            atomicAdd((unsigned long long*)(P.stats + GF_PS_SPAN), (unsigned long long)rec.n_span);
+            atomicAdd(P.round.stats + GF_PS_GAPS, 1u);
+            if (rec.n_unspanned) atomicAdd(P.round.stats + GF_PS_UNSPANNED, 1u);
+            atomicAdd((unsigned long long*)(P.round.stats + GF_PS_COMPLETE), (unsigned long long)rec.pairs_complete);
+            atomicAdd((unsigned long long*)(P.round.stats + GF_PS_PLACED), (unsigned long long)rec.pairs_placed);
+            atomicAdd((unsigned long long*)(P.round.stats + GF_PS_PROPER), (unsigned long long)rec.n_proper);
+            atomicAdd((unsigned long long*)(P.round.stats + GF_PS_IN_RANGE), (unsigned long long)rec.n_in_range);
+            atomicAdd((unsigned long long*)(P.round.stats + GF_PS_SPAN), (unsigned long long)rec.n_span);
         }
     }
 }
@@ -241,55 +229,21 @@ extern "C" int gf_fill_pairs_dev(gf_ctx* ctx, const void* d_pool_packed, const v
                                  size_t pool_cap_rows, int read_len, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
                                  const void* d_gap_best, const void* d_ctg_pick_or_null, int anchor_long, int anchor_short, int seed, int max_mismatch,
                                  int min_overlap, int is_mean, int is_sd, int z, void* d_place_scratch, void* d_rec, void* d_stats) {
-    if (!ctx || !d_pool_off || (pool_cap_rows && (!d_pool_packed || !d_pool_read_ids || !d_place_scratch)) || !d_contigs || !d_n_contigs || !d_seq ||
-        !d_gap_best || !d_rec || !d_stats || read_len < 1 || read_len > 1000 || contig_cap > 0x7FFFFFFFull)
-        return GF_E_INVAL;
-    if (!d_ctg_pick_or_null && (anchor_long < 8 || anchor_long > FB_ANCHOR_MAX || (anchor_short && (anchor_short < 8 || anchor_short >= anchor_long))))
-        return GF_E_INVAL;
-    if (seed < 12 || seed > 32 || max_mismatch < 0 || max_mismatch > 15 || min_overlap < seed || min_overlap > read_len || z < 1 || is_sd < 0 ||
-        read_len / seed <= max_mismatch)
-        return GF_E_UNSUPPORTED;
-    const size_t ng = ctx->gaps.size();
-    if (ctx->flank_left.size() != ng || ctx->flank_right.size() != ng) return GF_E_STATE;
-    GF_HIP(ctx, hipSetDevice(ctx->device));
-    GF_HIP(ctx, hipMemsetAsync(d_stats, 0, 4 * GF_PS_WORDS, ctx->stream));
-    if (!ng) return GF_OK;
+    if (pool_cap_rows && (!d_pool_read_ids || !d_place_scratch)) return GF_E_INVAL;
     PsParams P;
     memset(&P, 0, sizeof(P));
-    int rc;
-    if (!d_ctg_pick_or_null) {
-        if ((rc = anchor_table_for(ctx, anchor_long, &P.body.anc_l))) return rc;
-        if (anchor_short && (rc = anchor_table_for(ctx, anchor_short, &P.body.anc_s))) return rc;
-        P.body.a_l = (uint32_t)anchor_long;
-        P.body.a_s = (uint32_t)anchor_short;
-    }
-    P.place.pool = (const uint8_t*)d_pool_packed;
-    P.place.nmask = (const uint32_t*)d_nmask_or_null;
-    P.place.rb = (uint32_t)gf_packed_read_bytes(read_len);
-    P.place.L = (uint32_t)read_len;
-    P.place.nmw = (uint32_t)((read_len + 31) / 32);
-    P.place.batch_rows = pl_batch_rows(P.place.rb);
-    P.place.s = (uint32_t)seed;
-    P.place.n_seeds = (uint32_t)(read_len / seed);
-    P.place.max_mm = (uint32_t)max_mismatch;
-    P.place.min_ov = (uint32_t)min_overlap;
-    P.pool_off = (const uint64_t*)d_pool_off;
+    int own = pl_place_setup(d_pool_packed, d_nmask_or_null, read_len, seed, max_mismatch, min_overlap, &P.place);
+    if (z < 1 || is_sd < 0) own = GF_E_UNSUPPORTED;
+    const FillRoundIn in = {d_pool_packed, d_pool_off, pool_cap_rows, read_len, d_contigs, d_n_contigs, contig_cap, d_seq, d_gap_best,
+                            d_ctg_pick_or_null, anchor_long, anchor_short, d_rec, d_stats};
+    size_t blocks;
+    const int rc = fill_round_setup(ctx, in, own, GF_PS_WORDS, 3, &P.round, &blocks);   // 3: workgroups the static LDS lets a CU hold
+    if (rc || !blocks) return rc;
     P.ids = (const uint32_t*)d_pool_read_ids;
-    P.pool_rows = pool_cap_rows;
-    P.body.contigs = (const gf_contig*)d_contigs;
-    P.body.seq = P.seq = (const char*)d_seq;
-    P.body.ctg_pick = (const gf_ctg_pick*)d_ctg_pick_or_null;
-    P.n_contigs = (const uint32_t*)d_n_contigs;
-    P.contig_cap = (uint32_t)contig_cap;
-    P.gap_best = (const unsigned long long*)d_gap_best;
-    P.n_gaps = (uint32_t)ng;
     P.lo = (int64_t)is_mean - (int64_t)z * is_sd;
     P.hi = (int64_t)is_mean + (int64_t)z * is_sd;
     P.scratch = (uint32_t*)d_place_scratch;
     P.out = (gf_fill_pairs*)d_rec;
-    P.stats = (uint32_t*)d_stats;
-    const size_t resident = (size_t)ctx->n_cu * 3;                     // workgroups the static LDS lets a CU hold
-    const size_t blocks = ng < resident ? ng : resident;
     LaunchTimer tm(ctx, GF_KERNEL_PAIRS);
     hipLaunchKernelGGL(fill_pairs_kernel, dim3((unsigned)blocks), dim3(PL_THREADS), 0, ctx->stream, P);
     GF_HIP(ctx, hipGetLastError());

@@ -1,10 +1,13 @@
 // fill_place.hpp — the gapless placement of a gap's pool rows on its winning contig (gappadder_amd/polish.py: placements),
-// one device copy for the rounds that place reads on a fill: fill_polish.hip (the vote) and fill_pairs.hip (the pair spans).  Its pieces,
-// all but the last called by every thread of a workgroup of PL_THREADS threads:
+// one device copy for the rounds that place reads on a fill: fill_polish.hip (the vote) and fill_pairs.hip (the pair spans).  Host side,
+// pl_place_setup checks the placement rule of a launch and fills PlPlaceArgs.  The device pieces, all but the last called by every
+// thread of a workgroup of PL_THREADS threads:
 //   pl_stage_contig   the contig, 2 bits a base, twice in LDS: as stored and reverse-complemented, each between PL_LEAD bases of padding, so
 //                     that a read that overhangs either end is compared without a branch (the overlap mask removes the padding).  A read as
 //                     stored on the reverse-complemented contig at diagonal D is the reverse-complemented read on the contig at n - D - L:
 //                     no read is ever reverse-complemented.  Clears the index as well
+//   pl_stage_or_skip  pl_stage_contig, its barrier, and what the round does with the contig: 0 (staged), the round's LONG flag (more than
+//                     PL_MAX bases: nothing staged) or its NON_ACGT flag (a byte that is no base); what a skipped contig gets is the round's
 //   pl_build_index    an open-addressed multimap in LDS from the contig's s-mers to their positions: PL_SLOTS 16-bit slots (position + 1,
 //                     0 = free; load <= 1/2), claimed by a 32-bit CAS on the word that holds the slot; a key is compared through its position
 //                     (the contig's own bases), so there is no key array and no sentinel key
@@ -37,6 +40,26 @@ struct PlPlaceArgs {
 
 // the rows of one batch a workgroup may take: what fits PL_ROW_BYTES, one row per thread at the most
 inline uint32_t pl_batch_rows(uint32_t rb) { return PL_ROW_BYTES / rb < PL_THREADS ? PL_ROW_BYTES / rb : PL_THREADS; }
+
+// The placement rule of a launch as the ABI entries receive it: GF_E_UNSUPPORTED for seed outside 12..32, max_mismatch outside 0..15,
+// min_overlap outside seed..read_len or no more seeds than mismatches (then *A is untouched); else *A is filled and GF_OK returned
+inline int pl_place_setup(const void* d_pool_packed, const void* d_nmask_or_null, int read_len, int seed, int max_mismatch, int min_overlap,
+                          PlPlaceArgs* A) {
+    if (seed < 12 || seed > 32 || max_mismatch < 0 || max_mismatch > 15 || min_overlap < seed || min_overlap > read_len ||
+        read_len / seed <= max_mismatch)
+        return GF_E_UNSUPPORTED;
+    A->pool = (const uint8_t*)d_pool_packed;
+    A->nmask = (const uint32_t*)d_nmask_or_null;
+    A->rb = (uint32_t)gf_packed_read_bytes(read_len);
+    A->L = (uint32_t)read_len;
+    A->nmw = (uint32_t)((read_len + 31) / 32);
+    A->batch_rows = pl_batch_rows(A->rb);
+    A->s = (uint32_t)seed;
+    A->n_seeds = (uint32_t)(read_len / seed);
+    A->max_mm = (uint32_t)max_mismatch;
+    A->min_ov = (uint32_t)min_overlap;
+    return GF_OK;
+}
 
 // cnt accepted (strand, diagonal) pairs share the best key; strand and D are those of the first of them.  D is the diagonal on the array
 // of its strand: on the contig as stored for strand 0, on its reverse complement for strand 1
@@ -101,6 +124,17 @@ __device__ __forceinline__ uint32_t pl_stage_contig(const char* ctg, uint32_t n,
     }
     for (uint32_t i = t; i < PL_SLOTS / 2; i += PL_THREADS) s_idx[i] = 0;
     return bad;
+}
+
+// stage or skip: the contig of n bases is staged unless it is longer than PL_MAX; *s_bad — one word of LDS that is zero before the
+// caller's last barrier — takes the stage's verdict.  Ends on a workgroup barrier.  Returns, the same in all threads, 0 or the flag the
+// round gives a contig it does not place: f_long, f_non_acgt
+__device__ __forceinline__ uint32_t pl_stage_or_skip(const char* ctg, uint32_t n, uint32_t* s_fwd, uint32_t* s_rc, uint32_t* s_idx, uint32_t* s_bad,
+                                                     uint32_t f_long, uint32_t f_non_acgt) {
+    const bool is_long = n > PL_MAX;
+    if (!is_long && pl_stage_contig(ctg, n, s_fwd, s_rc, s_idx)) atomicOr(s_bad, 1u);
+    __syncthreads();
+    return is_long ? f_long : *s_bad ? f_non_acgt : 0u;
 }
 
 // index: every s-mer position into the first free slot from its hash on.  The caller's barrier ends the build

@@ -2,10 +2,11 @@
 // contig, every column of the fill takes a vote, and the polished contig is written out with one record per gap (gf_fill_polish_dev,
 // include/gapfill_hip.h; definition and host twin: gappadder_amd/polish.py).  The reference has no such stage.
 //
-// One workgroup of 256 threads per closed gap, grid-stride over the gaps.  The body [b0, b1) comes from fill_body.hpp, as in
-// fill_support.hip.  Per gap:
-//   stage, index, place   fill_place.hpp: the contig 2-bit packed on both strands and the multimap of its s-mers in LDS, the pool's packed
-//            rows staged a batch at a time, one row per thread, each row's best (strand, diagonal) with its multiplicity
+// One workgroup of 256 threads per closed gap, grid-stride over the gaps.  A gap is opened by fill_round.hpp (open / mismatch / ok, the
+// body [b0, b1) of fill_body.hpp, the gap's pool rows); the launch is set up by fill_round_setup and pl_place_setup.  Per gap:
+//   stage, index, place   fill_place.hpp (pl_stage_or_skip: a long or non-ACGT contig is copied out unpolished): the contig 2-bit packed on
+//            both strands and the multimap of its s-mers in LDS, the pool's packed rows staged a batch at a time, one row per thread,
+//            each row's best (strand, diagonal) with its multiplicity
 //   vote     a row with one best placement adds its unmasked bases to the columns' four counters (LDS atomics) — PL_VCHUNK body
 //            columns per pass; a longer body costs another pass over the pool (the placement is computed again), never a result
 //   decide   per column, integer comparisons of the four counters: independent of the order of the atomics.  The polished contig goes
@@ -15,6 +16,7 @@
 
 #include "fill_body.hpp"
 #include "fill_place.hpp"
+#include "fill_round.hpp"
 #include "gf_internal.hpp"
 
 namespace gf {
@@ -23,18 +25,11 @@ constexpr uint32_t PL_VCHUNK = 1024;
 
 struct PlParams {
     PlPlaceArgs place;
-    const uint64_t* pool_off;
-    uint64_t pool_rows;
-    FillBodyArgs body;
-    const uint32_t* n_contigs;
-    uint32_t contig_cap;
-    const char* seq;
-    const unsigned long long* gap_best;
-    uint32_t n_gaps, min_votes;
+    FillRoundArgs round;
+    uint32_t min_votes;
     gf_fill_polish* out;
     uint8_t* bases;
     uint64_t base_cap;
-    uint32_t* stats;
 };
 
 __global__ __launch_bounds__(PL_THREADS) void fill_polish_kernel(PlParams P) {
@@ -47,41 +42,36 @@ __global__ __launch_bounds__(PL_THREADS) void fill_polish_kernel(PlParams P) {
     __shared__ uint32_t s_acc[5];               // a byte that is no base, columns changed, columns uncovered, rows placed, rows ambiguous
     __shared__ unsigned long long s_off;
     const uint32_t t = threadIdx.x, L = P.place.L;
-    const uint32_t n_list = *P.n_contigs < P.contig_cap ? *P.n_contigs : P.contig_cap;
-    for (uint32_t g = blockIdx.x; g < P.n_gaps; g += gridDim.x) {
-        const unsigned long long word = P.gap_best[g];
+    const uint32_t n_list = fill_round_contigs(P.round);
+    for (uint32_t g = blockIdx.x; g < P.round.n_gaps; g += gridDim.x) {
         gf_fill_polish rec;
         rec.off = 0;
         rec.len = rec.flags = rec.n_cols = rec.n_changed = rec.n_uncovered = rec.reads_placed = rec.reads_ambiguous = rec.reserved = 0;
-        if (!word) {
+        const FillGap fg = fill_gap_open<PL_THREADS>(P.round, n_list, g, s_loc);        // (fill_round.hpp; the same in all threads)
+        if (fg.state == FILL_GAP_OPEN) {
             if (t == 0) P.out[g] = rec;
             continue;
         }
-        const FillBody fb = fill_body<PL_THREADS>(P.body, n_list, g, word, s_loc);      // (the same in all threads)
-        if (!fb.ok) {
+        if (fg.state == FILL_GAP_MISMATCH) {
             if (t == 0) {
                 P.out[g] = rec;
-                atomicAdd(P.stats + GF_PL_MISMATCH, 1u);
+                atomicAdd(P.round.stats + GF_PL_MISMATCH, 1u);
             }
             continue;
         }
-        const uint32_t n = fb.c.length;
-        const char* ctg = P.seq + fb.c.seq_off;
-        const uint32_t b0 = (uint32_t)fb.b0, b1 = (uint32_t)fb.b1, n_cols = b1 - b0;
-        const bool is_long = n > PL_MAX;
-        __syncthreads();                         // (the previous gap's record is written)
+        const uint32_t n = fg.fb.c.length;
+        const char* ctg = P.round.body.seq + fg.fb.c.seq_off;
+        const uint32_t b0 = (uint32_t)fg.fb.b0, b1 = (uint32_t)fg.fb.b1, n_cols = b1 - b0;
         if (t == 0) {
             s_acc[0] = s_acc[1] = s_acc[2] = s_acc[3] = s_acc[4] = 0;
-            s_off = atomicAdd((unsigned long long*)(P.stats + GF_PL_BASES), (unsigned long long)n);
+            s_off = atomicAdd((unsigned long long*)(P.round.stats + GF_PL_BASES), (unsigned long long)n);
         }
         __syncthreads();
-        // ---- stage (fill_place.hpp)
-        if (!is_long && pl_stage_contig(ctg, n, s_fwd, s_rc, s_idx)) atomicOr(&s_acc[0], 1u);
-        __syncthreads();
+        // ---- stage, or skip (fill_place.hpp)
+        const uint32_t skip = pl_stage_or_skip(ctg, n, s_fwd, s_rc, s_idx, &s_acc[0], GF_PL_F_LONG, GF_PL_F_NON_ACGT);
         const uint64_t off = s_off;
         const bool fits = off + n <= P.base_cap;
         uint8_t* outp = P.bases + off;
-        const uint32_t skip = is_long ? (uint32_t)GF_PL_F_LONG : s_acc[0] ? (uint32_t)GF_PL_F_NON_ACGT : 0u;
         if (skip) {                              // copied out unpolished
             if (fits)
                 for (uint32_t i = t; i < n; i += PL_THREADS) outp[i] = (uint8_t)ctg[i];
@@ -91,16 +81,15 @@ __global__ __launch_bounds__(PL_THREADS) void fill_polish_kernel(PlParams P) {
                 rec.flags = skip | (fits ? 0u : (uint32_t)GF_PL_F_OVERFLOW);
                 rec.n_cols = n_cols;
                 P.out[g] = rec;
-                atomicAdd(P.stats + (is_long ? GF_PL_SKIPPED_LONG : GF_PL_SKIPPED_NON_ACGT), 1u);
-                if (!fits) atomicAdd(P.stats + GF_PL_OVERFLOW, 1u);
+                atomicAdd(P.round.stats + (skip == GF_PL_F_LONG ? GF_PL_SKIPPED_LONG : GF_PL_SKIPPED_NON_ACGT), 1u);
+                if (!fits) atomicAdd(P.round.stats + GF_PL_OVERFLOW, 1u);
             }
             continue;
         }
         // ---- index
         pl_build_index(s_fwd, s_idx, n, P.place.s);
-        uint64_t r0 = P.pool_off[g], r1 = P.pool_off[g + 1];
-        if (r1 > P.pool_rows) r1 = P.pool_rows;
-        if (r0 > r1) r0 = r1;
+        const FillRows rows = fill_gap_rows(P.round, g);
+        const uint64_t r0 = rows.r0, r1 = rows.r1;
         // ---- place, vote and decide: PL_VCHUNK body columns per pass (one pass for an empty body: the rows are still counted)
         for (uint32_t c_lo = b0, pass = 0; pass == 0 || c_lo < b1; c_lo += PL_VCHUNK, ++pass) {
             const uint32_t c_hi = b1 - c_lo < PL_VCHUNK ? b1 : c_lo + PL_VCHUNK;
@@ -166,11 +155,11 @@ __global__ __launch_bounds__(PL_THREADS) void fill_polish_kernel(PlParams P) {
             rec.reads_placed = s_acc[3];
             rec.reads_ambiguous = s_acc[4];
             P.out[g] = rec;
-            atomicAdd(P.stats + GF_PL_GAPS, 1u);
-            atomicAdd((unsigned long long*)(P.stats + GF_PL_CHANGED), (unsigned long long)s_acc[1]);
-            atomicAdd((unsigned long long*)(P.stats + GF_PL_PLACED), (unsigned long long)s_acc[3]);
-            atomicAdd((unsigned long long*)(P.stats + GF_PL_AMBIGUOUS), (unsigned long long)s_acc[4]);
-            if (!fits) atomicAdd(P.stats + GF_PL_OVERFLOW, 1u);
+            atomicAdd(P.round.stats + GF_PL_GAPS, 1u);
+            atomicAdd((unsigned long long*)(P.round.stats + GF_PL_CHANGED), (unsigned long long)s_acc[1]);
+            atomicAdd((unsigned long long*)(P.round.stats + GF_PL_PLACED), (unsigned long long)s_acc[3]);
+            atomicAdd((unsigned long long*)(P.round.stats + GF_PL_AMBIGUOUS), (unsigned long long)s_acc[4]);
+            if (!fits) atomicAdd(P.round.stats + GF_PL_OVERFLOW, 1u);
         }
     }
 }
@@ -183,54 +172,20 @@ extern "C" int gf_fill_polish_dev(gf_ctx* ctx, const void* d_pool_packed, const 
                                   int read_len, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
                                   const void* d_gap_best, const void* d_ctg_pick_or_null, int anchor_long, int anchor_short, int seed, int max_mismatch,
                                   int min_overlap, int min_votes, void* d_polish, void* d_bases, size_t base_cap, void* d_stats) {
-    if (!ctx || !d_pool_off || (pool_rows && !d_pool_packed) || !d_contigs || !d_n_contigs || !d_seq || !d_gap_best || !d_polish || !d_stats ||
-        (base_cap && !d_bases) || read_len < 1 || read_len > 1000 || contig_cap > 0x7FFFFFFFull)
-        return GF_E_INVAL;
-    if (!d_ctg_pick_or_null && (anchor_long < 8 || anchor_long > FB_ANCHOR_MAX || (anchor_short && (anchor_short < 8 || anchor_short >= anchor_long))))
-        return GF_E_INVAL;
-    if (seed < 12 || seed > 32 || max_mismatch < 0 || max_mismatch > 15 || min_overlap < seed || min_overlap > read_len || min_votes < 1 ||
-        read_len / seed <= max_mismatch)
-        return GF_E_UNSUPPORTED;
-    const size_t ng = ctx->gaps.size();
-    if (ctx->flank_left.size() != ng || ctx->flank_right.size() != ng) return GF_E_STATE;
-    GF_HIP(ctx, hipSetDevice(ctx->device));
-    GF_HIP(ctx, hipMemsetAsync(d_stats, 0, 4 * GF_PL_WORDS, ctx->stream));
-    if (!ng) return GF_OK;
+    if (base_cap && !d_bases) return GF_E_INVAL;
     PlParams P;
     memset(&P, 0, sizeof(P));
-    int rc;
-    if (!d_ctg_pick_or_null) {
-        if ((rc = anchor_table_for(ctx, anchor_long, &P.body.anc_l))) return rc;
-        if (anchor_short && (rc = anchor_table_for(ctx, anchor_short, &P.body.anc_s))) return rc;
-        P.body.a_l = (uint32_t)anchor_long;
-        P.body.a_s = (uint32_t)anchor_short;
-    }
-    P.place.pool = (const uint8_t*)d_pool_packed;
-    P.place.nmask = (const uint32_t*)d_nmask_or_null;
-    P.pool_off = (const uint64_t*)d_pool_off;
-    P.pool_rows = pool_rows;
-    P.place.rb = (uint32_t)gf_packed_read_bytes(read_len);
-    P.place.L = (uint32_t)read_len;
-    P.place.nmw = (uint32_t)((read_len + 31) / 32);
-    P.place.batch_rows = pl_batch_rows(P.place.rb);
-    P.body.contigs = (const gf_contig*)d_contigs;
-    P.body.seq = P.seq = (const char*)d_seq;
-    P.body.ctg_pick = (const gf_ctg_pick*)d_ctg_pick_or_null;
-    P.n_contigs = (const uint32_t*)d_n_contigs;
-    P.contig_cap = (uint32_t)contig_cap;
-    P.gap_best = (const unsigned long long*)d_gap_best;
-    P.n_gaps = (uint32_t)ng;
-    P.place.s = (uint32_t)seed;
-    P.place.n_seeds = (uint32_t)(read_len / seed);
-    P.place.max_mm = (uint32_t)max_mismatch;
-    P.place.min_ov = (uint32_t)min_overlap;
+    int own = pl_place_setup(d_pool_packed, d_nmask_or_null, read_len, seed, max_mismatch, min_overlap, &P.place);
+    if (min_votes < 1) own = GF_E_UNSUPPORTED;
+    const FillRoundIn in = {d_pool_packed, d_pool_off, pool_rows, read_len, d_contigs, d_n_contigs, contig_cap, d_seq, d_gap_best, d_ctg_pick_or_null,
+                            anchor_long, anchor_short, d_polish, d_stats};
+    size_t blocks;
+    const int rc = fill_round_setup(ctx, in, own, GF_PL_WORDS, 2, &P.round, &blocks);   // 2: workgroups the static LDS lets a CU hold
+    if (rc || !blocks) return rc;
     P.min_votes = (uint32_t)min_votes;
     P.out = (gf_fill_polish*)d_polish;
     P.bases = (uint8_t*)d_bases;
     P.base_cap = base_cap;
-    P.stats = (uint32_t*)d_stats;
-    const size_t resident = (size_t)ctx->n_cu * 2;                     // workgroups the static LDS lets a CU hold
-    const size_t blocks = ng < resident ? ng : resident;
     LaunchTimer tm(ctx, GF_KERNEL_POLISH);
     hipLaunchKernelGGL(fill_polish_kernel, dim3((unsigned)blocks), dim3(PL_THREADS), 0, ctx->stream, P);
     GF_HIP(ctx, hipGetLastError());

@@ -2,15 +2,17 @@
 // about to insert (gf_fill_support_dev, include/gapfill_hip.h; definition and host twin: gappadder_amd/read_support.py).
 // The reference has no such check: it writes whatever the first anchored contig carries.
 //
-// One workgroup of 256 threads per closed gap, grid-stride over the gaps.  The gap's body [b0, b1) on its winning contig comes from the
-// contig's gf_ctg_pick (align / gapped) or from re-locating the exact anchors by pick.hip's rule (fill_body.hpp); the evaluated windows (every k-window
+// One workgroup of 256 threads per closed gap, grid-stride over the gaps.  A gap is opened by fill_round.hpp: open / mismatch / ok, the
+// gap's pool rows and its body [b0, b1) on the winning contig — from the contig's gf_ctg_pick (align / gapped) or from re-locating the
+// exact anchors by pick.hip's rule (fill_body.hpp); the launch is set up by fill_round_setup.  The evaluated windows (every k-window
 // with a body base) are taken in chunks of FS_CHUNK, and per chunk:
 //   build    the chunk's contig bytes are staged in LDS; every window's canonical k-mer goes into an exact-key open-addressed table in
 //            LDS (FS_SLOTS = 2 x FS_CHUNK slots: load <= 1/2).  A slot is claimed by a 32-bit CAS on its OWNER word (window + 1); keys
 //            are compared through the owners' keys, which lie in the first FS_CHUNK entries of the — still unused — key arrays; after a
 //            barrier every owner writes its key (from registers) into its slot and zeroes the slot's counter.  No sentinel key: any
 //            128-bit value is a legal key (k = 64 has a canonical k-mer of all ones in the high word)
-//   count    the pool's packed rows are staged a batch at a time (aligned dword loads; the batch is one contiguous byte range) and the
+//   count    the pool's packed rows are staged a batch at a time (aligned dword loads; the batch is one contiguous byte range; a loop of
+//            its own, not fill_place.hpp's pl_stage_rows: this row buffer is FS_ROW_WORDS long and takes 6 zero tail words, not 8) and the
 //            batch's read windows are dealt to the threads: stream_kmer / stream_kmer64, canonical, hash_kmer, probe; a hit is one LDS
 //            atomicAdd, a miss — most windows — ends at the first free slot
 //   reduce   every window looks its counter up (its slot stayed in a register); n_zero, n_below, min, max, sum by wave reduction and
@@ -20,6 +22,7 @@
 #include <cstring>
 
 #include "fill_body.hpp"
+#include "fill_round.hpp"
 #include "gf_internal.hpp"
 
 namespace gf {
@@ -33,17 +36,10 @@ static_assert(FS_SLOTS == 2 * FS_CHUNK && FS_PER == 4, "fill support geometry");
 struct FsParams {
     const uint8_t* pool;
     const uint32_t* nmask;       // or null
-    const uint64_t* pool_off;
-    uint64_t pool_rows;
+    FillRoundArgs round;
     uint32_t rb, L, nmw, batch_rows;
-    FillBodyArgs body;           // the contig list, its bases, the picks
-    const uint32_t* n_contigs;
-    uint32_t contig_cap;
-    const char* seq;
-    const unsigned long long* gap_best;
-    uint32_t n_gaps, k, min_count;
+    uint32_t k, min_count;
     gf_fill_support* out;
-    uint32_t* stats;
 };
 
 template <bool W>
@@ -59,38 +55,34 @@ __global__ __launch_bounds__(FS_THREADS) void fill_support_kernel(FsParams P) {
     __shared__ uint32_t s_acc[4];               // n_zero, n_below, min, max
     __shared__ unsigned long long s_sum;
     const uint32_t t = threadIdx.x, lane = t & 63, k = P.k;
-    const uint32_t n = *P.n_contigs < P.contig_cap ? *P.n_contigs : P.contig_cap;
+    const uint32_t n = fill_round_contigs(P.round);
     const uint32_t nwin = P.L >= k ? P.L - k + 1 : 0;
-    for (uint32_t g = blockIdx.x; g < P.n_gaps; g += gridDim.x) {
-        const unsigned long long word = P.gap_best[g];
+    for (uint32_t g = blockIdx.x; g < P.round.n_gaps; g += gridDim.x) {
         gf_fill_support rec;
         rec.n_windows = rec.n_zero = rec.n_below = rec.min = rec.max = rec.zero_run = 0;
         rec.sum = 0;
-        if (!word) {
+        // ---- open / mismatch / ok, the body [b0, b1) on the winning contig, the gap's rows (fill_round.hpp; the same in all threads)
+        const FillGap fg = fill_gap_open<FS_THREADS>(P.round, n, g, s_loc);
+        if (fg.state == FILL_GAP_OPEN) {
             if (t == 0) P.out[g] = rec;
             continue;
         }
-        // ---- the body [b0, b1) on the winning contig (fill_body.hpp; every value below is the same in all threads)
-        const FillBody fb = fill_body<FS_THREADS>(P.body, n, g, word, s_loc);
-        const bool ok = fb.ok;
-        const gf_contig c = fb.c;
-        const char* s = P.seq + c.seq_off;
-        const int64_t b0 = fb.b0, b1 = fb.b1;
-        if (!ok) {
+        if (fg.state == FILL_GAP_MISMATCH) {
             if (t == 0) {
                 P.out[g] = rec;
-                atomicAdd(P.stats + GF_FS_MISMATCH, 1u);
+                atomicAdd(P.round.stats + GF_FS_MISMATCH, 1u);
             }
             continue;
         }
+        const gf_contig c = fg.fb.c;
+        const char* s = P.round.body.seq + c.seq_off;
+        const int64_t b0 = fg.fb.b0, b1 = fg.fb.b1;
+        const FillRows rows = fill_gap_rows(P.round, g);
+        const uint64_t r0 = rows.r0, r1 = rows.r1;
         int64_t w_lo = b0 - (int64_t)k + 1, w_hi = (b1 > b0 ? b1 : b0) - 1;
         if (w_lo < 0) w_lo = 0;
         if (w_hi > (int64_t)c.length - (int64_t)k) w_hi = (int64_t)c.length - (int64_t)k;
         const uint32_t n_windows = w_hi >= w_lo ? (uint32_t)(w_hi - w_lo + 1) : 0u;
-        uint64_t r0 = P.pool_off[g], r1 = P.pool_off[g + 1];
-        if (r1 > P.pool_rows) r1 = P.pool_rows;
-        if (r0 > r1) r0 = r1;
-        __syncthreads();                         // (the previous gap's record is written)
         if (t == 0) {
             s_acc[0] = s_acc[1] = s_acc[3] = 0;
             s_acc[2] = EMPTY32;
@@ -263,8 +255,8 @@ __global__ __launch_bounds__(FS_THREADS) void fill_support_kernel(FsParams P) {
                 rec.sum = s_sum;
             }
             P.out[g] = rec;
-            atomicAdd(P.stats + GF_FS_GAPS, 1u);
-            atomicAdd((unsigned long long*)(P.stats + GF_FS_WINDOWS), (unsigned long long)n_windows);
+            atomicAdd(P.round.stats + GF_FS_GAPS, 1u);
+            atomicAdd((unsigned long long*)(P.round.stats + GF_FS_WINDOWS), (unsigned long long)n_windows);
         }
     }
 }
@@ -277,47 +269,24 @@ extern "C" int gf_fill_support_dev(gf_ctx* ctx, const void* d_pool_packed, const
                                    int read_len, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
                                    const void* d_gap_best, const void* d_ctg_pick_or_null, int anchor_long, int anchor_short, int k, int min_count,
                                    void* d_support, void* d_stats) {
-    if (!ctx || !d_pool_off || (pool_rows && !d_pool_packed) || !d_contigs || !d_n_contigs || !d_seq || !d_gap_best || !d_support || !d_stats ||
-        read_len < 1 || read_len > 1000 || contig_cap > 0x7FFFFFFFull || min_count < 0)
-        return GF_E_INVAL;
-    if (!d_ctg_pick_or_null && (anchor_long < 8 || anchor_long > FB_ANCHOR_MAX || (anchor_short && (anchor_short < 8 || anchor_short >= anchor_long))))
-        return GF_E_INVAL;
-    if (k < 16 || k > 64) return GF_E_UNSUPPORTED;
-    const size_t ng = ctx->gaps.size();
-    if (ctx->flank_left.size() != ng || ctx->flank_right.size() != ng) return GF_E_STATE;
-    GF_HIP(ctx, hipSetDevice(ctx->device));
-    GF_HIP(ctx, hipMemsetAsync(d_stats, 0, 4 * GF_FS_WORDS, ctx->stream));
-    if (!ng) return GF_OK;
+    if (min_count < 0) return GF_E_INVAL;
+    const FillRoundIn in = {d_pool_packed, d_pool_off, pool_rows, read_len, d_contigs, d_n_contigs, contig_cap, d_seq, d_gap_best, d_ctg_pick_or_null,
+                            anchor_long, anchor_short, d_support, d_stats};
     FsParams P;
     memset(&P, 0, sizeof(P));
-    int rc;
-    if (!d_ctg_pick_or_null) {
-        if ((rc = anchor_table_for(ctx, anchor_long, &P.body.anc_l))) return rc;
-        if (anchor_short && (rc = anchor_table_for(ctx, anchor_short, &P.body.anc_s))) return rc;
-        P.body.a_l = (uint32_t)anchor_long;
-        P.body.a_s = (uint32_t)anchor_short;
-    }
+    size_t blocks;
+    // workgroups the static LDS lets a CU hold: 3 with the wide table, 4 with the narrow one
+    const int rc = fill_round_setup(ctx, in, k < 16 || k > 64 ? GF_E_UNSUPPORTED : GF_OK, GF_FS_WORDS, k > 32 ? 3 : 4, &P.round, &blocks);
+    if (rc || !blocks) return rc;
     P.pool = (const uint8_t*)d_pool_packed;
     P.nmask = (const uint32_t*)d_nmask_or_null;
-    P.pool_off = (const uint64_t*)d_pool_off;
-    P.pool_rows = pool_rows;
     P.rb = (uint32_t)gf_packed_read_bytes(read_len);
     P.L = (uint32_t)read_len;
     P.nmw = (uint32_t)((read_len + 31) / 32);
     P.batch_rows = FS_ROW_BYTES / P.rb;
-    P.body.contigs = (const gf_contig*)d_contigs;
-    P.n_contigs = (const uint32_t*)d_n_contigs;
-    P.contig_cap = (uint32_t)contig_cap;
-    P.seq = P.body.seq = (const char*)d_seq;
-    P.gap_best = (const unsigned long long*)d_gap_best;
-    P.body.ctg_pick = (const gf_ctg_pick*)d_ctg_pick_or_null;
-    P.n_gaps = (uint32_t)ng;
     P.k = (uint32_t)k;
     P.min_count = (uint32_t)min_count;
     P.out = (gf_fill_support*)d_support;
-    P.stats = (uint32_t*)d_stats;
-    const size_t resident = (size_t)ctx->n_cu * (k > 32 ? 3 : 4);      // workgroups the static LDS lets a CU hold: wide / narrow table
-    const size_t blocks = ng < resident ? ng : resident;
     LaunchTimer tm(ctx, GF_KERNEL_SUPPORT);
     if (k > 32)
         hipLaunchKernelGGL(fill_support_kernel<true>, dim3((unsigned)blocks), dim3(FS_THREADS), 0, ctx->stream, P);

@@ -213,7 +213,7 @@ struct ZeroList {
 };
 void zero_regions(gf_ctx* ctx, const ZeroList& z);
 
-// pick.hip: the exact anchors of one length (built once per gf_set_gaps; also read by fill_support.hip, fill_polish.hip and fill_pairs.hip through fill_body.hpp); pick_align.hip: the align-mode hits of the extended fill
+// pick.hip: the exact anchors of one length (built once per gf_set_gaps; also read by the after-pick rounds, whose one launch setup — fill_round_setup, api.hip, declared in fill_round.hpp — asks for them); pick_align.hip: the align-mode hits of the extended fill
 int anchor_table_for(gf_ctx* ctx, int anchor_len, const uint8_t** out);
 int launch_align_ext(gf_ctx* ctx, bool gapped, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t, const void* d_first,
                      const void* d_gap_best, ExtHit* hits, uint32_t* heads, uint32_t* stats);

@@ -117,19 +117,18 @@ def picked_names(res, kmers):
 
 
 SUPPORT_FIELDS = ("n_windows", "n_zero", "n_below", "min", "max", "zero_run", "sum")
+POLISH_FIELDS = ("len", "flags", "n_cols", "n_changed", "n_uncovered", "reads_placed", "reads_ambiguous")
+
+
+def _tsv(names, header, rows_of):
+    """A header line, then rows_of(g, name) — lists of cells — for the gaps of `names` (picked_names) in gap order."""
+    return "".join("\t".join(cells) + "\n" for cells in [header] + [r for g in sorted(names) for r in rows_of(g, names[g])])
 
 
 def fill_support_tsv(res, kmers):
     """fill_support.tsv: a header line, then one row per gap the device step closed — its picked_seqs.fa name and the fields of its
     gf_fill_support record (Results.support), in gap order."""
-    names = picked_names(res, kmers)
-    rows = ["\t".join(("name",) + SUPPORT_FIELDS) + "\n"]
-    for g in sorted(names):
-        rows.append("\t".join([names[g]] + [str(int(res.support[g][f])) for f in SUPPORT_FIELDS]) + "\n")
-    return "".join(rows)
-
-
-POLISH_FIELDS = ("len", "flags", "n_cols", "n_changed", "n_uncovered", "reads_placed", "reads_ambiguous")
+    return _tsv(picked_names(res, kmers), ("name",) + SUPPORT_FIELDS, lambda g, name: [[name] + [str(int(res.support[g][f])) for f in SUPPORT_FIELDS]])
 
 
 def fill_polish_files(pipe, res, kmers):
@@ -137,12 +136,8 @@ def fill_polish_files(pipe, res, kmers):
     closed, named as in picked_seqs.fa: the polished gap sequence (Pipeline.polished_sequences) in lines of 60, and the fields of the
     gap's gf_fill_polish record (Results.polish) under a header line."""
     names, seqs = picked_names(res, kmers), pipe.polished_sequences(res)
-    fa, rows = [], ["\t".join(("name",) + POLISH_FIELDS) + "\n"]
-    for g in sorted(names):
-        seq = seqs[g][1]
-        fa.append(">" + names[g] + "\n" + "".join(seq[i:i + 60] + "\n" for i in range(0, len(seq), 60)))
-        rows.append("\t".join([names[g]] + [str(int(res.polish[g][f])) for f in POLISH_FIELDS]) + "\n")
-    return "".join(fa), "".join(rows)
+    fa = [">" + names[g] + "\n" + "".join(seqs[g][1][i:i + 60] + "\n" for i in range(0, len(seqs[g][1]), 60)) for g in sorted(names)]
+    return "".join(fa), _tsv(names, ("name",) + POLISH_FIELDS, lambda g, name: [[name] + [str(int(res.polish[g][f])) for f in POLISH_FIELDS]])
 
 
 def fill_pairs_tsv(pipe, res, kmers):
@@ -150,14 +145,25 @@ def fill_pairs_tsv(pipe, res, kmers):
     gap order and, per gap, library order: the library's index, the gap's name as in picked_seqs.fa, the fields of the gf_fill_pairs
     record (Results.pairs) and span_mean_minus_is = span_insert_sum // n_span - the library's insert size (empty without a spanning pair)."""
     from . import pair_span as PSP
-    names, fields = picked_names(res, kmers), B.FILL_PAIRS.names
-    rows = ["\t".join(("library", "name") + fields + ("span_mean_minus_is",)) + "\n"]
-    for g in sorted(names):
+    fields = B.FILL_PAIRS.names
+
+    def rows_of(g, name):
         for l, lb in enumerate(pipe.libs):
             rec = res.pairs[l, g]
             d = PSP.span_mean_minus_is(rec, lb.is_mean)
-            rows.append("\t".join([str(l), names[g]] + [str(int(rec[f])) for f in fields] + ["" if d is None else str(d)]) + "\n")
-    return "".join(rows)
+            yield [str(l), name] + [str(int(rec[f])) for f in fields] + ["" if d is None else str(d)]
+    return _tsv(picked_names(res, kmers), ("library", "name") + fields + ("span_mean_minus_is",), rows_of)
+
+
+def round_keywords(cfg, L, rnd, prefix, names, check, switch):
+    """The Pipeline keywords of an optional round of the CLI: <prefix>_<name> = cfg["fill_<rnd>_<name>"] for the names the configuration
+    holds, validated against the read length by `check` (its ValueError ends the run), and <switch> = True."""
+    own = {x: cfg["fill_%s_%s" % (rnd, x)] for x in names if "fill_%s_%s" % (rnd, x) in cfg}
+    try:
+        check(L, **own)
+    except ValueError as e:
+        raise SystemExit("parameters.fill_%s_*: %s" % (rnd, e))
+    return dict({"%s_%s" % (prefix, x): v for x, v in own.items()}, **{switch: True})
 
 
 class DeviceCollector:
@@ -495,24 +501,12 @@ class DeviceCollector:
                 libs = None
                 torch.cuda.empty_cache()
         kk = self._usable_pairs(L)
-        polish = {}
-        if cfg.get("fill_polish") and kk:
-            from . import polish as POL
-            polish = {"polish_" + x: cfg["fill_polish_" + x] for x in ("seed", "max_mismatch", "min_overlap", "min_votes") if ("fill_polish_" + x) in cfg}
-            try:
-                POL.check_params(L, **{x[len("polish_"):]: v for x, v in polish.items()})
-            except ValueError as e:
-                raise SystemExit("parameters.fill_polish_*: %s" % e)
-            polish["polish"] = True
-        pairs = {}
-        if cfg.get("fill_pairs") and kk:
-            from . import pair_span as PSP
-            pairs = {"pair_" + x: cfg["fill_pairs_" + x] for x in ("seed", "max_mismatch", "min_overlap", "z") if ("fill_pairs_" + x) in cfg}
-            try:
-                PSP.check_params(L, **{x[len("pair_"):]: v for x, v in pairs.items()})
-            except ValueError as e:
-                raise SystemExit("parameters.fill_pairs_*: %s" % e)
-            pairs["pair_span"] = True
+        from . import pair_span as PSP
+        from . import polish as POL
+        polish = round_keywords(cfg, L, "polish", "polish", ("seed", "max_mismatch", "min_overlap", "min_votes"), POL.check_params, "polish") \
+            if cfg.get("fill_polish") and kk else {}
+        pairs = round_keywords(cfg, L, "pairs", "pair", ("seed", "max_mismatch", "min_overlap", "z"), PSP.check_params, "pair_span") \
+            if cfg.get("fill_pairs") and kk else {}
         pipe = Pipeline(gf, len(gaps), L, kk, device=self.dev, anchor_mapq=self.anchor_mapq, clip_dist=self.clip_dist,
                         k_screen=k_screen or None, keep_read_ids=True, probe_column=False,
                         read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"), **polish, **pairs)
@@ -545,18 +539,16 @@ class DeviceCollector:
             t0 = time.perf_counter()
             self._write_files(pipe, libs, names, gaps, keys, folders, merge_folder)
             self.t["write_files"] = time.perf_counter() - t0
+        files = {}
         if res.support is not None:
-            with open(cfg["wf"] + "fill_support.tsv", "w") as f:
-                f.write(fill_support_tsv(res, cfg["kmers"]))
+            files["fill_support.tsv"] = fill_support_tsv(res, cfg["kmers"])
         if res.polish is not None:
-            fa, tsv = fill_polish_files(pipe, res, cfg["kmers"])
-            with open(cfg["wf"] + "polished_seqs.fa", "w") as f:
-                f.write(fa)
-            with open(cfg["wf"] + "fill_polish.tsv", "w") as f:
-                f.write(tsv)
+            files["polished_seqs.fa"], files["fill_polish.tsv"] = fill_polish_files(pipe, res, cfg["kmers"])
         if res.pairs is not None:
-            with open(cfg["wf"] + "fill_pairs.tsv", "w") as f:
-                f.write(fill_pairs_tsv(pipe, res, cfg["kmers"]))
+            files["fill_pairs.tsv"] = fill_pairs_tsv(pipe, res, cfg["kmers"])
+        for name, text in files.items():
+            with open(cfg["wf"] + name, "w") as f:
+                f.write(text)
         return res
 
     def footprint_bytes(self, L):

@@ -59,32 +59,21 @@ def parse_configuration(path):
     # extension: consensus polish of the fills the device step closes (polish.py): {wf}polished_seqs.fa — picked_seqs.fa's cut of the
     # winning contig after the gap's own reads have voted on every column of the fill — and {wf}fill_polish.tsv, one row per closed gap
     cfg["fill_polish"] = bool(p.get("fill_polish", False))
-    for name, default, lo, hi in (("seed", 16, 12, 32), ("max_mismatch", 4, 0, 15), ("min_overlap", 48, 12, None), ("min_votes", 2, 1, None)):
-        key = "fill_polish_" + name
-        try:
-            v = int(p[key]) if p.get(key) is not None else default
-        except (TypeError, ValueError):
-            raise SystemExit("parameters.%s must be an integer, not %r" % (key, p[key]))
-        if v < lo or (hi is not None and v > hi):
-            raise SystemExit("parameters.%s must be %s, not %r" % (key, "in %d..%d" % (lo, hi) if hi is not None else "at least %d" % lo, v))
-        cfg[key] = v
-    if cfg["fill_polish_min_overlap"] < cfg["fill_polish_seed"]:
-        raise SystemExit("parameters.fill_polish_min_overlap must be at least fill_polish_seed (%d), not %d"
-                         % (cfg["fill_polish_seed"], cfg["fill_polish_min_overlap"]))
     # extension: pair-span check of the fills the device step closes (pair_span.py): {wf}fill_pairs.tsv, one row per closed gap and library
     cfg["fill_pairs"] = bool(p.get("fill_pairs", False))
-    for name, default, lo, hi in (("seed", 16, 12, 32), ("max_mismatch", 4, 0, 15), ("min_overlap", 48, 12, None), ("z", 3, 1, None)):
-        key = "fill_pairs_" + name
-        try:
-            v = int(p[key]) if p.get(key) is not None else default
-        except (TypeError, ValueError):
-            raise SystemExit("parameters.%s must be an integer, not %r" % (key, p[key]))
-        if v < lo or (hi is not None and v > hi):
-            raise SystemExit("parameters.%s must be %s, not %r" % (key, "in %d..%d" % (lo, hi) if hi is not None else "at least %d" % lo, v))
-        cfg[key] = v
-    if cfg["fill_pairs_min_overlap"] < cfg["fill_pairs_seed"]:
-        raise SystemExit("parameters.fill_pairs_min_overlap must be at least fill_pairs_seed (%d), not %d"
-                         % (cfg["fill_pairs_seed"], cfg["fill_pairs_min_overlap"]))
+    for rnd, own in (("polish", ("min_votes", 2, 1, None)), ("pairs", ("z", 3, 1, None))):     # (name, default, lo, hi) of fill_<round>_<name>
+        for name, default, lo, hi in (("seed", 16, 12, 32), ("max_mismatch", 4, 0, 15), ("min_overlap", 48, 12, None), own):
+            key = "fill_%s_%s" % (rnd, name)
+            try:
+                v = int(p[key]) if p.get(key) is not None else default
+            except (TypeError, ValueError):
+                raise SystemExit("parameters.%s must be an integer, not %r" % (key, p[key]))
+            if v < lo or (hi is not None and v > hi):
+                raise SystemExit("parameters.%s must be %s, not %r" % (key, "in %d..%d" % (lo, hi) if hi is not None else "at least %d" % lo, v))
+            cfg[key] = v
+        if cfg["fill_%s_min_overlap" % rnd] < cfg["fill_%s_seed" % rnd]:
+            raise SystemExit("parameters.fill_%s_min_overlap must be at least fill_%s_seed (%d), not %d"
+                             % (rnd, rnd, cfg["fill_%s_seed" % rnd], cfg["fill_%s_min_overlap" % rnd]))
     for path_, what in [(cfg["draft"], "draft genome")] + [(a[0], "bam") for a in cfg["alignments"]] + \
                        [(x, "raw reads") for pair in cfg["raw_reads"] for x in pair] + [(cfg["wf"], "working folder")]:
         if not os.path.exists(path_):
@@ -197,13 +186,9 @@ def main_func(command, sf_config):
                     timings.pop(key, None)
         if not done:
             collect_per_scaffold(cfg, gf, sf_fai, sf_gap_pos, folders, anchor_mapq, clip_dist, wf)
-        if cfg["fill_support"] and (first_round is None or first_round.support is None):
-            sys.stderr.write("fill_support: only the first assembly round of the device-resident Collect (-c All) computes it: no fill_support.tsv\n")
-        if cfg["fill_polish"] and (first_round is None or first_round.polish is None):
-            sys.stderr.write("fill_polish: only the first assembly round of the device-resident Collect (-c All) computes it: "
-                             "no polished_seqs.fa, no fill_polish.tsv\n")
-        if cfg["fill_pairs"] and (first_round is None or first_round.pairs is None):
-            sys.stderr.write("fill_pairs: only the first assembly round of the device-resident Collect (-c All) computes it: no fill_pairs.tsv\n")
+        for rnd, files in (("support", "no fill_support.tsv"), ("polish", "no polished_seqs.fa, no fill_polish.tsv"), ("pairs", "no fill_pairs.tsv")):
+            if cfg["fill_" + rnd] and (first_round is None or getattr(first_round, rnd) is None):
+                sys.stderr.write("fill_%s: only the first assembly round of the device-resident Collect (-c All) computes it: %s\n" % (rnd, files))
         timings["stages_s"]["collect" + ("_and_first_assembly_round" if first_round is not None else "")] = time.perf_counter() - t0
     if command in ("Assembly", "All"):
         t0 = time.perf_counter()

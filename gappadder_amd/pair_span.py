@@ -28,33 +28,21 @@ import numpy as np
 import torch
 
 from . import _lib as B
+from . import fill_rounds as FR
 from . import pipeline as P
 from . import polish as POL
-from . import read_support as SUP
+from .fill_rounds import MAX_CONTIG
 
 SEED, MAX_MISMATCH, MIN_OVERLAP, Z = 16, 4, 48, 3       # (the first three: the polish's defaults)
-MAX_CONTIG = B.PL_MAX_CONTIG
 COUNT_FIELDS = ("pairs_complete", "pairs_placed", "n_proper", "n_misoriented", "n_in_range", "n_short", "n_long", "n_span")
 STAT_KEYS = ("gaps", "mismatches", "skipped_long", "skipped_non_acgt", "unspanned", "complete", "placed", "proper", "in_range", "span")
 
 
 def check_params(L, seed=SEED, max_mismatch=MAX_MISMATCH, min_overlap=MIN_OVERLAP, z=Z, is_sd=0):
     """The four parameters as integers; ValueError for a value out of range (module docstring; the ABI answers GF_E_UNSUPPORTED)."""
-    L, s, mm, mo, zz = int(L), int(seed), int(max_mismatch), int(min_overlap), int(z)
-    if not 12 <= s <= 32:
-        raise ValueError("pair_span seed %r: 12..32" % (seed,))
-    if not 0 <= mm <= 15:
-        raise ValueError("pair_span max_mismatch %r: 0..15" % (max_mismatch,))
-    if not s <= mo <= L:
-        raise ValueError("pair_span min_overlap %r: at least the seed (%d), at most the read length (%d)" % (min_overlap, s, L))
-    if zz < 1 or zz != z:
-        raise ValueError("pair_span z %r: an integer, at least 1" % (z,))
-    if int(is_sd) < 0:
-        raise ValueError("pair_span is_sd %r: at least 0" % (is_sd,))
-    if L // s <= mm:
-        raise ValueError("pair_span seed %d with max_mismatch %d: a read of %d bases has %d seeds, and more seeds than mismatches are needed"
-                         % (s, mm, L, L // s))
-    return s, mm, mo, zz
+    zz = int(z)
+    return FR.check_placement("pair_span", L, seed, max_mismatch, min_overlap, [(zz < 1 or zz != z, "z %r: an integer, at least 1" % (z,)),
+                                                                               (int(is_sd) < 0, "is_sd %r: at least 0" % (is_sd,))]) + (zz,)
 
 
 def pair_span_host(reads, ids, contig, b0, b1, is_mean, is_sd, seed=SEED, max_mismatch=MAX_MISMATCH, min_overlap=MIN_OVERLAP, z=Z, detail=False):
@@ -71,8 +59,7 @@ def pair_span_host(reads, ids, contig, b0, b1, is_mean, is_sd, seed=SEED, max_mi
     n = len(contig)
     rec = np.zeros((), dtype=B.FILL_PAIRS)
     rec["rows"] = len(ids)
-    raw = np.frombuffer(contig.encode(), dtype=np.uint8)
-    flag = B.PS_F_LONG if n > MAX_CONTIG else B.PS_F_NON_ACGT if (POL._LUT[raw] > 3).any() else 0
+    flag = FR.skip_flag(contig, B.PS_F_LONG, B.PS_F_NON_ACGT)
     if flag:
         rec["flags"] = flag
         return (rec, []) if detail else rec
@@ -134,16 +121,11 @@ def pair_span_of_results(res, flanks, L, libs, seed=SEED, max_mismatch=MAX_MISMA
         check_params(L, seed, max_mismatch, min_overlap, z, is_sd)
         off, rows, ids = res.lib_pool_off[l], res.lib_pool_rows[l], res.lib_pool_ids[l]
         nm = None if nmasks is None else nmasks[l]
-        for g in np.nonzero(res.best)[0]:
-            ci = P.decode_best(res.best[g])[2]
-            ok = ci < len(res.contigs) and int(res.contigs[ci]["gap"]) == g
-            contig = P.contig_text(res, ci) if ok else ""
-            body = SUP.locate(res.best[g], contig, flanks[g], res.ctg_pick[ci] if res.ctg_pick is not None else None) if ok else None
+        for g, contig, body in FR.closed_fills(res, flanks):
             if body is None:
                 stats[l]["mismatches"] += 1
                 continue
-            r0, r1 = int(off[g]), int(off[g + 1])
-            reads = SUP.codes_of_rows(rows[r0:r1], L, None if nm is None else nm[r0:r1])
+            r0, r1, reads = FR.pool_reads(off, rows, g, L, nm)
             out[l, g] = pair_span_host(reads, ids[r0:r1], contig, body[0], body[1], is_mean, is_sd, seed, max_mismatch, min_overlap, z)
             add_to_stats(stats[l], out[l, g])
     return out, stats
@@ -163,11 +145,12 @@ def span_mean_minus_is(rec, is_mean):
     return int(rec["span_insert_sum"]) // int(rec["n_span"]) - int(is_mean) if int(rec["n_span"]) else None
 
 
-class PairSpan:
+class PairSpan(FR.FillRound):
+    WHAT, RECORD = "pair span", B.FILL_PAIRS
+
     def __init__(self, pipe, seed=SEED, max_mismatch=MAX_MISMATCH, min_overlap=MIN_OVERLAP, z=Z, read_len=None):
-        self.p = pipe
+        super().__init__(pipe)
         self.params = check_params(read_len, seed, max_mismatch, min_overlap, z)
-        self.d_rec = None
 
     def prepare(self):
         """A record plane and a block of statistics words per library; one placement word per row of a library's pool array and — when a
@@ -192,28 +175,19 @@ class PairSpan:
                                         lb.d_pool_off.data_ptr() + 8 * p.n_gaps, p.lib_cap, self.d_nm.data_ptr()), "gf_gather_rows_dev")
         return self.d_nm.data_ptr()
 
-    def enqueue(self):
-        """After the last pick of the step (and the read-support and polish rounds): one launch per library, on that library's pool, read
-        ids and — gathered by the ids — N masks."""
+    def _launch(self, d_nmask):
+        """One launch per library (after the read-support and polish rounds), on that library's pool, read ids and — gathered by the
+        ids, so d_nmask, the masks of the step's merged pool, is not used — N masks."""
         p = self.p
-        if self.d_rec is None:        # a sizing run of one of the rounds: nobody reads its records
-            return
-        a_long, a_short = p.anchor_pair if not p.per_contig else (0, 0)
         for l, lb in enumerate(p.libs):
-            d_nm = self.masks_of(l)
-            p._chk(p.lib.gf_fill_pairs_dev(p.h, p.pool_ptr[l], d_nm, lb.d_pool_off.data_ptr(), lb.d_ids.data_ptr(), p.lib_cap, p.L,
-                                           p.d_ctg.data_ptr(), p.ap, p.contig_cap, p.d_seq.data_ptr(), p.d_best.data_ptr(),
-                                           p.d_ctg_pick.data_ptr() if p.per_contig else None, a_long, a_short, *self.params[:3],
-                                           lb.is_mean, lb.is_sd, self.params[3], self.d_scratch.data_ptr(), self.d_rec.data_ptr() + l * self.plane,
-                                           self.d_stats.data_ptr() + 4 * l * B.PS_WORDS), "gf_fill_pairs_dev")
+            p._chk(p.lib.gf_fill_pairs_dev(p.h, p.pool_ptr[l], self.masks_of(l), lb.d_pool_off.data_ptr(), lb.d_ids.data_ptr(), p.lib_cap, p.L,
+                                           *self.shared_args(), *self.params[:3], lb.is_mean, lb.is_sd, self.params[3], self.d_scratch.data_ptr(),
+                                           self.d_rec.data_ptr() + l * self.plane, self.d_stats.data_ptr() + 4 * l * B.PS_WORDS), "gf_fill_pairs_dev")
 
     def fetch(self, r):
         p = self.p
         st = self.d_stats.cpu().numpy().reshape(len(p.libs), B.PS_WORDS)
         r.pair_stats = [stats_of(st[l]) for l in range(len(p.libs))]
-        bad = max(s["mismatches"] for s in r.pair_stats) if r.pair_stats else 0       # (every library's launch meets the same contigs)
-        if bad:
-            raise RuntimeError("pair span: %d closed gaps whose winning contig does not carry the pick the word states (per library: %s)"
-                               % (bad, [s["mismatches"] for s in r.pair_stats]))
-        raw = self.d_rec.cpu().numpy().reshape(len(p.libs), self.plane)[:, :p.n_gaps * B.FILL_PAIRS.itemsize]
-        r.pairs = np.frombuffer(np.ascontiguousarray(raw).tobytes(), dtype=B.FILL_PAIRS).reshape(len(p.libs), p.n_gaps)
+        bad = [s["mismatches"] for s in r.pair_stats]
+        self.check_mismatches(max(bad, default=0), " (per library: %s)" % bad)      # (every library's launch meets the same contigs)
+        r.pairs = self.records(len(p.libs))

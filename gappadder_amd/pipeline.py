@@ -40,6 +40,7 @@ import torch
 
 from . import _lib as B
 from . import extended_fill as EXT
+from . import fill_rounds as FR
 from . import pair_span as PSP
 from . import polish as POL
 from . import read_support as SUP
@@ -132,16 +133,10 @@ class Pipeline:
                          (second_round and not single_rank, "second_round runs on a single rank"),
                          (second_round and merge_in_step, "second_round with merge_in_step: the order of the merge and the second round is not settled"),
                          (second_round and k_round2 is None, "second_round needs a k in 16..64 among k_pairs"),
-                         (read_support and not single_rank, "read_support runs on a single rank"),
-                         (read_support and second_round, "read_support with second_round: the second round assembles a pool of its own, "
-                                                         "not the step's, and the support is defined on the step's pool"),
+                         *FR.refusals("read_support", read_support, single_rank, second_round),
                          (read_support and support_k is None and k_round2 is None, "read_support needs support_k, or a k in 16..64 among k_pairs"),
-                         (polish and not single_rank, "polish runs on a single rank"),
-                         (polish and second_round, "polish with second_round: the second round assembles a pool of its own, not the step's, "
-                                                   "and the polish is defined on the step's pool"),
-                         (pair_span and not single_rank, "pair_span runs on a single rank"),
-                         (pair_span and second_round, "pair_span with second_round: the second round assembles a pool of its own, not the step's, "
-                                                      "and the pairs are looked up in the step's pools"),
+                         *FR.refusals("polish", polish, single_rank, second_round),
+                         *FR.refusals("pair_span", pair_span, single_rank, second_round),
                          (extended_fill and not single_rank, "extended_fill runs on a single rank"),
                          (extended_fill and len(k_pairs) > B.EXT_MAX_PAIRS, "extended_fill: at most %d (k, kv) pairs" % B.EXT_MAX_PAIRS)):
             if bad:
@@ -155,6 +150,7 @@ class Pipeline:
         self.support = SUP.ReadSupport(self, k_round2 if support_k is None else support_k) if read_support else None
         self.polish = POL.FillPolish(self, polish_seed, polish_max_mismatch, polish_min_overlap, polish_min_votes, read_len) if polish else None
         self.pairs = PSP.PairSpan(self, pair_seed, pair_max_mismatch, pair_min_overlap, pair_z, read_len) if pair_span else None
+        self.after_pick = [r for r in (self.support, self.polish, self.pairs) if r is not None]      # (the order they run in)
         self.gf, self.lib, self.h = gf, B.lib(), gf.handle
         self.n_gaps, self.L, self.kk = int(n_gaps), int(read_len), [(int(a), int(b)) for a, b in k_pairs]
         self.rb = self.lib.gf_packed_read_bytes(self.L)
@@ -511,12 +507,8 @@ class Pipeline:
             self.rescue.prepare()
         if self.ext is not None:        # (after the rounds: either may have grown the contig list its buffer is sized by)
             self.ext.prepare()
-        if self.support is not None:
-            self.support.prepare()
-        if self.polish is not None:     # (after the rounds: its base buffer takes what the contig bases take)
-            self.polish.prepare()
-        if self.pairs is not None:
-            self.pairs.prepare()
+        for rnd in self.after_pick:     # (after the rounds: the polish's base buffer takes what the contig bases take)
+            rnd.prepare()
         if self.tag_ahead:          # the first step's tagger pass (untimed, like a warm-up step's)
             assert all(lb.second_stream for lb in self.libs), "tag_ahead needs DeviceLibrary(tag_ctx=...)"
             self._on_stream(lambda: [self.tagger(lb) for lb in self.libs])
@@ -643,12 +635,10 @@ class Pipeline:
             self.rescue.enqueue()
         if self.ext is not None:
             self.ext.enqueue()
-        if self.support is not None:      # (neither the rescue's nor the extension's launches change d_best after the rescue's pick)
-            self.support.enqueue(d_nmask)
-        if self.polish is not None:       # (reads the step's contigs and picks, writes buffers of its own)
-            self.polish.enqueue(d_nmask)
-        if self.pairs is not None:        # (per library, on the libraries' own pools, ids and masks)
-            self.pairs.enqueue()
+        # (neither the rescue's nor the extension's launches change d_best after the rescue's pick; every round here reads the step's
+        # contigs and picks and writes buffers of its own; the pair span runs per library, on the libraries' own pools, ids and masks)
+        for rnd in self.after_pick:
+            rnd.enqueue(d_nmask)
 
     def _pick(self, a_long, a_short, first=None, own=None):
         """One pick in the Pipeline's anchor mode over the contigs from index *first on (a device address; None: all of them) of the step's
@@ -731,12 +721,8 @@ class Pipeline:
             self.round2.fetch(r)
         if self.ext is not None and self.kk:
             self.ext.fetch(r)
-        if self.support is not None and self.kk:
-            self.support.fetch(r)
-        if self.polish is not None and self.kk:
-            self.polish.fetch(r)
-        if self.pairs is not None and self.kk:
-            self.pairs.fetch(r)
+        for rnd in self.after_pick if self.kk else ():
+            rnd.fetch(r)
         if pools:
             r.pool_off = r.asm_off_t.cpu().numpy().astype(np.int64)
             r.pool_rows = r.asm_pool_t[:r.asm_rows_total * self.rb].cpu().numpy().reshape(-1, self.rb)

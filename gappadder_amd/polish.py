@@ -27,31 +27,18 @@ import numpy as np
 import torch
 
 from . import _lib as B
+from . import fill_rounds as FR
 from . import pipeline as P
 from . import read_support as SUP
+from .fill_rounds import MAX_CONTIG, _LUT
 
 SEED, MAX_MISMATCH, MIN_OVERLAP, MIN_VOTES = 16, 4, 48, 2
-MAX_CONTIG = B.PL_MAX_CONTIG
-_LUT = np.full(256, 4, dtype=np.uint8)
-for _i, _c in enumerate(b"ACGT"):
-    _LUT[_c] = _i
 
 
 def check_params(L, seed=SEED, max_mismatch=MAX_MISMATCH, min_overlap=MIN_OVERLAP, min_votes=MIN_VOTES):
     """The four parameters as integers; ValueError for a value out of range (module docstring; the ABI answers GF_E_UNSUPPORTED)."""
-    L, s, mm, mo, mv = int(L), int(seed), int(max_mismatch), int(min_overlap), int(min_votes)
-    if not 12 <= s <= 32:
-        raise ValueError("polish seed %r: 12..32" % (seed,))
-    if not 0 <= mm <= 15:
-        raise ValueError("polish max_mismatch %r: 0..15" % (max_mismatch,))
-    if not s <= mo <= L:
-        raise ValueError("polish min_overlap %r: at least the seed (%d), at most the read length (%d)" % (min_overlap, s, L))
-    if mv < 1:
-        raise ValueError("polish min_votes %r: at least 1" % (min_votes,))
-    if L // s <= mm:
-        raise ValueError("polish seed %d with max_mismatch %d: a read of %d bases has %d seeds, and more seeds than mismatches are needed"
-                         % (s, mm, L, L // s))
-    return s, mm, mo, mv
+    mv = int(min_votes)
+    return FR.check_placement("polish", L, seed, max_mismatch, min_overlap, [(mv < 1, "min_votes %r: at least 1" % (min_votes,))]) + (mv,)
 
 
 def _reads(reads):
@@ -104,12 +91,11 @@ def polish_host(reads, contig, b0, b1, seed=SEED, max_mismatch=MAX_MISMATCH, min
     b0, b1 = int(b0), max(int(b0), int(b1))
     rec = np.zeros((), dtype=B.FILL_POLISH)
     rec["len"], rec["n_cols"] = len(contig), b1 - b0
-    raw = np.frombuffer(contig.encode(), dtype=np.uint8)
-    flag = B.PL_F_LONG if len(contig) > MAX_CONTIG else B.PL_F_NON_ACGT if (_LUT[raw] > 3).any() else 0
+    flag = FR.skip_flag(contig, B.PL_F_LONG, B.PL_F_NON_ACGT)
     if flag:
         rec["flags"] = flag
         return (contig, rec, []) if detail else (contig, rec)
-    cc = _LUT[raw]
+    cc = _LUT[np.frombuffer(contig.encode(), dtype=np.uint8)]
     where = placements((codes, valid), contig, s, mm_max, mo) if len(codes) else []
     votes = np.zeros((len(cc), 4), dtype=np.int64)
     for r, w in enumerate(where):
@@ -142,16 +128,11 @@ def polish_of_results(res, flanks, L, seed=SEED, max_mismatch=MAX_MISMATCH, min_
     check_params(L, seed, max_mismatch, min_overlap, min_votes)
     out, texts = np.zeros(len(res.best), dtype=B.FILL_POLISH), {}
     stats = dict.fromkeys(STAT_KEYS, 0)
-    for g in np.nonzero(res.best)[0]:
-        ci = P.decode_best(res.best[g])[2]
-        ok = ci < len(res.contigs) and int(res.contigs[ci]["gap"]) == g
-        contig = P.contig_text(res, ci) if ok else ""
-        body = SUP.locate(res.best[g], contig, flanks[g], res.ctg_pick[ci] if res.ctg_pick is not None else None) if ok else None
+    for g, contig, body in FR.closed_fills(res, flanks):
         if body is None:
             stats["mismatches"] += 1
             continue
-        r0, r1 = int(res.pool_off[g]), int(res.pool_off[g + 1])
-        reads = SUP.codes_of_rows(res.pool_rows[r0:r1], L, None if nmask is None else nmask[r0:r1])
+        reads = FR.pool_reads(res.pool_off, res.pool_rows, g, L, nmask)[2]
         texts[int(g)], out[g] = polish_host(reads, contig, body[0], body[1], seed, max_mismatch, min_overlap, min_votes)
         f = int(out[g]["flags"])
         stats["skipped_long"] += bool(f & B.PL_F_LONG)
@@ -173,11 +154,12 @@ def stats_of(words):
             "overflow": int(st[B.PL_OVERFLOW])}
 
 
-class FillPolish:
+class FillPolish(FR.FillRound):
+    WHAT, RECORD = "polish", B.FILL_POLISH
+
     def __init__(self, pipe, seed=SEED, max_mismatch=MAX_MISMATCH, min_overlap=MIN_OVERLAP, min_votes=MIN_VOTES, read_len=None):
-        self.p = pipe
+        super().__init__(pipe)
         self.params = check_params(read_len, seed, max_mismatch, min_overlap, min_votes)
-        self.d_rec = None
 
     def prepare(self):
         """The base buffer takes what the contig bases take: no set of winners is longer."""
@@ -187,25 +169,18 @@ class FillPolish:
         self.d_bases = p._u8(max(1, self.base_cap))
         self.d_stats = torch.zeros(B.PL_WORDS, dtype=torch.int32, device=p.dev)
 
-    def enqueue(self, d_nmask=None):
-        """After the last pick of the step (and the read-support round), on the pool the step assembled and the N masks assemble() was given."""
+    def _launch(self, d_nmask):
+        """On the pool the step assembled (after the read-support round)."""
         p = self.p
-        if self.d_rec is None:        # a sizing run of one of the rounds: nobody reads its records
-            return
-        a_long, a_short = p.anchor_pair if not p.per_contig else (0, 0)
-        p._chk(p.lib.gf_fill_polish_dev(p.h, p.asm_ptr, d_nmask, p.asm_off, p.asm_rows, p.L, p.d_ctg.data_ptr(), p.ap, p.contig_cap,
-                                        p.d_seq.data_ptr(), p.d_best.data_ptr(), p.d_ctg_pick.data_ptr() if p.per_contig else None,
-                                        a_long, a_short, *self.params, self.d_rec.data_ptr(), self.d_bases.data_ptr(), self.base_cap,
-                                        self.d_stats.data_ptr()), "gf_fill_polish_dev")
+        p._chk(p.lib.gf_fill_polish_dev(p.h, p.asm_ptr, d_nmask, p.asm_off, p.asm_rows, p.L, *self.shared_args(), *self.params,
+                                        self.d_rec.data_ptr(), self.d_bases.data_ptr(), self.base_cap, self.d_stats.data_ptr()), "gf_fill_polish_dev")
 
     def fetch(self, r):
-        p = self.p
         r.polish_stats = stats_of(self.d_stats.cpu().numpy())
-        if r.polish_stats["mismatches"]:
-            raise RuntimeError("polish: %d closed gaps whose winning contig does not carry the pick the word states" % r.polish_stats["mismatches"])
+        self.check_mismatches(r.polish_stats["mismatches"])
         if r.polish_stats["overflow"] or r.polish_stats["bases"] > self.base_cap:
             raise RuntimeError("polish: %d polished bases (cap %d)" % (r.polish_stats["bases"], self.base_cap))
-        r.polish = np.frombuffer(self.d_rec[:p.n_gaps * B.FILL_POLISH.itemsize].cpu().numpy().tobytes(), dtype=B.FILL_POLISH)
+        r.polish = self.records()[0]
         r.polish_bases = self.d_bases[:r.polish_stats["bases"]].cpu().numpy().tobytes()
 
 

@@ -21,13 +21,12 @@ import numpy as np
 import torch
 
 from . import _lib as B
+from . import fill_rounds as FR
 from . import pipeline as P
+from .fill_rounds import _LUT
 from .pick_contigs import revcomp
 
 K_MIN, K_MAX = 16, 64
-_LUT = np.full(256, 4, dtype=np.uint8)
-for _i, _c in enumerate(b"ACGT"):
-    _LUT[_c] = _i
 
 
 def check_k(k):
@@ -174,47 +173,37 @@ def support_of_results(res, flanks, L, k, min_count=2, nmask=None):
     """The twin over a whole step: (records, stats) from fetch(pools=True)'s pools and the fetched contigs and picks."""
     out = np.zeros(len(res.best), dtype=B.FILL_SUPPORT)
     stats = {"gaps": 0, "mismatches": 0, "windows": 0}
-    for g in np.nonzero(res.best)[0]:
-        ci = P.decode_best(res.best[g])[2]
-        ok = ci < len(res.contigs) and int(res.contigs[ci]["gap"]) == g
-        contig = P.contig_text(res, ci) if ok else ""
-        body = locate(res.best[g], contig, flanks[g], res.ctg_pick[ci] if res.ctg_pick is not None else None) if ok else None
+    for g, contig, body in FR.closed_fills(res, flanks):
         if body is None:
             stats["mismatches"] += 1
             continue
-        r0, r1 = int(res.pool_off[g]), int(res.pool_off[g + 1])
-        reads = codes_of_rows(res.pool_rows[r0:r1], L, None if nmask is None else nmask[r0:r1])
+        reads = FR.pool_reads(res.pool_off, res.pool_rows, g, L, nmask)[2]
         out[g] = support_host(reads, contig, body[0], body[1], k, min_count)
         stats["gaps"] += 1
         stats["windows"] += int(out[g]["n_windows"])
     return out, stats
 
 
-class ReadSupport:
+class ReadSupport(FR.FillRound):
+    WHAT, RECORD = "read support", B.FILL_SUPPORT
+
     def __init__(self, pipe, k):
-        self.p, self.k = pipe, check_k(k)
-        self.d_sup = None
+        super().__init__(pipe)
+        self.k = check_k(k)
 
     def prepare(self):
         p = self.p
-        self.d_sup = p._u8(max(1, p.n_gaps) * B.FILL_SUPPORT.itemsize)
+        self.d_rec = p._u8(max(1, p.n_gaps) * B.FILL_SUPPORT.itemsize)
         self.d_stats = torch.zeros(B.FS_WORDS, dtype=torch.int32, device=p.dev)
 
-    def enqueue(self, d_nmask=None):
-        """After the last pick of the step, on the pool the step assembled (and the N masks assemble() was given)."""
+    def _launch(self, d_nmask):
+        """On the pool the step assembled."""
         p = self.p
-        if self.d_sup is None:        # a sizing run of one of the rounds: nobody reads its records
-            return
-        a_long, a_short = p.anchor_pair if not p.per_contig else (0, 0)
-        p._chk(p.lib.gf_fill_support_dev(p.h, p.asm_ptr, d_nmask, p.asm_off, p.asm_rows, p.L, p.d_ctg.data_ptr(), p.ap, p.contig_cap,
-                                         p.d_seq.data_ptr(), p.d_best.data_ptr(), p.d_ctg_pick.data_ptr() if p.per_contig else None,
-                                         a_long, a_short, self.k, p.min_count, self.d_sup.data_ptr(), self.d_stats.data_ptr()),
-               "gf_fill_support_dev")
+        p._chk(p.lib.gf_fill_support_dev(p.h, p.asm_ptr, d_nmask, p.asm_off, p.asm_rows, p.L, *self.shared_args(), self.k, p.min_count,
+                                         self.d_rec.data_ptr(), self.d_stats.data_ptr()), "gf_fill_support_dev")
 
     def fetch(self, r):
-        p = self.p
         st = self.d_stats.cpu().numpy().view(np.uint32)
         r.support_stats = {"gaps": int(st[B.FS_GAPS]), "mismatches": int(st[B.FS_MISMATCH]), "windows": P.counter_u64(st, B.FS_WINDOWS), "k": self.k}
-        if r.support_stats["mismatches"]:
-            raise RuntimeError("read support: %d closed gaps whose winning contig does not carry the pick the word states" % r.support_stats["mismatches"])
-        r.support = np.frombuffer(self.d_sup[:p.n_gaps * B.FILL_SUPPORT.itemsize].cpu().numpy().tobytes(), dtype=B.FILL_SUPPORT)
+        self.check_mismatches(r.support_stats["mismatches"])
+        r.support = self.records()[0]

@@ -14,12 +14,10 @@ One JSON object on stdout, and in --out when given.
     python tools/pair_span.py --config C2RM --merge-in-step --mp-reads N [--anchor-mode exact|align|gapped]
 """
 import argparse
-import json
-import time
 
 import numpy as np
 
-from preset_setup import preset_setup
+from preset_setup import emit, off_and_on, round_arguments, round_ms, round_setup, spread
 
 
 def _dist(v):
@@ -31,31 +29,10 @@ def _dist(v):
             "mean": round(float(v.mean()), 3)}
 
 
-def _spread(ms):
-    return {"ms": [round(x, 3) for x in ms], "median": round(float(np.median(ms)), 3), "min": round(min(ms), 3), "max": round(max(ms), 3)}
-
-
 def _low(rec, is_mean, is_sd):
     """Does the record's mean spanning insert lie more than 3 * is_sd / sqrt(n_span) below is_mean?"""
     n = int(rec["n_span"])
     return bool(n) and int(rec["span_insert_sum"]) / n < is_mean - 3.0 * is_sd / np.sqrt(n)
-
-
-def _round_ms(pipe, gf, enqueue, kernel, steps, reps):
-    import torch
-    out = []
-    gf.timing(True)
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(steps):
-            enqueue()
-        e1.record()
-        pipe.barrier()
-        out.append(e0.elapsed_time(e1) / steps)
-    t_ms, n = gf.kernel_time(kernel)
-    gf.timing(False)
-    return _spread(out), round(t_ms / max(1, n), 4)
 
 
 def _delete(pipe, res, flanks, n_cut, l):
@@ -88,11 +65,10 @@ def _delete(pipe, res, flanks, n_cut, l):
     d_rec = torch.zeros(max(1, pipe.n_gaps) * B.FILL_PAIRS.itemsize, dtype=torch.uint8, device=pipe.dev)
     d_st = torch.zeros(B.PS_WORDS, dtype=torch.int32, device=pipe.dev)
     lb, ps = pipe.libs[l], pipe.pairs
-    a_long, a_short = pipe.anchor_pair if not pipe.per_contig else (0, 0)
     torch.cuda.synchronize()
     pipe._chk(pipe.lib.gf_fill_pairs_dev(pipe.h, pipe.pool_ptr[l], ps.masks_of(l), lb.d_pool_off.data_ptr(), lb.d_ids.data_ptr(), pipe.lib_cap, pipe.L,
                                          d_ctg.data_ptr(), d_n.data_ptr(), len(ctg), d_seq.data_ptr(), d_best.data_ptr(),
-                                         d_pick.data_ptr() if d_pick is not None else None, a_long, a_short, *ps.params[:3], lb.is_mean, lb.is_sd,
+                                         d_pick.data_ptr() if d_pick is not None else None, *ps.shared_args()[6:], *ps.params[:3], lb.is_mean, lb.is_sd,
                                          ps.params[3], ps.d_scratch.data_ptr(), d_rec.data_ptr(), d_st.data_ptr()), "gf_fill_pairs_dev")
     pipe.barrier()
     recs = np.frombuffer(d_rec[:pipe.n_gaps * B.FILL_PAIRS.itemsize].cpu().numpy().tobytes(), dtype=B.FILL_PAIRS)
@@ -102,49 +78,22 @@ def _delete(pipe, res, flanks, n_cut, l):
 
 
 def main():
-    import bench
     from gappadder_amd import _lib as B
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="C4", choices=sorted(bench.PRESETS))
-    ap.add_argument("--steps", type=int, default=3, help="steps per timed window")
-    ap.add_argument("--reps", type=int, default=3, help="timed windows per setting, off and on in turn")
-    ap.add_argument("--reads", type=int, default=0, help="read records of the short-insert library (default: the preset's)")
-    ap.add_argument("--mp-reads", type=int, default=0, help="read records of the preset's mate-pair library (default: none)")
-    ap.add_argument("--gap-len", type=int, default=0)
-    ap.add_argument("--anchor-mode", default="exact")
-    ap.add_argument("--asm-tiebreak", default="counts", choices=["counts", "none"])
-    ap.add_argument("--merge-in-step", action="store_true")
-    ap.add_argument("--seed", type=int, default=16)
-    ap.add_argument("--max-mismatch", type=int, default=4)
-    ap.add_argument("--min-overlap", type=int, default=48)
+    round_arguments(ap, reps=True, placing=True)
     ap.add_argument("--z", type=int, default=3)
     ap.add_argument("--delete", type=int, action="append", default=[], help="bases cut from every tenth closed fill (may be given more than once)")
-    ap.add_argument("--out", default="")
     args = ap.parse_args()
-    s = preset_setup(args.config, reads=args.reads, gap_len=args.gap_len, mp_reads=args.mp_reads)
-    s.gf.set_option("asm_tiebreak", 0 if args.asm_tiebreak == "none" else 1)
-    flags = dict(anchor_mode=args.anchor_mode, merge_in_step=args.merge_in_step)
+    s, flags, out = round_setup(args)
     prm = dict(pair_seed=args.seed, pair_max_mismatch=args.max_mismatch, pair_min_overlap=args.min_overlap, pair_z=args.z)
-    out = {"config": args.config, "gaps": len(s.gaps), "gap_len": s.gap_len, "reads": s.reads, "mp_reads": args.mp_reads,
-           "asm_tiebreak": args.asm_tiebreak, "steps": args.steps, **flags, **prm}
-    pipes = {"off": s.pipeline(**flags), "on": s.pipeline(pair_span=True, **prm, **flags)}
-    for pipe in pipes.values():
-        pipe.prepare()
-        pipe.step(1)
-        pipe.barrier()
-    ms = {"off": [], "on": []}
-    for _ in range(args.reps):
-        for name, pipe in pipes.items():
-            t0 = time.perf_counter()
-            pipe.step(args.steps)
-            pipe.barrier()
-            ms[name].append((time.perf_counter() - t0) * 1e3 / args.steps)
-    out["ms_per_step_off"], out["ms_per_step_on"] = _spread(ms["off"]), _spread(ms["on"])
-    pipe = pipes["on"]
+    out.update(steps=args.steps, **flags, **prm)
+    pipe, ms = off_and_on(s, flags, dict(pair_span=True, **prm), args.steps, args.reps)
+    out.update(ms)
     res = pipe.fetch()
     libs = [(lb.name, lb.is_mean, lb.is_sd) for lb in pipe.libs]
     out["closed"], out["libraries"], out["pair_stats"] = int((res.best != 0).sum()), libs, res.pair_stats
-    out["round_ms"], out["round_kernel_ms_per_launch"] = _round_ms(pipe, s.gf, pipe.pairs.enqueue, B.KERNEL_PAIRS, args.steps, args.reps)
+    ms, out["round_kernel_ms_per_launch"] = round_ms(pipe, s.gf, pipe.pairs.enqueue, B.KERNEL_PAIRS, args.steps, args.reps)
+    out["round_ms"] = spread(ms)
     picked = pipe.picked_sequences(res)
     groups = {"correct": [], "wrong": []}
     for g in picked:
@@ -176,11 +125,7 @@ def main():
                 "untouched_with_spanning_pairs": int(sum(int(recs[g]["n_span"]) > 0 for g in rest)),
                 "untouched_low": int(sum(_low(recs[g], is_mean, is_sd) for g in rest)), "untouched_records_equal_the_steps": bool(same),
                 "edited_span_mean_minus_is": _dist([int(recs[g]["span_insert_sum"]) // int(recs[g]["n_span"]) - is_mean for g in edited if int(recs[g]["n_span"])])}
-    text = json.dumps(out)
-    print(text, flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -8,12 +8,10 @@ the distributions of `n_changed` and `reads_ambiguous` per transition group.  On
     python tools/polish_fills.py --config C2RM --merge-in-step [--mp-reads N] [--anchor-mode exact|align|gapped]
 """
 import argparse
-import json
-import time
 
 import numpy as np
 
-from preset_setup import preset_setup
+from preset_setup import emit, off_and_on, round_arguments, round_ms, round_setup
 
 
 def _dist(v):
@@ -24,64 +22,22 @@ def _dist(v):
     return {"n": int(len(v)), "zero": int((v == 0).sum()), "median": float(q[0]), "p95": float(q[1]), "max": int(v.max()), "mean": round(float(v.mean()), 3)}
 
 
-def _spread(ms):
-    return {"ms": [round(x, 3) for x in ms], "median": round(float(np.median(ms)), 3), "min": round(min(ms), 3), "max": round(max(ms), 3)}
-
-
 def main():
-    import bench
-    import torch
     from gappadder_amd import _lib as B
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="C4", choices=sorted(bench.PRESETS))
-    ap.add_argument("--steps", type=int, default=3, help="steps per timed window")
-    ap.add_argument("--reps", type=int, default=3, help="timed windows per setting, off and on in turn")
-    ap.add_argument("--reads", type=int, default=0, help="read records of the short-insert library (default: the preset's)")
-    ap.add_argument("--mp-reads", type=int, default=0, help="read records of the preset's mate-pair library (default: none)")
-    ap.add_argument("--gap-len", type=int, default=0)
-    ap.add_argument("--anchor-mode", default="exact")
-    ap.add_argument("--asm-tiebreak", default="counts", choices=["counts", "none"])
-    ap.add_argument("--merge-in-step", action="store_true")
-    ap.add_argument("--seed", type=int, default=16)
-    ap.add_argument("--max-mismatch", type=int, default=4)
-    ap.add_argument("--min-overlap", type=int, default=48)
+    round_arguments(ap, reps=True, placing=True)
     ap.add_argument("--min-votes", type=int, default=2)
-    ap.add_argument("--out", default="")
     args = ap.parse_args()
-    s = preset_setup(args.config, reads=args.reads, gap_len=args.gap_len, mp_reads=args.mp_reads)
-    s.gf.set_option("asm_tiebreak", 0 if args.asm_tiebreak == "none" else 1)
-    flags = dict(anchor_mode=args.anchor_mode, merge_in_step=args.merge_in_step)
+    s, flags, out = round_setup(args)
     prm = dict(polish_seed=args.seed, polish_max_mismatch=args.max_mismatch, polish_min_overlap=args.min_overlap, polish_min_votes=args.min_votes)
-    out = {"config": args.config, "gaps": len(s.gaps), "gap_len": s.gap_len, "reads": s.reads, "mp_reads": args.mp_reads,
-           "asm_tiebreak": args.asm_tiebreak, "steps": args.steps, **flags, **prm}
-    pipes = {"off": s.pipeline(**flags), "on": s.pipeline(polish=True, **prm, **flags)}
-    for pipe in pipes.values():
-        pipe.prepare()
-        pipe.step(1)
-        pipe.barrier()
-    ms = {"off": [], "on": []}
-    for _ in range(args.reps):
-        for name, pipe in pipes.items():
-            t0 = time.perf_counter()
-            pipe.step(args.steps)
-            pipe.barrier()
-            ms[name].append((time.perf_counter() - t0) * 1e3 / args.steps)
-    out["ms_per_step_off"], out["ms_per_step_on"] = _spread(ms["off"]), _spread(ms["on"])
-    pipe = pipes["on"]
+    out.update(steps=args.steps, **flags, **prm)
+    pipe, ms = off_and_on(s, flags, dict(polish=True, **prm), args.steps, args.reps)
+    out.update(ms)
     res = pipe.fetch()
     pool_off = res.asm_off_t.cpu().numpy().astype(np.int64)
     out["closed"], out["polish_stats"] = int((res.best != 0).sum()), res.polish_stats
-    s.gf.timing(True)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(args.steps):
-        pipe.polish.enqueue()
-    e1.record()
-    pipe.barrier()
-    out["round_ms"] = round(e0.elapsed_time(e1) / args.steps, 4)
-    t_ms, n = s.gf.kernel_time(B.KERNEL_POLISH)
-    out["round_kernel_ms"] = round(t_ms / max(1, n), 4)
-    s.gf.timing(False)
+    ms, out["round_kernel_ms"] = round_ms(pipe, s.gf, pipe.polish.enqueue, B.KERNEL_POLISH, args.steps)
+    out["round_ms"] = round(ms[0], 4)
     before, after = pipe.picked_sequences(res), pipe.polished_sequences(res)
     groups = {"wrong_to_correct": [], "wrong_to_wrong": [], "correct_to_correct": [], "correct_to_wrong": []}
     for g in before:
@@ -98,11 +54,7 @@ def main():
     out["correct_to_wrong_gaps"] = [{"gap": int(g), "pool_rows": int(pool_off[g + 1] - pool_off[g]),
                                      **{f: int(pol[g][f]) for f in ("n_cols", "n_changed", "n_uncovered", "reads_placed", "reads_ambiguous")}}
                                     for g in groups["correct_to_wrong"]]
-    text = json.dumps(out)
-    print(text, flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    emit(out, args.out)
 
 
 if __name__ == "__main__":

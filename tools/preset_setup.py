@@ -1,5 +1,7 @@
 """What the per-feature scripts (second_round.py, rescue_round.py, extended_fill.py, anchor_modes.py) share: one bench preset as a GapFill
-with its gaps set and the preset's libraries synthesised on the device."""
+with its gaps set and the preset's libraries synthesised on the device; and what the scripts of the three after-pick rounds
+(read_support.py, polish_fills.py, pair_span.py) share on top: their options, the off / on timing, the round's own time, the output."""
+import json
 import os
 import sys
 import time
@@ -70,3 +72,82 @@ def release():
     import torch
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
+
+
+def round_arguments(ap, reps=False, placing=False):
+    """The options of a script of an after-pick round; reps: the off / on windows in turn; placing: the placement rule's as well."""
+    import bench
+    ap.add_argument("--config", default="C4", choices=sorted(bench.PRESETS))
+    ap.add_argument("--steps", type=int, default=3, help="steps per timed window")
+    if reps:
+        ap.add_argument("--reps", type=int, default=3, help="timed windows per setting, off and on in turn")
+    ap.add_argument("--reads", type=int, default=0, help="read records of the short-insert library (default: the preset's)")
+    ap.add_argument("--mp-reads", type=int, default=0, help="read records of the preset's mate-pair library (default: none)")
+    ap.add_argument("--gap-len", type=int, default=0)
+    ap.add_argument("--anchor-mode", default="exact")
+    ap.add_argument("--asm-tiebreak", default="counts", choices=["counts", "none"])
+    ap.add_argument("--merge-in-step", action="store_true")
+    ap.add_argument("--out", default="")
+    if placing:
+        ap.add_argument("--seed", type=int, default=16)
+        ap.add_argument("--max-mismatch", type=int, default=4)
+        ap.add_argument("--min-overlap", type=int, default=48)
+
+
+def round_setup(args, **flags):
+    """(preset_setup's namespace, the Pipeline flags of both settings, the head of the output object) for round_arguments' options."""
+    s = preset_setup(args.config, reads=args.reads, gap_len=args.gap_len, mp_reads=args.mp_reads)
+    s.gf.set_option("asm_tiebreak", 0 if args.asm_tiebreak == "none" else 1)
+    flags = dict(dict(anchor_mode=args.anchor_mode, merge_in_step=args.merge_in_step), **flags)
+    return s, flags, {"config": args.config, "gaps": len(s.gaps), "gap_len": s.gap_len, "reads": s.reads, "mp_reads": args.mp_reads,
+                      "asm_tiebreak": args.asm_tiebreak}
+
+
+def spread(ms):
+    import numpy as np
+    return {"ms": [round(x, 3) for x in ms], "median": round(float(np.median(ms)), 3), "min": round(min(ms), 3), "max": round(max(ms), 3)}
+
+
+def off_and_on(s, flags, on, steps, reps):
+    """The step with the round off and on (Pipeline keywords `on`): two prepared pipelines, a warm-up step each, then `reps` windows of
+    `steps` steps each, in turn.  Returns (the pipeline with the round on, {"ms_per_step_off": spread, "ms_per_step_on": spread})."""
+    pipes = {"off": s.pipeline(**flags), "on": s.pipeline(**on, **flags)}
+    for pipe in pipes.values():
+        pipe.prepare()
+        pipe.step(1)
+        pipe.barrier()
+    ms = {"off": [], "on": []}
+    for _ in range(reps):
+        for name, pipe in pipes.items():
+            t0 = time.perf_counter()
+            pipe.step(steps)
+            pipe.barrier()
+            ms[name].append((time.perf_counter() - t0) * 1e3 / steps)
+    return pipes["on"], {"ms_per_step_" + name: spread(v) for name, v in ms.items()}
+
+
+def round_ms(pipe, gf, enqueue, kernel, steps, reps=1):
+    """The round's own time: its launches repeated on the step's results — `reps` windows of `steps` calls, milliseconds per call — and
+    the library's launch timer for `kernel`, milliseconds per launch."""
+    import torch
+    out = []
+    gf.timing(True)
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(steps):
+            enqueue()
+        e1.record()
+        pipe.barrier()
+        out.append(e0.elapsed_time(e1) / steps)
+    t_ms, n = gf.kernel_time(kernel)
+    gf.timing(False)
+    return out, round(t_ms / max(1, n), 4)
+
+
+def emit(out, path):
+    text = json.dumps(out)
+    print(text, flush=True)
+    if path:
+        with open(path, "w") as f:
+            f.write(text + "\n")

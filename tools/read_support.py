@@ -7,11 +7,10 @@ One JSON object on stdout, and in --out when given.
     python tools/read_support.py --config C2RM --merge-in-step [--mp-reads N] [--support-k K] [--anchor-mode exact|align|gapped]
 """
 import argparse
-import json
 
 import numpy as np
 
-from preset_setup import preset_setup, release, timed_steps
+from preset_setup import emit, release, round_arguments, round_ms, round_setup, timed_steps
 
 
 def _dist(v):
@@ -24,27 +23,15 @@ def _dist(v):
 
 
 def main():
-    import bench
-    import torch
     from gappadder_amd import _lib as B
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="C4", choices=sorted(bench.PRESETS))
-    ap.add_argument("--steps", type=int, default=3)
-    ap.add_argument("--reads", type=int, default=0, help="read records of the short-insert library (default: the preset's)")
-    ap.add_argument("--mp-reads", type=int, default=0, help="read records of the preset's mate-pair library (default: none)")
-    ap.add_argument("--gap-len", type=int, default=0)
-    ap.add_argument("--anchor-mode", default="exact")
-    ap.add_argument("--asm-tiebreak", default="counts", choices=["counts", "none"])
-    ap.add_argument("--merge-in-step", action="store_true")
+    round_arguments(ap)
     ap.add_argument("--rescue-round", action="store_true")
     ap.add_argument("--support-k", type=int, default=0)
-    ap.add_argument("--out", default="")
     args = ap.parse_args()
-    s = preset_setup(args.config, reads=args.reads, gap_len=args.gap_len, mp_reads=args.mp_reads)
-    s.gf.set_option("asm_tiebreak", 0 if args.asm_tiebreak == "none" else 1)
-    flags = dict(anchor_mode=args.anchor_mode, merge_in_step=args.merge_in_step or args.rescue_round, rescue_round=args.rescue_round)
-    out = {"config": args.config, "gaps": len(s.gaps), "gap_len": s.gap_len, "reads": s.reads, "mp_reads": args.mp_reads,
-           "asm_tiebreak": args.asm_tiebreak, **flags}
+    s, flags, out = round_setup(args, rescue_round=args.rescue_round)
+    flags["merge_in_step"] = args.merge_in_step or args.rescue_round
+    out.update(flags)
     pipe = s.pipeline(**flags)
     out["ms_per_step_off"] = round(timed_steps(pipe, args.steps), 3)
     del pipe
@@ -53,17 +40,8 @@ def main():
     out["ms_per_step_on"] = round(timed_steps(pipe, args.steps), 3)
     res = pipe.fetch()
     out["support_k"], out["closed"], out["windows"] = pipe.support.k, int((res.best != 0).sum()), res.support_stats["windows"]
-    s.gf.timing(True)
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(args.steps):
-        pipe.support.enqueue()
-    e1.record()
-    pipe.barrier()
-    out["round_ms"] = round(e0.elapsed_time(e1) / args.steps, 4)
-    ms, n = s.gf.kernel_time(B.KERNEL_SUPPORT)
-    out["round_kernel_ms"] = round(ms / max(1, n), 4)
-    s.gf.timing(False)
+    ms, out["round_kernel_ms"] = round_ms(pipe, s.gf, pipe.support.enqueue, B.KERNEL_SUPPORT, args.steps)
+    out["round_ms"] = round(ms[0], 4)
     seqs = pipe.picked_sequences(res)
     groups = {"correct": [], "wrong": []}
     for g, (_, body, _) in seqs.items():
@@ -79,11 +57,7 @@ def main():
                       "n_below>0": [int((sup["n_below"][w] > 0).sum()), int((sup["n_below"][c] > 0).sum())],
                       "zero_run>=k": [int((sup["zero_run"][w] >= pipe.support.k).sum()), int((sup["zero_run"][c] >= pipe.support.k).sum())]}
     out["flagged_columns"] = ["of the wrong fills", "of the correct fills"]
-    text = json.dumps(out)
-    print(text, flush=True)
-    if args.out:
-        with open(args.out, "w") as f:
-            f.write(text + "\n")
+    emit(out, args.out)
 
 
 if __name__ == "__main__":
