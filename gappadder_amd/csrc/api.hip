@@ -45,33 +45,28 @@ void zero_regions(gf_ctx* ctx, const ZeroList& z) {
 // the one setup of a launch over the closed fills (fill_round.hpp: order of the answers, *blocks)
 int fill_round_setup(gf_ctx* ctx, const FillRoundIn& in, int own_rc, uint32_t stats_words, uint32_t wgs_per_cu, FillRoundArgs* R, size_t* blocks) {
     *blocks = 0;
-    if (!ctx || !in.d_pool_off || (in.pool_rows && !in.d_pool_packed) || !in.d_contigs || !in.d_n_contigs || !in.d_seq || !in.d_gap_best ||
-        !in.d_records || !in.d_stats || in.read_len < 1 || in.read_len > 1000 || in.contig_cap > 0x7FFFFFFFull)
-        return GF_E_INVAL;
-    if (!in.d_ctg_pick_or_null && (in.anchor_long < 8 || in.anchor_long > FB_ANCHOR_MAX ||
-                                   (in.anchor_short && (in.anchor_short < 8 || in.anchor_short >= in.anchor_long))))
-        return GF_E_INVAL;
-    if (own_rc) return own_rc;
-    const size_t ng = ctx->gaps.size();
-    if (ctx->flank_left.size() != ng || ctx->flank_right.size() != ng) return GF_E_STATE;
+    const bool shared_ok = in.d_pool_off && (!in.pool_rows || in.d_pool_packed) && in.d_gap_best && in.d_records && in.d_stats && in.read_len >= 1 &&
+                           in.read_len <= 1000 &&
+                           (in.d_ctg_pick_or_null || (in.anchor_long >= 8 && in.anchor_long <= ANCHOR_MAX &&
+                                                      (!in.anchor_short || (in.anchor_short >= 8 && in.anchor_short < in.anchor_long))));
+    ContigList list;
+    int rc = contig_list_view(ctx, in.d_contigs, in.d_n_contigs, in.contig_cap, CONTIG_CAP_WORD, in.d_seq, nullptr, shared_ok ? own_rc : GF_E_INVAL, &list);
+    if (rc) return rc;
     GF_HIP(ctx, hipSetDevice(ctx->device));
     GF_HIP(ctx, hipMemsetAsync(in.d_stats, 0, 4 * (size_t)stats_words, ctx->stream));
+    const size_t ng = ctx->gaps.size();
     if (!ng) return GF_OK;
     memset(R, 0, sizeof(*R));
-    int rc;
     if (!in.d_ctg_pick_or_null) {
-        if ((rc = anchor_table_for(ctx, in.anchor_long, &R->body.anc_l))) return rc;
-        if (in.anchor_short && (rc = anchor_table_for(ctx, in.anchor_short, &R->body.anc_s))) return rc;
+        if ((rc = anchor_table(ctx, in.anchor_long, &R->body.anc_l))) return rc;
+        if (in.anchor_short && (rc = anchor_table(ctx, in.anchor_short, &R->body.anc_s))) return rc;
         R->body.a_l = (uint32_t)in.anchor_long;
         R->body.a_s = (uint32_t)in.anchor_short;
     }
     R->pool_off = (const uint64_t*)in.d_pool_off;
     R->pool_rows = in.pool_rows;
-    R->body.contigs = (const gf_contig*)in.d_contigs;
-    R->body.seq = (const char*)in.d_seq;
+    R->body.list = list;
     R->body.ctg_pick = (const gf_ctg_pick*)in.d_ctg_pick_or_null;
-    R->n_contigs = (const uint32_t*)in.d_n_contigs;
-    R->contig_cap = (uint32_t)in.contig_cap;
     R->gap_best = (const unsigned long long*)in.d_gap_best;
     R->n_gaps = (uint32_t)ng;
     R->stats = (uint32_t*)in.d_stats;

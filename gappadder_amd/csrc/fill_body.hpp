@@ -1,15 +1,16 @@
 // fill_body.hpp — where the fill of a closed gap lies on its winning contig: the body [b0, b1) between the two flank hits of the pick
 // word (gappadder_amd/read_support.py: locate).  One rule for the rounds that look at a fill after the last pick of the
 // step — fill_support.hip, fill_polish.hip and fill_pairs.hip —, which reach it through fill_round.hpp's gap prologue (the latter two
-// also use fill_place.hpp, which uses the window-mask and base-code helpers below).  With a gf_ctg_pick per contig (the align and gapped modes) the body lies between the two
-// alignments; without it the exact anchors are re-located by pick.hip's rule at the anchor length the word carries, and a span that
-// is not the word's (unsaturated) span field is a mismatch.
+// also use fill_place.hpp, which uses the window-mask helper below).  With a gf_ctg_pick per contig (the align and gapped modes) the body lies between the two
+// alignments; without it the exact anchors (anchor.hpp) are re-located by pick.hip's rule at the anchor length the word carries, and a
+// span that does not match the word's span field (pick_word.hpp) is a mismatch.
 #pragma once
+#include "anchor.hpp"
+#include "contig_list.hpp"
 #include "gf_internal.hpp"
+#include "pick_word.hpp"
 
 namespace gf {
-
-constexpr int FB_ANCHOR_MAX = 32, FB_ANCHOR_ROW = 5 * FB_ANCHOR_MAX;          // the anchor rows of pick.hip (left, right, rc(left), rc(right), flags)
 
 // the assembly's window rule (assemble.hip window_masked): does the window [p, p + len) touch a masked base of the row?
 __device__ __forceinline__ bool row_window_masked(const uint32_t* row, uint32_t nmw, uint32_t p, uint32_t len) {
@@ -20,12 +21,8 @@ __device__ __forceinline__ bool row_window_masked(const uint32_t* row, uint32_t 
     return (len >= 64 ? a : a & ((1ull << len) - 1)) != 0;
 }
 
-// A, C, G, T -> 0..3; any other byte -> 4
-__device__ __forceinline__ uint32_t base_code4(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
-
 struct FillBodyArgs {
-    const gf_contig* contigs;
-    const char* seq;
+    ContigList list;             // (first: null)
     const gf_ctg_pick* ctg_pick; // or null: exact anchors
     const uint8_t* anc_l;        // exact: table of anchor length a_l, and of a_s (or null)
     const uint8_t* anc_s;
@@ -44,17 +41,17 @@ struct FillBody {
 template <uint32_t THREADS>
 __device__ __forceinline__ FillBody fill_body(const FillBodyArgs& A, uint32_t n, uint32_t g, unsigned long long word, uint32_t* s_loc) {
     const uint32_t t = threadIdx.x;
-    const uint32_t ci = 0x7FFFFFFFu - (uint32_t)((word >> 1) & 0x7FFFFFFFu), rev = (uint32_t)(word & 1u);
-    const uint32_t a = (uint32_t)(word >> 56), span1 = (uint32_t)((word >> 32) & 0xFFFFFFu);
+    const PickWord w = pick_word_unpack(word);
+    const uint32_t ci = w.contig, rev = w.reverse, a = w.level;
     bool ok = ci < n;
     gf_contig c;
     c.length = 0;
     c.seq_off = 0;
     if (ok) {
-        c = A.contigs[ci];
+        c = A.list.contigs[ci];
         ok = c.gap == g && c.length > 0;
     }
-    const char* s = A.seq + c.seq_off;
+    const char* s = A.list.seq + c.seq_off;
     int64_t b0 = 0, b1 = 0;
     if (ok && A.ctg_pick) {
         const gf_ctg_pick p = A.ctg_pick[ci];
@@ -65,15 +62,15 @@ __device__ __forceinline__ FillBody fill_body(const FillBodyArgs& A, uint32_t n,
         ok = ok && b1 <= (int64_t)c.length;
     } else if (ok) {
         const uint8_t* tab = a == A.a_l ? A.anc_l : (A.anc_s && a == A.a_s) ? A.anc_s : nullptr;
-        const uint8_t* row = tab ? tab + (uint64_t)g * FB_ANCHOR_ROW : nullptr;
-        ok = row && row[0] != 0 && row[FB_ANCHOR_MAX] != 0 && c.length >= a;
+        const uint8_t* row = tab ? anchor_rows(tab, g) : nullptr;
+        ok = row && anchor_rows_set(row) && c.length >= a;
         __syncthreads();                     // (the previous gap's readers of s_loc)
         if (t == 0) { s_loc[0] = EMPTY32; s_loc[1] = 0; }
         __syncthreads();
         if (ok) {
             // forward: leftmost left anchor, rightmost right anchor; reverse word: leftmost rc(right), rightmost rc(left)
-            const uint8_t* pa = row + (rev ? 3 : 0) * FB_ANCHOR_MAX;
-            const uint8_t* pb = row + (rev ? 2 : 1) * FB_ANCHOR_MAX;
+            const uint8_t* pa = anchor_row(row, rev ? ANC_RC_RIGHT : ANC_LEFT);
+            const uint8_t* pb = anchor_row(row, rev ? ANC_RC_LEFT : ANC_RIGHT);
             for (uint32_t p = t; p + a <= c.length; p += THREADS) {
                 uint32_t i = 0;
                 while (i < a && (uint8_t)s[p + i] == pa[i]) ++i;
@@ -89,17 +86,10 @@ __device__ __forceinline__ FillBody fill_body(const FillBodyArgs& A, uint32_t n,
         if (ok) {
             b0 = (int64_t)first + a;
             b1 = (int64_t)last1 - 1;
-            const uint64_t sp1 = (uint64_t)(b1 - b0) + 1;
-            ok = span1 < 0xFFFFFFu ? sp1 == span1 : sp1 >= span1;
+            ok = pick_word_span_matches((uint64_t)(b1 - b0) + 1, w.span1);
         }
     }
-    FillBody out;
-    out.ok = ok;
-    out.rev = rev;
-    out.c = c;
-    out.b0 = b0;
-    out.b1 = b1;
-    return out;
+    return {ok, rev, c, b0, b1};
 }
 
 }  // namespace gf

@@ -54,7 +54,7 @@ __global__ __launch_bounds__(PL_THREADS) void fill_pairs_kernel(PsParams P) {
     __shared__ unsigned long long s_sum, s_min;
     int32_t* s_diff = (int32_t*)s_idx;
     const uint32_t t = threadIdx.x, L = P.place.L;
-    const uint32_t n_list = fill_round_contigs(P.round);
+    const uint32_t n_list = contig_list_end(P.round.body.list);
     for (uint32_t g = blockIdx.x; g < P.round.n_gaps; g += gridDim.x) {
         gf_fill_pairs rec;
         memset(&rec, 0, sizeof(rec));
@@ -71,7 +71,7 @@ __global__ __launch_bounds__(PL_THREADS) void fill_pairs_kernel(PsParams P) {
             continue;
         }
         const uint32_t n = fg.fb.c.length;
-        const char* ctg = P.round.body.seq + fg.fb.c.seq_off;
+        const char* ctg = P.round.body.list.seq + fg.fb.c.seq_off;
         const uint32_t b0 = (uint32_t)fg.fb.b0, b1 = (uint32_t)fg.fb.b1;
         const FillRows rows = fill_gap_rows(P.round, g);
         const uint64_t r0 = rows.r0, r1 = rows.r1;

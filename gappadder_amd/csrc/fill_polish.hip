@@ -42,7 +42,7 @@ __global__ __launch_bounds__(PL_THREADS) void fill_polish_kernel(PlParams P) {
     __shared__ uint32_t s_acc[5];               // a byte that is no base, columns changed, columns uncovered, rows placed, rows ambiguous
     __shared__ unsigned long long s_off;
     const uint32_t t = threadIdx.x, L = P.place.L;
-    const uint32_t n_list = fill_round_contigs(P.round);
+    const uint32_t n_list = contig_list_end(P.round.body.list);
     for (uint32_t g = blockIdx.x; g < P.round.n_gaps; g += gridDim.x) {
         gf_fill_polish rec;
         rec.off = 0;
@@ -60,7 +60,7 @@ __global__ __launch_bounds__(PL_THREADS) void fill_polish_kernel(PlParams P) {
             continue;
         }
         const uint32_t n = fg.fb.c.length;
-        const char* ctg = P.round.body.seq + fg.fb.c.seq_off;
+        const char* ctg = P.round.body.list.seq + fg.fb.c.seq_off;
         const uint32_t b0 = (uint32_t)fg.fb.b0, b1 = (uint32_t)fg.fb.b1, n_cols = b1 - b0;
         if (t == 0) {
             s_acc[0] = s_acc[1] = s_acc[2] = s_acc[3] = s_acc[4] = 0;

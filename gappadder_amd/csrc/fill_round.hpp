@@ -10,11 +10,9 @@ namespace gf {
 
 // the arguments of a launch that every round reads the same way
 struct FillRoundArgs {
+    FillBodyArgs body;           // the contig list (body.list: the only copy), the picks
     const uint64_t* pool_off;    // the gaps' row ranges in the pool the round reads ...
     uint64_t pool_rows;          // ... and the rows of that pool array
-    FillBodyArgs body;           // the contig list, its bases (body.seq: the only copy), the picks
-    const uint32_t* n_contigs;
-    uint32_t contig_cap;
     const unsigned long long* gap_best;
     uint32_t n_gaps;
     uint32_t* stats;             // the round's own statistics words
@@ -42,10 +40,7 @@ __device__ __forceinline__ FillRows fill_gap_rows(const FillRoundArgs& R, uint32
     return out;
 }
 
-// the contigs of the list, as every consumer reads it
-__device__ __forceinline__ uint32_t fill_round_contigs(const FillRoundArgs& R) { return *R.n_contigs < R.contig_cap ? *R.n_contigs : R.contig_cap; }
-
-// Gap g of the launch, called by every thread of a workgroup of THREADS threads (n_list: fill_round_contigs; s_loc: two words of LDS);
+// Gap g of the launch, called by every thread of a workgroup of THREADS threads (n_list: contig_list_end(R.body.list); s_loc: two words of LDS);
 // every thread gets the same answer.  FILL_GAP_OPEN and FILL_GAP_MISMATCH: the caller writes its zero record (thread 0, no barrier)
 // and, for a mismatch, counts it in its MISMATCH word — in a branch per state: one merged branch spills more.  FILL_GAP_OK: returns behind a workgroup barrier, so the record thread 0
 // wrote for the workgroup's previous gap — from LDS the caller is about to reset — is written.  fill_body's exact branch goes through

@@ -55,7 +55,7 @@ __global__ __launch_bounds__(FS_THREADS) void fill_support_kernel(FsParams P) {
     __shared__ uint32_t s_acc[4];               // n_zero, n_below, min, max
     __shared__ unsigned long long s_sum;
     const uint32_t t = threadIdx.x, lane = t & 63, k = P.k;
-    const uint32_t n = fill_round_contigs(P.round);
+    const uint32_t n = contig_list_end(P.round.body.list);
     const uint32_t nwin = P.L >= k ? P.L - k + 1 : 0;
     for (uint32_t g = blockIdx.x; g < P.round.n_gaps; g += gridDim.x) {
         gf_fill_support rec;
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(FS_THREADS) void fill_support_kernel(FsParams P) {
             continue;
         }
         const gf_contig c = fg.fb.c;
-        const char* s = P.round.body.seq + c.seq_off;
+        const char* s = P.round.body.list.seq + c.seq_off;
         const int64_t b0 = fg.fb.b0, b1 = fg.fb.b1;
         const FillRows rows = fill_gap_rows(P.round, g);
         const uint64_t r0 = rows.r0, r1 = rows.r1;

@@ -71,6 +71,12 @@ struct ExtHit {
     uint16_t pad;
 };
 static_assert(sizeof(ExtHit) == 24, "ExtHit");
+// contig ci of gap `gap` has the hits h (next not yet set): pushed on the gap's list of every side it has a hit on — the old head is its link
+__device__ __forceinline__ void ext_hit_publish(uint32_t* heads, ExtHit* hits, uint32_t gap, uint32_t ci, ExtHit h) {
+#pragma unroll
+    for (int sd = 0; sd < 2; ++sd) h.next[sd] = h.m[sd] ? atomicExch(heads + 2 * gap + sd, ci) : EMPTY32;
+    hits[ci] = h;
+}
 
 // merge.hip's kernels in the rescue round (rescue.hip).  MG_MODE_ROUND: the merge round of the step (gf_merge_open_gaps_dev);
 // MG_MODE_RESCUE: the rescue's merge (gf_merge_rescue_dev); MG_MODE_SETS: the rescue's alignment sets — the open gaps' records, own and
@@ -213,10 +219,10 @@ struct ZeroList {
 };
 void zero_regions(gf_ctx* ctx, const ZeroList& z);
 
-// pick.hip: the exact anchors of one length (built once per gf_set_gaps; also read by the after-pick rounds, whose one launch setup — fill_round_setup, api.hip, declared in fill_round.hpp — asks for them); pick_align.hip: the align-mode hits of the extended fill
-int anchor_table_for(gf_ctx* ctx, int anchor_len, const uint8_t** out);
-int launch_align_ext(gf_ctx* ctx, bool gapped, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t, const void* d_first,
-                     const void* d_gap_best, ExtHit* hits, uint32_t* heads, uint32_t* stats);
+// pick.hip: the exact anchors of one length (anchor.hpp; built once per gf_set_gaps; also read by the after-pick rounds, whose one launch setup — fill_round_setup, api.hip, declared in fill_round.hpp — asks for them); pick_align.hip: the align-mode hits of the extended fill
+struct ContigList;   // contig_list.hpp
+int anchor_table(gf_ctx* ctx, int anchor_len, const uint8_t** out);
+int launch_align_ext(gf_ctx* ctx, bool gapped, const ContigList& list, int t, const void* d_gap_best, ExtHit* hits, uint32_t* heads, uint32_t* stats);
 
 // merge.hip: MG_MODE_SETS (d_stats: u32[GF_MG_WORDS] of its own)
 int launch_merge_sets(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t contig_cap, void* d_seq, void* d_seq_len, size_t seq_cap,

@@ -132,6 +132,11 @@ GF_HD uint32_t base_code(char c) {
     return (c == 'C' || c == 'c') ? 1u : (c == 'G' || c == 'g') ? 2u : (c == 'T' || c == 't') ? 3u : 0u;
 }
 
+// A, C, G, T -> 0..3; any other byte -> 4 (the contigs and flanks of the picks, which are upper case)
+GF_HD uint32_t base_code4(uint8_t c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
+// the complement of an upper-case base; any other byte stays as it is
+GF_HD char base_comp(char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c; }
+
 // ---- bit-stream access to packed bases held as bytes (big-endian base order) ------------------------
 // `words` is the byte stream viewed as little-endian uint32 (as a GPU/x86 load sees it); returns the 32 bits
 // starting at bit offset `bitoff` of the stream, first base in the top bits.

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "contig_list.hpp"
 #include "gf_internal.hpp"
 #include "merge_dev.hpp"
 
@@ -317,7 +318,7 @@ __device__ __forceinline__ void ov_load_node(char* dst, const char* src, int n, 
     for (int i = (int)threadIdx.x; i < n; i += (int)blockDim.x) {
         char ch = src[rc ? n - 1 - i : i];
         if (ch >= 'a' && ch <= 'z') ch = (char)(ch - 32);
-        if (rc) ch = ch == 'A' ? 'T' : ch == 'C' ? 'G' : ch == 'G' ? 'C' : ch == 'T' ? 'A' : ch;
+        if (rc) ch = base_comp(ch);
         dst[i] = ch;
     }
 }
@@ -383,7 +384,7 @@ __device__ __forceinline__ bool mg_takes_part(const MgParams& P, const gf_contig
 
 __global__ __launch_bounds__(256) void mg_count_kernel(MgParams P) {
     if (mg_list_overflowed(P)) return;
-    const uint32_t n = *P.n_contigs < P.contig_cap ? *P.n_contigs : P.contig_cap;
+    const uint32_t n = contig_list_end(P.n_contigs, P.contig_cap);
     for (uint32_t c = blockIdx.x * blockDim.x + threadIdx.x; c < n; c += gridDim.x * blockDim.x) {
         const gf_contig ct = P.contigs[c];
         if (mg_takes_part(P, ct, c)) atomicAdd(&P.cnt[ct.gap], 1u);
@@ -414,7 +415,7 @@ __global__ __launch_bounds__(1024) void mg_scan_gaps_kernel(MgParams P) {
     if (threadIdx.x == 0) {
         P.pre_off[carry_set] = carry_off;
         P.stats[MG_N_PRE] = carry_set;
-        P.stats[MG_N0] = *P.n_contigs < P.contig_cap ? *P.n_contigs : P.contig_cap;
+        P.stats[MG_N0] = contig_list_end(P.n_contigs, P.contig_cap);
         if (*P.n_contigs > P.contig_cap) atomicOr(&P.stats[MG_ERR], MG_E_CONTIGS);
         if (*P.seq_len > P.seq_cap) atomicOr(&P.stats[MG_ERR], MG_E_OUTSEQ);
     }
@@ -431,8 +432,6 @@ __global__ __launch_bounds__(256) void mg_fill_kernel(MgParams P) {
         P.ids[P.pre_off[pre] + atomicAdd(&P.cnt[g], 1u)] = c;
     }
 }
-
-__device__ __forceinline__ char mg_comp(char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c; }
 
 // one workgroup per open gap: q is dropped iff it occurs, on either strand, inside a contig that precedes it in (length descending,
 // index ascending) order — containment is transitive, so this is drop_contained's "inside a KEPT contig" without its serial order
@@ -504,7 +503,7 @@ __global__ __launch_bounds__(1024) void mg_dedup_kernel(MgParams P) {
             unsigned long long hf = 0, hr = 0;
             for (uint32_t t = 0; t < hb; ++t) {
                 hf |= (unsigned long long)(uint8_t)sq[t] << (8 * t);
-                hr |= (unsigned long long)(uint8_t)mg_comp(sq[lq - 1 - t]) << (8 * t);
+                hr |= (unsigned long long)(uint8_t)base_comp(sq[lq - 1 - t]) << (8 * t);
             }
             const unsigned long long hmask = hb == 8 ? ~0ull : ((1ull << (8 * hb)) - 1);
             bool gone = false;
@@ -527,7 +526,7 @@ __global__ __launch_bounds__(1024) void mg_dedup_kernel(MgParams P) {
                         }
                         if (!hit && w == hr) {
                             uint32_t t = hb;
-                            while (t < lq && mg_comp(sq[lq - 1 - t]) == sp[at + t]) ++t;
+                            while (t < lq && base_comp(sq[lq - 1 - t]) == sp[at + t]) ++t;
                             hit = t == lq;
                         }
                     }
@@ -991,7 +990,7 @@ __global__ __launch_bounds__(OV_NT) void mg_strings_kernel(MgParams P) {
         {
             const char* src = node_src(path[0], &n1);
             const bool rc = path[0] & 1;
-            for (int i = (int)tid; i < n1; i += OV_NT) { const char ch = src[rc ? n1 - 1 - i : i]; cur[i] = rc ? mg_comp(ch) : ch; }
+            for (int i = (int)tid; i < n1; i += OV_NT) { const char ch = src[rc ? n1 - 1 - i : i]; cur[i] = rc ? base_comp(ch) : ch; }
         }
         __syncthreads();
         uint32_t step = 1;

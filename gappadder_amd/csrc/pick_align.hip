@@ -25,7 +25,9 @@
 #include <algorithm>
 #include <cstring>
 
+#include "contig_list.hpp"
 #include "gf_internal.hpp"
+#include "pick_word.hpp"
 
 namespace gf {
 
@@ -45,10 +47,7 @@ struct AlignMeta {
 static_assert(sizeof(AlignMeta) == 16, "AlignMeta");
 
 struct AlignParams {
-    const gf_contig* contigs;
-    const uint32_t* n_contigs;
-    uint32_t contig_cap;
-    const char* seq;
+    ContigList list;
     const AlignMeta* meta;
     const uint8_t* qbytes;
     const unsigned long long* kmers;
@@ -57,7 +56,6 @@ struct AlignParams {
     uint32_t* n_closed;
     gf_ctg_pick* ctg_pick;
     uint32_t* stats;           // [0] alignments beyond the cap, [1] contigs with more than AL_SEED_MAX seeds
-    const uint32_t* first;     // or null
     ExtHit* ext_hits;          // the extended fill (pick_ext.hip): per contig its wanted hit per side, pushed on ...
     uint32_t* ext_heads;       // ... the lists of its gap (t_long = the threshold; gap_best is read, not written)
 };
@@ -66,10 +64,6 @@ struct AlHit {
     uint32_t m, score, rev, pos;   // m == 0: none
 };
 
-__device__ __forceinline__ uint32_t al_code(char c) {
-    return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u;
-}
-
 __device__ __forceinline__ int al_score(uint32_t a, uint32_t b) {
     return (a > 3 || b > 3) ? AL_NSCORE : a == b ? AL_MATCH : AL_MISMATCH;
 }
@@ -77,11 +71,11 @@ __device__ __forceinline__ int al_score(uint32_t a, uint32_t b) {
 // one seed -> score << 33 | seed end << 22 | query begin << 11 | query end (pick_contigs.py::_extend)
 __device__ uint64_t al_extend(const uint8_t* Q, int n, const char* s, int m, int d, int qs) {
     int se = qs;
-    while (se < n && se + d < m && Q[se] < 4 && Q[se] == al_code(s[se + d])) ++se;
+    while (se < n && se + d < m && Q[se] < 4 && Q[se] == base_code4(s[se + d])) ++se;
     int run = se - qs, best = run, qb = qs, i = qs - 1;
     bool stopped = false;
     for (; i >= 0 && i + d >= 0; --i) {
-        run += al_score(Q[i], al_code(s[i + d]));
+        run += al_score(Q[i], base_code4(s[i + d]));
         if (run > best) { best = run; qb = i; }
         else if (best - run > AL_ZDROP) { stopped = true; break; }
     }
@@ -91,7 +85,7 @@ __device__ uint64_t al_extend(const uint8_t* Q, int n, const char* s, int m, int
     int qe = se, j = se;
     stopped = false;
     for (; j < n && j + d < m; ++j) {
-        run += al_score(Q[j], al_code(s[j + d]));
+        run += al_score(Q[j], base_code4(s[j + d]));
         if (run > best) { best = run; qe = j + 1; }
         else if (best - run > AL_ZDROP) { stopped = true; break; }
     }
@@ -187,15 +181,15 @@ __device__ __forceinline__ void pick_align_body(const AlignParams& P) {
     __shared__ uint32_t kept_q[GAPPED ? AL_CAP : 1], kept_cb[GAPPED ? AL_CAP : 1], kept_ce[GAPPED ? AL_CAP : 1];
     __shared__ uint8_t qst[GAPPED ? AL_FLANK_MAX : 4], cst[GAPPED ? GP_CTG : 4];
     __shared__ AlHit tab[2][2][3];                     // [threshold][side][clip type] (lane 0)
-    const uint32_t n_ctg = *P.n_contigs < P.contig_cap ? *P.n_contigs : P.contig_cap;
+    const uint32_t n_ctg = contig_list_end(P.list);
     const int lane = threadIdx.x;
-    for (uint32_t ci = (P.first ? *P.first : 0u) + blockIdx.x; ci < n_ctg; ci += gridDim.x) {
-        const gf_contig c = P.contigs[ci];
+    for (uint32_t ci = contig_list_begin(P.list) + blockIdx.x; ci < n_ctg; ci += gridDim.x) {
+        const gf_contig c = P.list.contigs[ci];
         if (c.gap >= P.n_gaps || c.length < (uint32_t)AL_SEED) continue;        // (uniform over the workgroup)
         if (EXT && P.gap_best[c.gap]) continue;
         const AlignMeta M = P.meta[c.gap];
         if (!M.kn) continue;
-        const char* s = P.seq + c.seq_off;
+        const char* s = P.list.seq + c.seq_off;
         const int m = (int)c.length, nl = M.nl, nr = M.nr;
         const uint8_t* qb0 = P.qbytes + M.qoff;
         const unsigned long long* km = P.kmers + M.kbeg;
@@ -208,7 +202,7 @@ __device__ __forceinline__ void pick_align_body(const AlignParams& P) {
             uint64_t kmer = 0;
             int run = 0;
             for (int j = p0; j < p1 + AL_SEED - 1; ++j) {
-                const uint32_t b = al_code(s[j]);
+                const uint32_t b = base_code4(s[j]);
                 if (b < 4) { kmer = ((kmer << 2) | b) & ((1ull << (2 * AL_SEED)) - 1); ++run; } else run = 0;
                 if (j < p0 + AL_SEED - 1 || run < AL_SEED) continue;
                 const int p = j - AL_SEED + 1;
@@ -218,7 +212,7 @@ __device__ __forceinline__ void pick_align_body(const AlignParams& P) {
                     const uint32_t h = (a + z) >> 1;
                     if (km[h] < lo) a = h + 1; else z = h;
                 }
-                const uint32_t prev = p > 0 ? al_code(s[p - 1]) : 4u;
+                const uint32_t prev = p > 0 ? base_code4(s[p - 1]) : 4u;
                 for (; a < M.kn && (km[a] >> 12) == kmer; ++a) {
                     const uint32_t qi = (uint32_t)(km[a] >> 10) & 3u, q = (uint32_t)km[a] & 1023u;
                     const uint8_t* Q = qb0 + (qi == 0 ? 0 : qi == 1 ? nl : qi == 2 ? 2 * nl : 2 * nl + nr);
@@ -257,7 +251,7 @@ __device__ __forceinline__ void pick_align_body(const AlignParams& P) {
                 int se = q + AL_SEED;                             // the end of the seed's run of identical ACGT bases
                 for (;;) {
                     const int x = se + lane;
-                    const bool on = x < nq && x + d < m && Q[x] < 4 && Q[x] == al_code(s[x + d]);
+                    const bool on = x < nq && x + d < m && Q[x] < 4 && Q[x] == base_code4(s[x + d]);
                     const unsigned long long off = __ballot(!on);
                     if (off) { se += __ffsll((long long)off) - 1; break; }
                     se += 64;
@@ -279,7 +273,7 @@ __device__ __forceinline__ void pick_align_body(const AlignParams& P) {
                 // left of the seed: query bases q-1 .. 0 against contig bases q+d-1 .. 0
                 int J = q, I = min(q + d, J + GP_BAND);
                 for (int x = lane; x < J; x += 64) qst[x] = Q[q - 1 - x];
-                for (int x = lane; x < I; x += 64) cst[x] = (uint8_t)al_code(s[q + d - 1 - x]);
+                for (int x = lane; x < I; x += 64) cst[x] = (uint8_t)base_code4(s[q + d - 1 - x]);
                 __syncthreads();
                 const unsigned long long lres = gp_side(qst, cst, I, J, se - q, lane);
                 __syncthreads();
@@ -288,7 +282,7 @@ __device__ __forceinline__ void pick_align_body(const AlignParams& P) {
                 J = nq - se;
                 I = min(m - se - d, J + GP_BAND);
                 for (int x = lane; x < J; x += 64) qst[x] = Q[se + x];
-                for (int x = lane; x < I; x += 64) cst[x] = (uint8_t)al_code(s[se + d + x]);
+                for (int x = lane; x < I; x += 64) cst[x] = (uint8_t)base_code4(s[se + d + x]);
                 __syncthreads();
                 const unsigned long long rres = gp_side(qst, cst, I, J, (int)(lres >> 22), lane);
                 const int qe = se + (int)(rres & 2047u), ce = se + d + (int)((rres >> 11) & 2047u);
@@ -370,20 +364,17 @@ __device__ __forceinline__ void pick_align_body(const AlignParams& P) {
                 }
             }
             if (drops) atomicAdd(P.stats, drops);
-            if (EXT) {
-                if (fh_l.m || fh_r.m) {
-                    ExtHit eh;
-                    eh.pad = 0;
+            if (EXT && (fh_l.m || fh_r.m)) {
+                ExtHit eh;
+                eh.pad = 0;
 #pragma unroll
-                    for (int sd = 0; sd < 2; ++sd) {
-                        const AlHit o = sd ? fh_r : fh_l;
-                        eh.m[sd] = (uint16_t)o.m;
-                        eh.rev[sd] = (uint8_t)o.rev;
-                        eh.pos[sd] = o.pos;
-                        eh.next[sd] = o.m ? atomicExch(P.ext_heads + 2 * c.gap + sd, ci) : EMPTY32;
-                    }
-                    P.ext_hits[ci] = eh;
+                for (int sd = 0; sd < 2; ++sd) {
+                    const AlHit o = sd ? fh_r : fh_l;
+                    eh.m[sd] = (uint16_t)o.m;
+                    eh.rev[sd] = (uint8_t)o.rev;
+                    eh.pos[sd] = o.pos;
                 }
+                ext_hit_publish(P.ext_heads, P.ext_hits, c.gap, ci, eh);
             }
             uint32_t lp = 0, rp = 0, lm = 0, rm = 0, rc = 0, T = 0;
             int span = -1;
@@ -398,12 +389,7 @@ __device__ __forceinline__ void pick_align_body(const AlignParams& P) {
                     v.reserved = 0;
                     *cp = v;
                 }
-                unsigned long long sp = (unsigned long long)span + 1;
-                if (sp > 0xFFFFFFull) sp = 0xFFFFFFull;
-                const unsigned long long val = ((unsigned long long)T << 56) | (sp << 32) |
-                                               ((unsigned long long)(0x7FFFFFFFu - ci) << 1) | rc;
-                const unsigned long long old = atomicMax(P.gap_best + c.gap, val);
-                if (old == 0) atomicAdd(P.n_closed, 1u);
+                pick_word_publish(P.gap_best, P.n_closed, c.gap, pick_word_pack(T, (uint64_t)span, ci, rc));   // (pick_word.hpp; T: the word's level)
             }
         }
         __syncthreads();
@@ -431,7 +417,6 @@ static int align_tables(gf_ctx* ctx, const AlignMeta** meta, const uint8_t** qby
         std::vector<AlignMeta> mt(ng);
         std::vector<uint8_t> qb;
         std::vector<unsigned long long> km;
-        auto code = [](char c) -> uint8_t { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; };
         for (size_t g = 0; g < ng; ++g) {
             const std::string &l = ctx->flank_left[g], &r = ctx->flank_right[g];
             if ((int)l.size() > AL_FLANK_MAX || (int)r.size() > AL_FLANK_MAX) {
@@ -448,7 +433,7 @@ static int align_tables(gf_ctx* ctx, const AlignMeta** meta, const uint8_t** qby
                 const std::string& f = *fl[qi >> 1];
                 const size_t n = f.size(), q0 = qb.size();
                 for (size_t i = 0; i < n; ++i) {
-                    const uint8_t b = (qi & 1) ? code(f[n - 1 - i]) : code(f[i]);
+                    const uint8_t b = (uint8_t)base_code4((qi & 1) ? f[n - 1 - i] : f[i]);
                     qb.push_back((qi & 1) && b < 4 ? (uint8_t)(3 - b) : b);
                 }
                 uint64_t kmer = 0;
@@ -477,32 +462,32 @@ static int align_tables(gf_ctx* ctx, const AlignMeta** meta, const uint8_t** qby
     return GF_OK;
 }
 
+// what both launches of pick_align_body read the same way: the tables, the list, the gaps, the thresholds, the picks and the statistics
+static int align_params(gf_ctx* ctx, const ContigList& list, int t_long, int t_short, const void* d_gap_best, void* d_stats, AlignParams* P) {
+    memset(P, 0, sizeof(*P));
+    const int rc = align_tables(ctx, &P->meta, &P->qbytes, &P->kmers);
+    if (rc) return rc;
+    P->list = list;
+    P->n_gaps = (uint32_t)ctx->gaps.size();
+    P->t_long = (uint32_t)t_long;
+    P->t_short = (uint32_t)t_short;
+    P->gap_best = (unsigned long long*)d_gap_best;
+    P->stats = (uint32_t*)d_stats;
+    return GF_OK;
+}
+
 static int pick_aligned(gf_ctx* ctx, bool gapped, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t_long,
                         int t_short, const void* d_first, void* d_gap_best, void* d_n_closed, void* d_ctg_pick, void* d_stats) {
-    if (!ctx || !d_contigs || !d_n_contigs || !d_seq || !d_gap_best || !d_n_closed || !d_ctg_pick || !d_stats || t_long < 1 ||
-        t_long > 255 || contig_cap > 0x7FFFFFFFull || t_short < 0 || (t_short && t_short >= t_long))
-        return GF_E_INVAL;
-    const size_t ng = ctx->gaps.size();
-    if (ctx->flank_left.size() != ng || ctx->flank_right.size() != ng) return GF_E_STATE;
-    if (!ng) return GF_OK;
+    const bool own_ok = d_gap_best && d_n_closed && d_ctg_pick && d_stats && t_long >= 1 && t_long <= 255 && t_short >= 0 && (!t_short || t_short < t_long);
+    ContigList list;
+    int rc = contig_list_view(ctx, d_contigs, d_n_contigs, contig_cap, CONTIG_CAP_WORD, d_seq, d_first, own_ok ? GF_OK : GF_E_INVAL, &list);
+    if (rc) return rc;
+    if (!ctx->gaps.size()) return GF_OK;
     GF_HIP(ctx, hipSetDevice(ctx->device));
     AlignParams P;
-    int rc = align_tables(ctx, &P.meta, &P.qbytes, &P.kmers);
-    if (rc) return rc;
-    P.contigs = (const gf_contig*)d_contigs;
-    P.n_contigs = (const uint32_t*)d_n_contigs;
-    P.contig_cap = (uint32_t)contig_cap;
-    P.seq = (const char*)d_seq;
-    P.n_gaps = (uint32_t)ng;
-    P.t_long = (uint32_t)t_long;
-    P.t_short = (uint32_t)t_short;
-    P.gap_best = (unsigned long long*)d_gap_best;
+    if ((rc = align_params(ctx, list, t_long, t_short, d_gap_best, d_stats, &P))) return rc;
     P.n_closed = (uint32_t*)d_n_closed;
     P.ctg_pick = (gf_ctg_pick*)d_ctg_pick;
-    P.stats = (uint32_t*)d_stats;
-    P.first = (const uint32_t*)d_first;
-    P.ext_hits = nullptr;
-    P.ext_heads = nullptr;
     LaunchTimer tm(ctx, GF_KERNEL_PICK);
     hipLaunchKernelGGL(gapped ? pick_gapped_kernel : pick_align_kernel, dim3(ctx->n_cu * 16), dim3(64), 0, ctx->stream, P);
     GF_HIP(ctx, hipGetLastError());
@@ -535,21 +520,11 @@ int gf_pick_gapped_from_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_
 
 namespace gf {
 
-int launch_align_ext(gf_ctx* ctx, bool gapped, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int t, const void* d_first,
-                     const void* d_gap_best, ExtHit* hits, uint32_t* heads, uint32_t* stats) {   // (pick_ext.hip; the caller checked the arguments)
+int launch_align_ext(gf_ctx* ctx, bool gapped, const ContigList& list, int t, const void* d_gap_best, ExtHit* hits, uint32_t* heads,
+                     uint32_t* stats) {   // (pick_ext.hip, which checked the arguments; gap_best is read, not written)
     AlignParams P;
-    memset(&P, 0, sizeof(P));
-    int rc = align_tables(ctx, &P.meta, &P.qbytes, &P.kmers);
+    const int rc = align_params(ctx, list, t, 0, d_gap_best, stats, &P);
     if (rc) return rc;
-    P.contigs = (const gf_contig*)d_contigs;
-    P.n_contigs = (const uint32_t*)d_n_contigs;
-    P.contig_cap = (uint32_t)contig_cap;
-    P.seq = (const char*)d_seq;
-    P.n_gaps = (uint32_t)ctx->gaps.size();
-    P.t_long = (uint32_t)t;
-    P.gap_best = (unsigned long long*)d_gap_best;
-    P.stats = stats;
-    P.first = (const uint32_t*)d_first;
     P.ext_hits = hits;
     P.ext_heads = heads;
     hipLaunchKernelGGL(gapped ? pick_gapped_ext_kernel : pick_align_ext_kernel, dim3(ctx->n_cu * 16), dim3(64), 0, ctx->stream, P);

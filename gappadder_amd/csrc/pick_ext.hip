@@ -18,18 +18,14 @@
 //   write    one wave per gap: the parts gathered (and reverse-complemented) into the base buffer around "NN"
 #include <cstring>
 
+#include "anchor.hpp"
+#include "contig_list.hpp"
 #include "gf_internal.hpp"
 
 namespace gf {
 
-constexpr int EXT_ANCHOR_MAX = 32, EXT_ROW = 5 * EXT_ANCHOR_MAX;   // the anchor rows of pick.hip (left, right, rc(left), rc(right), flags)
-
 struct ExtParams {
-    const gf_contig* contigs;
-    const uint32_t* n_contigs;
-    uint32_t contig_cap;
-    const char* seq;
-    const uint32_t* first;                 // or null
+    ContigList list;
     const unsigned long long* gap_best;
     uint32_t n_gaps;
     ExtHit* hits;                          // per contig index
@@ -47,71 +43,36 @@ struct ExtParams {
 // reverse strand searched in the reverse-complemented contig, positions in the contig's own frame).  Wanted: the side's flank is
 // longer than the anchor (a flank of exactly `a` bases gives unclipped hits); forward before reverse.
 __global__ __launch_bounds__(256) void ext_anchor_kernel(ExtParams P, const uint8_t* anc, uint32_t a) {
-    const uint32_t n = *P.n_contigs < P.contig_cap ? *P.n_contigs : P.contig_cap;
+    const uint32_t n = contig_list_end(P.list);
     const uint32_t lane = threadIdx.x & 63;
     const uint32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, n_waves = (gridDim.x * blockDim.x) >> 6;
-    for (uint32_t ci = (P.first ? *P.first : 0u) + wave; ci < n; ci += n_waves) {
-        const gf_contig c = P.contigs[ci];
+    for (uint32_t ci = contig_list_begin(P.list) + wave; ci < n; ci += n_waves) {
+        const gf_contig c = P.list.contigs[ci];
         if (c.gap >= P.n_gaps || c.length < a || P.gap_best[c.gap]) continue;
-        const uint8_t* as = anc + (uint64_t)c.gap * EXT_ROW;
-        const uint32_t fl = as[4 * EXT_ANCHOR_MAX];
-        const bool want[2] = {as[0] != 0 && !(fl & 1), as[EXT_ANCHOR_MAX] != 0 && !(fl & 2)};   // (no anchors: both rows empty)
+        const uint8_t* as = anchor_rows(anc, c.gap);
+        const uint32_t fl = anchor_flags(as);
+        const bool want[2] = {anchor_row(as, ANC_LEFT)[0] != 0 && !(fl & ANC_F_LEFT_WHOLE),
+                              anchor_row(as, ANC_RIGHT)[0] != 0 && !(fl & ANC_F_RIGHT_WHOLE)};   // (no anchors: both rows empty)
         if (!want[0] && !want[1]) continue;
-        const char* s = P.seq + c.seq_off;
-        uint32_t head[4], mn[4], mx[4];
+        uint32_t mn[4], mx[4];
         bool any[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const uint8_t* pat = as + q * EXT_ANCHOR_MAX;
-            head[q] = (uint32_t)pat[0] | ((uint32_t)pat[1] << 8) | ((uint32_t)pat[2] << 16) | ((uint32_t)pat[3] << 24);
-            mn[q] = EMPTY32;
-            mx[q] = 0;
-            any[q] = false;
-        }
-        const uint32_t last = c.length - a;
-        for (uint32_t p = lane; p <= last; p += 64) {
-            uint32_t w = 0;                                       // four bases at p (a >= 8: they exist)
-#pragma unroll
-            for (int b = 0; b < 4; ++b) w |= (uint32_t)(uint8_t)s[p + b] << (8 * b);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {                         // q: left, right, rc(left), rc(right) — side q & 1
-                if (!want[q & 1] || w != head[q]) continue;
-                const uint8_t* pat = as + q * EXT_ANCHOR_MAX;
-                uint32_t i = 4;
-                while (i < a && (uint8_t)s[p + i] == pat[i]) ++i;
-                if (i != a) continue;
-                any[q] = true;
-                mn[q] = p < mn[q] ? p : mn[q];
-                mx[q] = p > mx[q] ? p : mx[q];
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {   // wave reductions
-            for (int d = 32; d >= 1; d >>= 1) {
-                const uint32_t m2 = __shfl_xor(mn[q], d), x2 = __shfl_xor(mx[q], d);
-                mn[q] = m2 < mn[q] ? m2 : mn[q];
-                mx[q] = x2 > mx[q] ? x2 : mx[q];
-            }
-            any[q] = __ballot(any[q]) != 0;
-        }
+        anchor_scan<false>(P.list.seq + c.seq_off, c.length, as, nullptr, a, 0, want, lane, mn, mx, any);
         if (lane != 0) continue;
         ExtHit h;
         h.m[0] = h.m[1] = 0;
         h.pad = 0;
-        if (any[0] || any[2]) {
+        if (any[ANC_LEFT] || any[ANC_RC_LEFT]) {
             h.m[0] = (uint16_t)a;
-            h.rev[0] = !any[0];
-            h.pos[0] = (any[0] ? mn[0] : mx[2]) + 1;
+            h.rev[0] = !any[ANC_LEFT];
+            h.pos[0] = (any[ANC_LEFT] ? mn[ANC_LEFT] : mx[ANC_RC_LEFT]) + 1;
         }
-        if (any[1] || any[3]) {
+        if (any[ANC_RIGHT] || any[ANC_RC_RIGHT]) {
             h.m[1] = (uint16_t)a;
-            h.rev[1] = !any[1];
-            h.pos[1] = (any[1] ? mx[1] : mn[3]) + 1;
+            h.rev[1] = !any[ANC_RIGHT];
+            h.pos[1] = (any[ANC_RIGHT] ? mx[ANC_RIGHT] : mn[ANC_RC_RIGHT]) + 1;
         }
         if (!h.m[0] && !h.m[1]) continue;
-        for (int sd = 0; sd < 2; ++sd)
-            h.next[sd] = h.m[sd] ? atomicExch(P.heads + 2 * c.gap + sd, ci) : EMPTY32;
-        P.hits[ci] = h;
+        ext_hit_publish(P.heads, P.hits, c.gap, ci, h);
     }
 }
 
@@ -124,11 +85,11 @@ __device__ __forceinline__ uint32_t ext_rank(const ExtParams& P, const gf_contig
 
 // contig a before contig b in the extension order
 __device__ bool ext_before(const ExtParams& P, uint32_t a, uint32_t b) {
-    const gf_contig ca = P.contigs[a], cb = P.contigs[b];
+    const gf_contig ca = P.list.contigs[a], cb = P.list.contigs[b];
     const uint32_t ra = ext_rank(P, ca), rb = ext_rank(P, cb);
     if (ra != rb) return ra < rb;
     if (ca.length != cb.length) return ca.length > cb.length;
-    const uint8_t *sa = (const uint8_t*)P.seq + ca.seq_off, *sb = (const uint8_t*)P.seq + cb.seq_off;
+    const uint8_t *sa = (const uint8_t*)P.list.seq + ca.seq_off, *sb = (const uint8_t*)P.list.seq + cb.seq_off;
     for (uint32_t i = 0; i < ca.length; ++i)
         if (sa[i] != sb[i]) return sa[i] < sb[i];
     return a < b;
@@ -148,14 +109,14 @@ __global__ __launch_bounds__(256) void ext_choose_kernel(ExtParams P) {
     r.right = R;
     if (L != EMPTY32 && L != R) {          // the contig beyond the left anchor; reverse: before rc(anchor), its first base kept
         const ExtHit h = P.hits[L];
-        const uint32_t n = P.contigs[L].length;
+        const uint32_t n = P.list.contigs[L].length;
         r.l_rev = h.rev[0];
         r.l_beg = h.rev[0] ? 0u : h.pos[0] + h.m[0] - 1;
         r.l_len = h.rev[0] ? h.pos[0] : n - r.l_beg;
     }
     if (R != EMPTY32) {                    // the contig before the right anchor (reverse: after rc(anchor)); the same contig on both
         const ExtHit h = P.hits[R];        // sides: the forward part keeps the anchor's first base (pick_contigs.py:480-486)
-        const uint32_t n = P.contigs[R].length;
+        const uint32_t n = P.list.contigs[R].length;
         r.r_rev = h.rev[1];
         r.r_beg = h.rev[1] ? h.pos[1] + h.m[1] - 1 : 0u;
         r.r_len = h.rev[1] ? n - r.r_beg : h.pos[1] - (L == R ? 0u : 1u);
@@ -221,9 +182,9 @@ __global__ __launch_bounds__(256) void ext_write_kernel(ExtParams P) {
         const gf_ext_pick r = P.ext[g];
         if (!r.len || r.off + r.len > P.base_cap) continue;     // (beyond the buffer: the overflow flag is set, nothing is cut)
         char* o = P.bases + r.off;
-        if (r.l_len) ext_copy(o, P.seq + P.contigs[r.left].seq_off + r.l_beg, r.l_len, r.l_rev, lane);
+        if (r.l_len) ext_copy(o, P.list.seq + P.list.contigs[r.left].seq_off + r.l_beg, r.l_len, r.l_rev, lane);
         if (lane < 2) o[r.l_len + lane] = 'N';
-        if (r.r_len) ext_copy(o + r.l_len + 2, P.seq + P.contigs[r.right].seq_off + r.r_beg, r.r_len, r.r_rev, lane);
+        if (r.r_len) ext_copy(o + r.l_len + 2, P.list.seq + P.list.contigs[r.right].seq_off + r.r_beg, r.r_len, r.r_rev, lane);
     }
 }
 
@@ -236,27 +197,20 @@ extern "C" {
 static int pick_extended(gf_ctx* ctx, bool align, bool gapped, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int a,
                          const int* k_list, const int* kv_list, int n_k, const void* d_first, const void* d_gap_best, void* d_ext, void* d_bases,
                          size_t base_cap, void* d_stats) {
-    if (!ctx || !d_contigs || !d_n_contigs || !d_seq || !d_gap_best || !d_ext || !d_stats || (base_cap && !d_bases) ||
-        contig_cap > 0x7FFFFFFFull || n_k < 0 || n_k > GF_EXT_MAX_PAIRS || (n_k && (!k_list || !kv_list)) ||
-        (align ? (a < 1 || a > 255) : (a < 8 || a > EXT_ANCHOR_MAX)))
-        return GF_E_INVAL;
-    const size_t ng = ctx->gaps.size();
-    if (ctx->flank_left.size() != ng || ctx->flank_right.size() != ng) return GF_E_STATE;
-    GF_HIP(ctx, hipSetDevice(ctx->device));
-    GF_HIP(ctx, hipMemsetAsync(d_stats, 0, 4 * GF_EXT_WORDS, ctx->stream));
-    if (!ng) return GF_OK;
+    const bool own_ok = d_gap_best && d_ext && d_stats && (!base_cap || d_bases) && n_k >= 0 && n_k <= GF_EXT_MAX_PAIRS && (!n_k || (k_list && kv_list)) &&
+                        (align ? (a >= 1 && a <= 255) : (a >= 8 && a <= ANCHOR_MAX));
     ExtParams P;
     memset(&P, 0, sizeof(P));
+    int rc = contig_list_view(ctx, d_contigs, d_n_contigs, contig_cap, CONTIG_CAP_WORD, d_seq, d_first, own_ok ? GF_OK : GF_E_INVAL, &P.list);
+    if (rc) return rc;
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    GF_HIP(ctx, hipMemsetAsync(d_stats, 0, 4 * GF_EXT_WORDS, ctx->stream));
+    const size_t ng = ctx->gaps.size();
+    if (!ng) return GF_OK;
     const uint8_t* anc = nullptr;
-    int rc;
-    if (!align && (rc = anchor_table_for(ctx, a, &anc))) return rc;
+    if (!align && (rc = anchor_table(ctx, a, &anc))) return rc;
     const size_t head_bytes = (ng * 8 + 255) & ~(size_t)255;
     if ((rc = ensure(ctx, ctx->ext_ws, head_bytes + contig_cap * sizeof(ExtHit) + 64))) return rc;
-    P.contigs = (const gf_contig*)d_contigs;
-    P.n_contigs = (const uint32_t*)d_n_contigs;
-    P.contig_cap = (uint32_t)contig_cap;
-    P.seq = (const char*)d_seq;
-    P.first = (const uint32_t*)d_first;
     P.gap_best = (const unsigned long long*)d_gap_best;
     P.n_gaps = (uint32_t)ng;
     P.heads = (uint32_t*)ctx->ext_ws.p;
@@ -274,9 +228,7 @@ static int pick_extended(gf_ctx* ctx, bool align, bool gapped, const void* d_con
     GF_HIP(ctx, hipMemsetAsync(P.heads, 0xFF, ng * 8, ctx->stream));
     LaunchTimer tm(ctx, GF_KERNEL_PICK);
     if (align) {
-        if ((rc = launch_align_ext(ctx, gapped, d_contigs, d_n_contigs, contig_cap, d_seq, a, d_first, d_gap_best, P.hits, P.heads,
-                                   P.stats + GF_EXT_ALIGN_DROPPED)))
-            return rc;
+        if ((rc = launch_align_ext(ctx, gapped, P.list, a, d_gap_best, P.hits, P.heads, P.stats + GF_EXT_ALIGN_DROPPED))) return rc;
     } else {
         hipLaunchKernelGGL(ext_anchor_kernel, dim3(ctx->n_cu * 8), dim3(256), 0, ctx->stream, P, anc, (uint32_t)a);
         GF_HIP(ctx, hipGetLastError());

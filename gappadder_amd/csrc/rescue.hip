@@ -198,8 +198,6 @@ __device__ __forceinline__ bool rs_lookup(const RsSlot* tab, uint32_t log2, unsi
     return false;
 }
 
-__device__ __forceinline__ uint32_t rs_acgt(char c) { return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 4u; }
-
 // ---- seeds: one workgroup per alignment set (gap with HQ reads); windows rolled over a stretch of 64 positions per thread
 __global__ __launch_bounds__(256) void rs_seeds_kernel(const gf_contig* ctg, const char* seq, MgSetsView V, const uint32_t* sets_stats,
                                                        const uint32_t* gap_hq, uint64_t n_gaps, const RsSlot* tab, uint32_t log2,
@@ -222,7 +220,7 @@ __global__ __launch_bounds__(256) void rs_seeds_kernel(const gf_contig* ctg, con
                 uint32_t run = 0;
                 const uint32_t p1 = min(p0 + STRETCH, n_win);
                 for (uint32_t x = p0; x < p1 + RS_SEED - 1; ++x) {      // bases p0 .. p1 + 28: windows starting at p0 .. p1 - 1
-                    const uint32_t b = rs_acgt(s[x]);
+                    const uint32_t b = base_code4(s[x]);
                     run = b == 4u ? 0 : run + 1;
                     f = ((f << 2) | (b & 3u)) & RS_WIN_MASK;
                     r = (r >> 2) | ((unsigned long long)(3u - (b & 3u)) << (2 * (RS_SEED - 1)));
@@ -255,8 +253,6 @@ __device__ __forceinline__ uint32_t rs_lower(const unsigned long long* win, cons
     }
     return lo;
 }
-
-__device__ __forceinline__ char rs_comp(char c) { return c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : c == 'T' ? 'A' : c; }
 
 __global__ __launch_bounds__(64) void rs_bridge_kernel(const gf_contig* ctg, const char* seq, MgSetsView V, const unsigned long long* hq,
                                                        const uint32_t* stats_ro, RsLibs L, uint32_t len, uint32_t rb, uint32_t nmw,
@@ -291,7 +287,7 @@ __global__ __launch_bounds__(64) void rs_bridge_kernel(const gf_contig* ctg, con
             unsigned long long v = 0;
             bool ok = true;
             for (uint32_t t = 0; t < RS_SEED; ++t) {
-                const uint32_t b = rs_acgt(s_rd[i + t]);
+                const uint32_t b = base_code4(s_rd[i + t]);
                 ok = ok && b != 4u;
                 v = (v << 2) | (b & 3u);
             }
@@ -335,7 +331,7 @@ __global__ __launch_bounds__(64) void rs_bridge_kernel(const gf_contig* ctg, con
                 for (uint32_t t = 0; t < len && left <= RS_BUDGET && right <= RS_BUDGET; ++t) {
                     if (t >= si && t < si + RS_SEED) continue;
                     const uint64_t cp = (uint64_t)start + t;
-                    const char cb = st ? rs_comp(cs[c.length - 1 - cp]) : cs[cp];
+                    const char cb = st ? base_comp(cs[c.length - 1 - cp]) : cs[cp];
                     if (s_rd[t] != cb) { if (t < si) ++left; else ++right; }
                 }
                 clipped = left > RS_BUDGET || right > RS_BUDGET;
