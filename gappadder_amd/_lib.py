@@ -35,7 +35,7 @@ assert CONTIG.itemsize == 32 and EXT_PICK.itemsize == 40 and GAP.itemsize == 16 
 GF_OK, GF_E_INVAL, GF_E_NODEV, GF_E_NOMEM, GF_E_NOSPACE, GF_E_STATE, GF_E_UNSUPPORTED, GF_E_FORMAT = 0, -1, -2, -3, -4, -5, -6, -7
 KIND_CLIP, KIND_DISCORDANT, KIND_UNMAP, KIND_LOWMAPQ = 0, 1, 2, 3
 KIND_NAMES = {KIND_CLIP: "clip", KIND_DISCORDANT: "discordant", KIND_UNMAP: "unmap"}
-KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT, KERNEL_POLISH, KERNEL_PAIRS = range(14)
+KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT, KERNEL_POLISH, KERNEL_PAIRS, KERNEL_ANCHORS = range(15)
 
 # words of the merge round's statistics (gf_merge_open_gaps_dev, u32[32])
 MG_N_PRE, MG_N_SETS, MG_SKIPPED, MG_N_PAIRS, MG_QC_FLAGS, MG_N_JOBS, MG_ERR, MG_N0, MG_N_EDGES, MG_SETS_WITH_JOBS = range(10)
@@ -92,6 +92,19 @@ FILL_PAIRS = np.dtype([("flags", "<u4"), ("rows", "<u4"), ("pairs_complete", "<u
 assert FILL_PAIRS.itemsize == 64
 PS_F_LONG, PS_F_NON_ACGT = 1, 2
 PS_GAPS, PS_MISMATCH, PS_SKIPPED_LONG, PS_SKIPPED_NON_ACGT, PS_UNSPANNED, PS_COMPLETE, PS_PLACED, PS_PROPER, PS_IN_RANGE, PS_SPAN, PS_WORDS = 0, 1, 2, 3, 4, 6, 8, 10, 12, 14, 16
+
+# the anchored pair span (gf_fill_pairs_anchored_dev): the record per (library, gap) — its flags are PS_F_* — and the words of its
+# statistics (u32[20]): gaps examined, mismatches, skipped long / non-ACGT, hits kept, dropped for a clipped anchor / an anchor inside the
+# gap / a secondary or supplementary record, hits whose target has no row, every other dropped hit, then u64 each: anchored, placed,
+# proper, in-range, spanning pairs
+FILL_ANCHORS = np.dtype([("flags", "<u4"), ("rows", "<u4"), ("n_anchored", "<u4"), ("n_placed", "<u4"), ("n_proper", "<u4"),
+                         ("n_misoriented", "<u4"), ("n_in_range", "<u4"), ("n_short", "<u4"), ("n_long", "<u4"), ("n_left", "<u4"),
+                         ("n_span", "<u4"), ("n_cols", "<u4"), ("span_insert_sum", "<i8"), ("dev_sum", "<i8"), ("min_cover", "<u4"),
+                         ("min_col", "<u4"), ("n_unspanned", "<u4"), ("n_eval", "<u4"), ("dev_min_col", "<u4"), ("dev_min_n", "<u4"),
+                         ("dev_min_sum", "<i8"), ("dev_max_col", "<u4"), ("dev_max_n", "<u4"), ("dev_max_sum", "<i8")])
+assert FILL_ANCHORS.itemsize == 112
+(PA_GAPS, PA_MISMATCH, PA_SKIPPED_LONG, PA_SKIPPED_NON_ACGT, PA_KEPT, PA_DROP_CLIPPED, PA_DROP_IN_GAP, PA_DROP_SECONDARY, PA_ABSENT,
+ PA_DROP_OTHER, PA_ANCHORED, PA_PLACED, PA_PROPER, PA_IN_RANGE, PA_SPAN, PA_WORDS) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 14, 16, 18, 20
 
 _lib = None
 
@@ -223,6 +236,7 @@ def lib():
         "gf_fill_support_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
         "gf_fill_polish_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
         "gf_fill_pairs_dev": (i32, [vp, vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+        "gf_fill_pairs_anchored_dev": (i32, [vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, vp, vp, sz, vp, vp, sz, i32, i32, i32, i32, vp, vp, vp]),
         "gf_contigs_append_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp]),
         "gf_rescue_work_bytes": (sz, [sz, sz, sz, i32]),
         "gf_rescue_reset_dev": (i32, [vp, vp, sz, sz, sz, i32, vp]),

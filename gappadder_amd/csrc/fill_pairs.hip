@@ -20,6 +20,7 @@
 #include <cstring>
 
 #include "fill_body.hpp"
+#include "fill_pair_word.hpp"
 #include "fill_place.hpp"
 #include "fill_round.hpp"
 #include "gf_internal.hpp"
@@ -27,8 +28,7 @@
 namespace gf {
 
 constexpr uint32_t PS_IDX_WORDS = PL_MAX + 4;                                // the index's PL_SLOTS / 2 words, then the n + 1 differences
-constexpr uint32_t PS_BIAS = 1024, PS_STRAND = 1u << 16, PS_PLACED = 1u << 17, PS_AMBIGUOUS = 2u << 17;
-static_assert(PS_IDX_WORDS >= PL_SLOTS / 2 && PS_IDX_WORDS >= PL_MAX + 1 && PL_MAX + 2 * PS_BIAS < PS_STRAND, "pair-span geometry");
+static_assert(PS_IDX_WORDS >= PL_SLOTS / 2 && PS_IDX_WORDS >= PL_MAX + 1, "pair-span geometry");      // (the placement word: fill_pair_word.hpp)
 enum { PS_A_BAD, PS_A_COMPLETE, PS_A_PLACED, PS_A_PROPER, PS_A_MISORIENTED, PS_A_IN_RANGE, PS_A_SHORT, PS_A_LONG, PS_A_SPAN, PS_A_ZERO, PS_A_N };
 
 struct PsParams {
@@ -39,9 +39,6 @@ struct PsParams {
     uint32_t* scratch;
     gf_fill_pairs* out;
 };
-
-// the order of a gap's id slice: mate side, then pair
-__device__ __forceinline__ uint32_t ps_order(uint32_t id) { return ((id & 1u) << 31) | (id >> 1); }
 
 __global__ __launch_bounds__(PL_THREADS) void fill_pairs_kernel(PsParams P) {
     __shared__ uint32_t s_idx[PS_IDX_WORDS];

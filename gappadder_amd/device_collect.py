@@ -155,6 +155,19 @@ def fill_pairs_tsv(pipe, res, kmers):
     return _tsv(picked_names(res, kmers), ("library", "name") + fields + ("span_mean_minus_is",), rows_of)
 
 
+def fill_pairs_anchored_tsv(pipe, res, kmers):
+    """fill_pairs_anchored.tsv of a step with the anchored pair span on: fill_pairs.tsv's rows and order with the fields of the
+    gf_fill_anchors record (Results.pair_anchors), then dev_min_mean = dev_min_sum // dev_min_n and dev_max_mean (empty when n_eval = 0)."""
+    from . import pair_anchors as PAN
+    fields = B.FILL_ANCHORS.names
+
+    def rows_of(g, name):
+        for l in range(len(pipe.libs)):
+            rec = res.pair_anchors[l, g]
+            yield [str(l), name] + [str(int(rec[f])) for f in fields] + ["" if d is None else str(d) for d in PAN.dev_means(rec)]
+    return _tsv(picked_names(res, kmers), ("library", "name") + fields + ("dev_min_mean", "dev_max_mean"), rows_of)
+
+
 def round_keywords(cfg, L, rnd, prefix, names, check, switch):
     """The Pipeline keywords of an optional round of the CLI: <prefix>_<name> = cfg["fill_<rnd>_<name>"] for the names the configuration
     holds, validated against the read length by `check` (its ValueError ends the run), and <switch> = True."""
@@ -507,6 +520,9 @@ class DeviceCollector:
             if cfg.get("fill_polish") and kk else {}
         pairs = round_keywords(cfg, L, "pairs", "pair", ("seed", "max_mismatch", "min_overlap", "z"), PSP.check_params, "pair_span") \
             if cfg.get("fill_pairs") and kk else {}
+        if pairs and cfg.get("fill_pairs_anchored"):
+            from . import pair_anchors as PAN
+            pairs.update(round_keywords(cfg, L, "pairs", "pair", ("seed", "max_mismatch", "min_overlap", "z", "min_pairs"), PAN.check_params, "pair_anchors"))
         pipe = Pipeline(gf, len(gaps), L, kk, device=self.dev, anchor_mapq=self.anchor_mapq, clip_dist=self.clip_dist,
                         k_screen=k_screen or None, keep_read_ids=True, probe_column=False,
                         read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"), **polish, **pairs)
@@ -546,6 +562,8 @@ class DeviceCollector:
             files["polished_seqs.fa"], files["fill_polish.tsv"] = fill_polish_files(pipe, res, cfg["kmers"])
         if res.pairs is not None:
             files["fill_pairs.tsv"] = fill_pairs_tsv(pipe, res, cfg["kmers"])
+        if res.pair_anchors is not None:
+            files["fill_pairs_anchored.tsv"] = fill_pairs_anchored_tsv(pipe, res, cfg["kmers"])
         for name, text in files.items():
             with open(cfg["wf"] + name, "w") as f:
                 f.write(text)

@@ -61,8 +61,14 @@ def parse_configuration(path):
     cfg["fill_polish"] = bool(p.get("fill_polish", False))
     # extension: pair-span check of the fills the device step closes (pair_span.py): {wf}fill_pairs.tsv, one row per closed gap and library
     cfg["fill_pairs"] = bool(p.get("fill_pairs", False))
-    for rnd, own in (("polish", ("min_votes", 2, 1, None)), ("pairs", ("z", 3, 1, None))):     # (name, default, lo, hi) of fill_<round>_<name>
-        for name, default, lo, hi in (("seed", 16, 12, 32), ("max_mismatch", 4, 0, 15), ("min_overlap", 48, 12, None), own):
+    # extension: with fill_pairs, the anchored pair span (pair_anchors.py): {wf}fill_pairs_anchored.tsv, one row per closed gap and library —
+    # the mates anchored in the flanks against the fill; fill_pairs_min_pairs: the pairs a column needs for its mean insert deviation to count
+    cfg["fill_pairs_anchored"] = bool(p.get("fill_pairs_anchored", False))
+    if cfg["fill_pairs_anchored"] and not cfg["fill_pairs"]:
+        raise SystemExit("parameters.fill_pairs_anchored needs fill_pairs: it reads the pair span's placements")
+    # (name, default, lo, hi) of fill_<round>_<name>
+    for rnd, own in (("polish", (("min_votes", 2, 1, None),)), ("pairs", (("z", 3, 1, None), ("min_pairs", 8, 1, None)))):
+        for name, default, lo, hi in (("seed", 16, 12, 32), ("max_mismatch", 4, 0, 15), ("min_overlap", 48, 12, None)) + own:
             key = "fill_%s_%s" % (rnd, name)
             try:
                 v = int(p[key]) if p.get(key) is not None else default
@@ -189,6 +195,9 @@ def main_func(command, sf_config):
         for rnd, files in (("support", "no fill_support.tsv"), ("polish", "no polished_seqs.fa, no fill_polish.tsv"), ("pairs", "no fill_pairs.tsv")):
             if cfg["fill_" + rnd] and (first_round is None or getattr(first_round, rnd) is None):
                 sys.stderr.write("fill_%s: only the first assembly round of the device-resident Collect (-c All) computes it: %s\n" % (rnd, files))
+        if cfg["fill_pairs_anchored"] and (first_round is None or first_round.pair_anchors is None):
+            sys.stderr.write("fill_pairs_anchored: only the first assembly round of the device-resident Collect (-c All) computes it: "
+                             "no fill_pairs_anchored.tsv\n")
         timings["stages_s"]["collect" + ("_and_first_assembly_round" if first_round is not None else "")] = time.perf_counter() - t0
     if command in ("Assembly", "All"):
         t0 = time.perf_counter()

@@ -183,6 +183,8 @@ class PairSpan(FR.FillRound):
             p._chk(p.lib.gf_fill_pairs_dev(p.h, p.pool_ptr[l], self.masks_of(l), lb.d_pool_off.data_ptr(), lb.d_ids.data_ptr(), p.lib_cap, p.L,
                                            *self.shared_args(), *self.params[:3], lb.is_mean, lb.is_sd, self.params[3], self.d_scratch.data_ptr(),
                                            self.d_rec.data_ptr() + l * self.plane, self.d_stats.data_ptr() + 4 * l * B.PS_WORDS), "gf_fill_pairs_dev")
+            if p.anchored is not None:        # (pair_anchors.py: it reads this library's placement words before the next library's replace them)
+                p.anchored.launch_library(l)
 
     def fetch(self, r):
         p = self.p

@@ -41,6 +41,7 @@ import torch
 from . import _lib as B
 from . import extended_fill as EXT
 from . import fill_rounds as FR
+from . import pair_anchors as PAN
 from . import pair_span as PSP
 from . import polish as POL
 from . import read_support as SUP
@@ -81,6 +82,7 @@ class Results:
     the merge round and of the optional rounds are None unless the round ran."""
     merge = rescue = rescue_first = round2 = round2_first = round2_reads = extended = ext = ext_bases = support = support_stats = None
     polish = polish_bases = polish_stats = pairs = pair_stats = lib_pool_off = lib_pool_rows = lib_pool_ids = None
+    pair_anchors = pair_anchor_stats = lib_taghits = None
 
 
 # anchor mode -> its pick, its pick over the contigs from an index on, its extended fill; do its picks leave a selection per contig
@@ -96,7 +98,7 @@ class Pipeline:
                  key_column=True, probe_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False,
                  extended_fill=False, ext_base_cap=None, rescue_round=False, read_support=False, support_k=None, polish=False,
                  polish_seed=16, polish_max_mismatch=4, polish_min_overlap=48, polish_min_votes=2, pair_span=False, pair_seed=16,
-                 pair_max_mismatch=4, pair_min_overlap=48, pair_z=3):
+                 pair_max_mismatch=4, pair_min_overlap=48, pair_z=3, pair_anchors=False, pair_min_pairs=8):
         """gf: a GapFill whose gaps (and flanks, when a library is screened) are set.  k_pairs: [(k, k_velvet)] of
         assemble_gaps.py:87-122.  The screen runs at the SMALLEST k of the list: a read that shares a 51-mer with a flank shares
         its 31-mers too, so this is the superset every assembly k needs (the reference recruits once, then assembles at every k).
@@ -122,7 +124,10 @@ class Pipeline:
         polished_sequences); the step's contigs and picks stay as they are, and read_support keeps describing the UNPOLISHED fill.
         pair_span with pair_seed, pair_max_mismatch, pair_min_overlap, pair_z (pair_span.py): after them, per library, the read pairs of
         every closed gap placed on its (unpolished) winning contig: inserts against is_mean -/+ pair_z * is_sd and the physical coverage
-        of the fill (Results.pairs [n_lib, n_gaps], .pair_stats); it keeps the pools' read ids (keep_read_ids)."""
+        of the fill (Results.pairs [n_lib, n_gaps], .pair_stats); it keeps the pools' read ids (keep_read_ids).
+        pair_anchors with pair_min_pairs (pair_anchors.py; only with pair_span, not with tag_ahead): behind each library's pair span, the
+        mates the tagger found anchored in a flank paired, at their draft coordinates, with the other mate's placement on the fill: the
+        insert-size deviation per column of the fill (Results.pair_anchors [n_lib, n_gaps], .pair_anchor_stats)."""
         # what the options exclude, before anything touches gf or the library
         single_rank = int(world) == 1 and not force_exchange
         k_round2 = min([int(a) for a, _ in k_pairs if 16 <= int(a) <= 64], default=None)
@@ -137,6 +142,8 @@ class Pipeline:
                          (read_support and support_k is None and k_round2 is None, "read_support needs support_k, or a k in 16..64 among k_pairs"),
                          *FR.refusals("polish", polish, single_rank, second_round),
                          *FR.refusals("pair_span", pair_span, single_rank, second_round),
+                         (pair_anchors and not pair_span, "pair_anchors needs pair_span: it reads the pair span's placements"),
+                         *FR.refusals("pair_anchors", pair_anchors, single_rank, second_round),
                          (extended_fill and not single_rank, "extended_fill runs on a single rank"),
                          (extended_fill and len(k_pairs) > B.EXT_MAX_PAIRS, "extended_fill: at most %d (k, kv) pairs" % B.EXT_MAX_PAIRS)):
             if bad:
@@ -150,7 +157,8 @@ class Pipeline:
         self.support = SUP.ReadSupport(self, k_round2 if support_k is None else support_k) if read_support else None
         self.polish = POL.FillPolish(self, polish_seed, polish_max_mismatch, polish_min_overlap, polish_min_votes, read_len) if polish else None
         self.pairs = PSP.PairSpan(self, pair_seed, pair_max_mismatch, pair_min_overlap, pair_z, read_len) if pair_span else None
-        self.after_pick = [r for r in (self.support, self.polish, self.pairs) if r is not None]      # (the order they run in)
+        self.anchored = PAN.PairAnchors(self, pair_min_pairs, read_len) if pair_anchors else None        # (launched by self.pairs, per library)
+        self.after_pick = [r for r in (self.support, self.polish, self.pairs, self.anchored) if r is not None]      # (the order they run in)
         self.gf, self.lib, self.h = gf, B.lib(), gf.handle
         self.n_gaps, self.L, self.kk = int(n_gaps), int(read_len), [(int(a), int(b)) for a, b in k_pairs]
         self.rb = self.lib.gf_packed_read_bytes(self.L)
@@ -731,6 +739,9 @@ class Pipeline:
                 r.lib_pool_rows = [self.d_pools[l * self.lib_cap * self.rb:(l * self.lib_cap + int(o[-1])) * self.rb].cpu().numpy().reshape(-1, self.rb)
                                    for l, o in enumerate(r.lib_pool_off)]
                 r.lib_pool_ids = [lb.d_ids[:int(o[-1])].cpu().numpy().view(np.uint32) for lb, o in zip(self.libs, r.lib_pool_off)]
+            if self.anchored is not None:      # the libraries' tagger hits, clamped to the count: what anchors_of_results reads
+                r.lib_taghits = [np.frombuffer(lb.d_thits[:min(lb.counts["tagger_hits"], lb.hit_cap) * 12].cpu().numpy().tobytes(), dtype=B.TAGHIT)
+                                 for lb in self.libs]
         return r
 
     def extended_sequences(self, res):

@@ -862,6 +862,72 @@ int gf_fill_pairs_dev(gf_ctx* ctx, const void* d_pool_packed, const void* d_nmas
                       const void* d_gap_best, const void* d_ctg_pick_or_null, int anchor_long, int anchor_short, int seed, int max_mismatch,
                       int min_overlap, int is_mean, int is_sd, int z, void* d_place_scratch, void* d_rec, void* d_stats);
 
+/* ---- anchored pair span (csrc/fill_anchor.hip; definition and host twin: gappadder_amd/pair_anchors.py).  Called behind
+ * gf_fill_pairs_dev of the SAME library in the same step, with that call's pool offsets, read ids, shared arguments and d_place_scratch
+ * (an INPUT here: the rows' placement words as that call left them).  A tagger hit h of [0, min(*d_n_taghits, hit_cap)) with to_mate == 1
+ * and kind GF_KIND_DISCORDANT or GF_KIND_UNMAP says: record A = d_recs[h.rec] is anchored in a flank of gap h.gap and A's mate B = A.read ^ 1
+ * was recruited for it.  The hit is kept when A has clipflag == 0, flag & (0x100 | 0x800 | 4) == 0, a read (the low 32 bits of A.read are
+ * not 0xFFFFFFFF), A0 = A.pos - 1 < gap.start (a left anchor) or >= gap.end (a right one), and B has a row in the gap's id slice; of
+ * several kept hits of one (gap, B) the one with the smallest (A0 << 1 | sA), sA = (flag >> 4) & 1, counts.  For a closed gap with the
+ * winning contig c (n bases, strand bit rev, body [b0, b1): all as gf_fill_pairs_dev) A lies, virtually and unbounded, on
+ *   rev = 0: strand sA,     column b0 - (start - A0) (left) or b1 + (A0 - end) (right)
+ *   rev = 1: strand 1 - sA, column b1 + (start - A0) - read_len (left) or b0 - (A0 - end) - read_len (right)
+ * and together with a PLACED row B it is one placed pair, classified word for word as gf_fill_pairs_dev classifies its pairs (proper /
+ * misoriented, insert, in range / short / long against is_mean -/+ z * is_sd, spanning).  Every in-range pair covers the columns
+ * [max(0, d_f), min(n, d_r + read_len)) with dev = insert - is_mean: min_cover, min_col, n_unspanned over the body as there, and among the
+ * body columns covered by at least min_pairs pairs (n_eval of them) the one with the smallest and the one with the largest mean dev, as
+ * (column, pairs, sum of dev); means are compared exactly, the smaller column wins a tie.  A contig gf_fill_pairs_dev skips is skipped
+ * (flags and rows); an open gap and a mismatch get the zero record.  min_pairs >= 1, z >= 1, is_sd >= 0, z * is_sd < 2^20:
+ * GF_E_UNSUPPORTED otherwise.  d_anchor: u64 per pool row (pool_cap_rows of them; overwritten).  d_rec: gf_fill_anchors per gap;
+ * d_stats: u32[GF_PA_WORDS] (set by the call).  Two kernels on the context's stream, no host synchronisation. */
+typedef struct {
+    uint32_t flags;            /* GF_PS_F_* */
+    uint32_t rows;             /* rows of the library's pool for the gap */
+    uint32_t n_anchored;       /* rows whose mate is anchored in a flank */
+    uint32_t n_placed;         /* ... and that are PLACED: the placed pairs */
+    uint32_t n_proper;
+    uint32_t n_misoriented;
+    uint32_t n_in_range;
+    uint32_t n_short;
+    uint32_t n_long;
+    uint32_t n_left;           /* in-range pairs with a left anchor */
+    uint32_t n_span;           /* proper pairs that span the body */
+    uint32_t n_cols;           /* body columns */
+    int64_t span_insert_sum;   /* the sum of the spanning pairs' inserts */
+    int64_t dev_sum;           /* the sum of insert - is_mean over the in-range pairs */
+    uint32_t min_cover;        /* the fewest in-range pairs over a body column */
+    uint32_t min_col;          /* the first column with that few */
+    uint32_t n_unspanned;      /* body columns no in-range pair covers */
+    uint32_t n_eval;           /* body columns with at least min_pairs in-range pairs */
+    uint32_t dev_min_col;      /* of those, the column with the smallest mean dev: its pairs and their sum of dev */
+    uint32_t dev_min_n;
+    int64_t dev_min_sum;
+    uint32_t dev_max_col;      /* ... and the one with the largest */
+    uint32_t dev_max_n;
+    int64_t dev_max_sum;
+} gf_fill_anchors;
+#define GF_PA_GAPS 0           /* gaps examined (not skipped) */
+#define GF_PA_MISMATCH 1
+#define GF_PA_SKIPPED_LONG 2
+#define GF_PA_SKIPPED_NON_ACGT 3
+#define GF_PA_KEPT 4           /* hits kept (before the smallest of a (gap, read) is chosen) */
+#define GF_PA_DROP_CLIPPED 5   /* hits dropped: a clipped anchor */
+#define GF_PA_DROP_IN_GAP 6    /* ... an anchor that starts inside the gap */
+#define GF_PA_DROP_SECONDARY 7 /* ... a secondary or supplementary record */
+#define GF_PA_ABSENT 8         /* ... the mate has no row in the gap's slice */
+#define GF_PA_DROP_OTHER 9     /* ... to_mate == 0, another kind, an unmapped record, no read, a record or gap out of range */
+#define GF_PA_ANCHORED 10      /* u64 each: anchored, placed, proper, in-range, spanning pairs */
+#define GF_PA_PLACED 12
+#define GF_PA_PROPER 14
+#define GF_PA_IN_RANGE 16
+#define GF_PA_SPAN 18
+#define GF_PA_WORDS 20
+int gf_fill_pairs_anchored_dev(gf_ctx* ctx, const void* d_pool_off, const void* d_pool_read_ids, size_t pool_cap_rows, int read_len,
+                               const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, const void* d_gap_best,
+                               const void* d_ctg_pick_or_null, int anchor_long, int anchor_short, const void* d_place_scratch,
+                               const void* d_recs, size_t n_recs, const void* d_taghits, const void* d_n_taghits, size_t hit_cap, int is_mean,
+                               int is_sd, int z, int min_pairs, void* d_anchor, void* d_rec, void* d_stats);
+
 /* ---- the second assembly round inside the step (assemble_gaps.py:328-368 with collect_both_unmapped_reads.py's recruitment; DESIGN.md
  * "Second round").  Predicate (the CLI's kmer_recruit_unmapped): a both-unmapped pair is recruited for an open gap when one of its reads shares
  * a canonical k-mer with one of the gap's round-1 contigs; k-mers touching a non-ACGT contig base or an N-masked read base do not count.
@@ -980,6 +1046,7 @@ int gf_memset_dev(gf_ctx* ctx, void* d_ptr, int value, size_t bytes);
 #define GF_KERNEL_SUPPORT 11  /* read support of the closed gaps */
 #define GF_KERNEL_POLISH 12  /* consensus polish of the closed gaps */
 #define GF_KERNEL_PAIRS 13  /* pair-span check of the closed gaps */
+#define GF_KERNEL_ANCHORS 14  /* anchored pair span of the closed gaps */
 int gf_timing_enable(gf_ctx* ctx, int on);
 int gf_timing_read(gf_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int gf_timing_reset(gf_ctx* ctx);
