@@ -35,7 +35,7 @@ assert CONTIG.itemsize == 32 and EXT_PICK.itemsize == 40 and GAP.itemsize == 16 
 GF_OK, GF_E_INVAL, GF_E_NODEV, GF_E_NOMEM, GF_E_NOSPACE, GF_E_STATE, GF_E_UNSUPPORTED, GF_E_FORMAT = 0, -1, -2, -3, -4, -5, -6, -7
 KIND_CLIP, KIND_DISCORDANT, KIND_UNMAP, KIND_LOWMAPQ = 0, 1, 2, 3
 KIND_NAMES = {KIND_CLIP: "clip", KIND_DISCORDANT: "discordant", KIND_UNMAP: "unmap"}
-KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT, KERNEL_POLISH, KERNEL_PAIRS, KERNEL_ANCHORS = range(15)
+KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT, KERNEL_POLISH, KERNEL_PAIRS, KERNEL_ANCHORS, KERNEL_GAPSPAN = range(16)
 
 # words of the merge round's statistics (gf_merge_open_gaps_dev, u32[32])
 MG_N_PRE, MG_N_SETS, MG_SKIPPED, MG_N_PAIRS, MG_QC_FLAGS, MG_N_JOBS, MG_ERR, MG_N0, MG_N_EDGES, MG_SETS_WITH_JOBS = range(10)
@@ -105,6 +105,15 @@ FILL_ANCHORS = np.dtype([("flags", "<u4"), ("rows", "<u4"), ("n_anchored", "<u4"
 assert FILL_ANCHORS.itemsize == 112
 (PA_GAPS, PA_MISMATCH, PA_SKIPPED_LONG, PA_SKIPPED_NON_ACGT, PA_KEPT, PA_DROP_CLIPPED, PA_DROP_IN_GAP, PA_DROP_SECONDARY, PA_ABSENT,
  PA_DROP_OTHER, PA_ANCHORED, PA_PLACED, PA_PROPER, PA_IN_RANGE, PA_SPAN, PA_WORDS) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 14, 16, 18, 20
+
+# the gap-size measurement (gf_gap_span_dev): the record per (library, gap), its flag (n >= 1) and the words of its statistics (u32[16]):
+# u64 each: candidates, accepted, multi, clipped, lowq, low, high; then u32 gaps with n >= 1
+GAP_SPAN = np.dtype([("flags", "<u4"), ("n_cand", "<u4"), ("n", "<u4"), ("n_multi", "<u4"), ("n_clipped", "<u4"), ("n_lowq", "<u4"),
+                     ("n_low", "<u4"), ("n_high", "<u4"), ("tlen_min", "<u4"), ("tlen_max", "<u4"), ("sum", "<i8"), ("sum_sq", "<u8"),
+                     ("reserved", "<u8")])
+assert GAP_SPAN.itemsize == 64
+GS_F_PAIRS = 1
+GS_CANDIDATES, GS_ACCEPTED, GS_MULTI, GS_CLIPPED, GS_LOWQ, GS_LOW, GS_HIGH, GS_GAPS_WITH_PAIRS, GS_WORDS = 0, 2, 4, 6, 8, 10, 12, 14, 16
 
 _lib = None
 
@@ -237,6 +246,7 @@ def lib():
         "gf_fill_polish_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
         "gf_fill_pairs_dev": (i32, [vp, vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
         "gf_fill_pairs_anchored_dev": (i32, [vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, vp, vp, sz, vp, vp, sz, i32, i32, i32, i32, vp, vp, vp]),
+        "gf_gap_span_dev": (i32, [vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp, vp]),
         "gf_contigs_append_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp]),
         "gf_rescue_work_bytes": (sz, [sz, sz, sz, i32]),
         "gf_rescue_reset_dev": (i32, [vp, vp, sz, sz, sz, i32, vp]),

@@ -466,6 +466,13 @@ int gf_tag_alignments_keys_dev(gf_ctx* ctx, const void* d_recs, const void* d_ke
     return launch_tag(ctx, d_recs, n, insert_size, sd, clip_dist, anchor_mapq, d_out, cap, d_n_out, d_low, low_cap, d_n_low, d_keys);
 }
 
+int gf_gap_span_dev(gf_ctx* ctx, const void* d_recs, const void* d_keys_or_null, size_t n, int read_len, int is_mean, int is_sd, int z, int shift,
+                    int min_mapq, void* d_rec, void* d_stats) {
+    if (!ctx || !d_rec || !d_stats || (n && !d_recs)) return GF_E_INVAL;
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_gap_span(ctx, d_recs, d_keys_or_null, n, read_len, is_mean, is_sd, z, shift, min_mapq, d_rec, d_stats);
+}
+
 int gf_tag_low_mapq_compact_dev(gf_ctx* ctx, const void* d_low, const void* d_n_low, size_t low_cap, const gf_dpos* table,
                                 size_t n_rows, void* d_out, size_t cap, void* d_n_out) {
     if (!ctx || !d_n_out || !d_low || !d_n_low || (cap && !d_out) || (n_rows && !table)) return GF_E_INVAL;

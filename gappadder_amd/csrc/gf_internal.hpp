@@ -14,7 +14,7 @@ namespace gf {
 
 constexpr uint32_t EMPTY32 = 0xFFFFFFFFu;
 constexpr int TILE_READS = 256;  // reads staged per workgroup pass of the screen filter
-constexpr int N_KERNEL_SLOTS = 15;
+constexpr int N_KERNEL_SLOTS = 16;
 
 // flank k-mer index for one k: three levels, all read-only on the device
 struct FlankIndex {
@@ -251,6 +251,12 @@ int launch_screen(gf_ctx* ctx, const FlankIndex& ix, const void* d_reads, const 
 int launch_tag(gf_ctx* ctx, const void* d_recs, size_t n, int insert_size, int sd, int clip_dist, int anchor_mapq,
                void* d_out, size_t cap, void* d_n_out, void* d_low, size_t low_cap, void* d_n_low, const void* d_keys = nullptr);
 int launch_alnrec_keys(gf_ctx* ctx, const void* d_recs, size_t n, void* d_keys);
+// the coarse (and, where it pays, fine) bin map of the gap windows for one dist2, built on first use and kept (the four last used): the
+// tagger's, shared with the gap-span pass (gap_span.hip), which asks for the tagger's own dist2 so that a library keeps ONE map
+int ensure_bin_map(gf_ctx* ctx, int dist2, gf_ctx::TagMap** out);
+// gap_span.hip
+int launch_gap_span(gf_ctx* ctx, const void* d_recs, const void* d_keys, size_t n, int read_len, int is_mean, int is_sd, int z, int shift,
+                    int min_mapq, void* d_rec, void* d_stats);
 int launch_low_mapq(gf_ctx* ctx, const void* d_recs, size_t n, const gf_dpos* table, size_t n_rows, void* d_out,
                     size_t cap, void* d_n_out, const void* d_low, const void* d_n_low, size_t low_cap);
 

@@ -569,7 +569,7 @@ void drop_tag_maps(gf_ctx* ctx) {
 
 // Coarse bin map of the gap windows for one dist2 (host build: n_gaps work; kept until the gaps change, the four last used dist2).
 // Bits cover, per scaffold, positions 0 .. last window end; everything beyond has no window.
-static int ensure_bin_map(gf_ctx* ctx, int dist2, gf_ctx::TagMap** out) {
+int ensure_bin_map(gf_ctx* ctx, int dist2, gf_ctx::TagMap** out) {
     for (gf_ctx::TagMap& m : ctx->tag_maps)
         if (m.dist2 == dist2 && m.map.p) { m.used = ++ctx->tag_map_clock; *out = &m; return GF_OK; }
     if (ctx->tag_maps.size() >= 4) {   // drop the one that was not used for the longest time

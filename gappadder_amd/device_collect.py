@@ -168,6 +168,30 @@ def fill_pairs_anchored_tsv(pipe, res, kmers):
     return _tsv(picked_names(res, kmers), ("library", "name") + fields + ("dev_min_mean", "dev_max_mean"), rows_of)
 
 
+def gap_span_tsv(pipe, res, gaps, kmers):
+    """gap_span.tsv of a step with the gap-span round on: under a header line one row per gap and library, in gap order and, per gap,
+    library order: the library's index, the gap's name (as in picked_seqs.fa for a gap the device step closed, the gap id for an open one),
+    G0 = end - start, the fields of the gf_gap_span record (Results.gap_span), naive / est / se of gap_span.estimate (empty cells below
+    min_pairs) and, for a closed gap, the length of the picked fill and fill_len - est (empty otherwise)."""
+    from . import gap_span as GSP
+    fields = B.GAP_SPAN.names[:-1]            # (not the reserved word)
+    closed = picked_names(res, kmers) if np.count_nonzero(res.best) else {}
+    fills = pipe.picked_sequences(res) if closed else {}
+    gs = pipe.gap_span
+    rows = [("library", "name", "G0") + fields + ("naive", "est", "se", "fill_len", "fill_len_minus_est")]
+    for g in range(len(gaps)):
+        g0 = int(gaps[g]["end"]) - int(gaps[g]["start"])
+        for l, lb in enumerate(pipe.libs):
+            rec = res.gap_span[l, g]
+            e = GSP.estimate(rec, g0, pipe.L, lb.is_mean, lb.is_sd, gs.z, gs.shift, gs.min_pairs)
+            cells = [str(l), closed.get(g, res.keys[g]), str(g0)] + [str(int(rec[f])) for f in fields]
+            cells += ["", "", ""] if e is None else ["%.2f" % e.naive, "%.2f" % e.est, "%.2f" % e.se]
+            fl = len(fills[g][1]) if g in fills else None
+            cells += ["" if fl is None else str(fl), "" if fl is None or e is None else "%.2f" % (fl - e.est)]
+            rows.append(cells)
+    return "".join("\t".join(c) + "\n" for c in rows)
+
+
 def round_keywords(cfg, L, rnd, prefix, names, check, switch):
     """The Pipeline keywords of an optional round of the CLI: <prefix>_<name> = cfg["fill_<rnd>_<name>"] for the names the configuration
     holds, validated against the read length by `check` (its ValueError ends the run), and <switch> = True."""
@@ -523,9 +547,19 @@ class DeviceCollector:
         if pairs and cfg.get("fill_pairs_anchored"):
             from . import pair_anchors as PAN
             pairs.update(round_keywords(cfg, L, "pairs", "pair", ("seed", "max_mismatch", "min_overlap", "z", "min_pairs"), PAN.check_params, "pair_anchors"))
+        span = {}
+        if cfg.get("gap_span"):
+            from . import gap_span as GSP
+            span = dict(gap_span=True, span_shift=cfg.get("gap_span_shift", GSP.SHIFT), span_min_pairs=cfg.get("gap_span_min_pairs", GSP.MIN_PAIRS))
+            try:
+                GSP.check_params(GSP.Z, span["span_shift"], span["span_min_pairs"])
+                for _, is_, sd in cfg["alignments"]:
+                    GSP.window(is_, sd, GSP.Z, span["span_shift"])
+            except ValueError as e:
+                raise SystemExit("parameters.gap_span_*: %s" % e)
         pipe = Pipeline(gf, len(gaps), L, kk, device=self.dev, anchor_mapq=self.anchor_mapq, clip_dist=self.clip_dist,
                         k_screen=k_screen or None, keep_read_ids=True, probe_column=False,
-                        read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"), **polish, **pairs)
+                        read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"), **polish, **pairs, **span)
         # (no probe column on the file path: a file-born library is screened once, and until the packing kernels write the column while
         # they hold the bases, building it is a pass of its own — 38 B read + 4 np written per read — that costs more than pass A saves)
         pipe.assemble_in_step = False
@@ -564,6 +598,8 @@ class DeviceCollector:
             files["fill_pairs.tsv"] = fill_pairs_tsv(pipe, res, cfg["kmers"])
         if res.pair_anchors is not None:
             files["fill_pairs_anchored.tsv"] = fill_pairs_anchored_tsv(pipe, res, cfg["kmers"])
+        if res.gap_span is not None:
+            files["gap_span.tsv"] = gap_span_tsv(pipe, res, gaps, cfg["kmers"])
         for name, text in files.items():
             with open(cfg["wf"] + name, "w") as f:
                 f.write(text)

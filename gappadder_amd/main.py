@@ -80,6 +80,16 @@ def parse_configuration(path):
         if cfg["fill_%s_min_overlap" % rnd] < cfg["fill_%s_seed" % rnd]:
             raise SystemExit("parameters.fill_%s_min_overlap must be at least fill_%s_seed (%d), not %d"
                              % (rnd, rnd, cfg["fill_%s_seed" % rnd], cfg["fill_%s_min_overlap" % rnd]))
+    # extension: the size of every gap, open or closed, from the read pairs that span it (gap_span.py): {wf}gap_span.tsv, one row per gap
+    # and library; gap_span_shift: how far off the draft's N-run may be; gap_span_min_pairs: the pairs an estimate needs
+    cfg["gap_span"] = bool(p.get("gap_span", False))
+    for key, default, lo in (("gap_span_shift", 1000, 0), ("gap_span_min_pairs", 8, 1)):
+        v = p.get(key)
+        if v is None:
+            v = default
+        if isinstance(v, bool) or not isinstance(v, int) or v < lo:
+            raise SystemExit("parameters.%s must be an integer, at least %d, not %r" % (key, lo, p[key]))
+        cfg[key] = v
     for path_, what in [(cfg["draft"], "draft genome")] + [(a[0], "bam") for a in cfg["alignments"]] + \
                        [(x, "raw reads") for pair in cfg["raw_reads"] for x in pair] + [(cfg["wf"], "working folder")]:
         if not os.path.exists(path_):
@@ -198,6 +208,8 @@ def main_func(command, sf_config):
         if cfg["fill_pairs_anchored"] and (first_round is None or first_round.pair_anchors is None):
             sys.stderr.write("fill_pairs_anchored: only the first assembly round of the device-resident Collect (-c All) computes it: "
                              "no fill_pairs_anchored.tsv\n")
+        if cfg["gap_span"] and not done:
+            sys.stderr.write("gap_span: only the device-resident Collect computes it: no gap_span.tsv\n")
         timings["stages_s"]["collect" + ("_and_first_assembly_round" if first_round is not None else "")] = time.perf_counter() - t0
     if command in ("Assembly", "All"):
         t0 = time.perf_counter()

@@ -25,6 +25,7 @@ What the reference does with files between processes —
     gf_fill_support_dev                                        how the pool of every closed gap backs the k-mers of its fill (read_support.py)
     gf_fill_polish_dev                                         the pool of every closed gap piled up on its fill: a vote per column (polish.py)
     gf_fill_pairs_dev                                          per library: the read pairs of every closed gap placed on its fill (pair_span.py)
+    gf_gap_span_dev                                            per library, behind its tagger: the size of every gap from the pairs that span it (gap_span.py)
 
 `Pipeline` owns the sizing pass (capacities follow what the libraries actually recruit), every buffer of the core step, the stream
 wiring and — in a multi-rank run — the one exchange step; an optional round keeps its buffers, sizing, launches and
@@ -41,6 +42,7 @@ import torch
 from . import _lib as B
 from . import extended_fill as EXT
 from . import fill_rounds as FR
+from . import gap_span as GSP
 from . import pair_anchors as PAN
 from . import pair_span as PSP
 from . import polish as POL
@@ -82,7 +84,7 @@ class Results:
     the merge round and of the optional rounds are None unless the round ran."""
     merge = rescue = rescue_first = round2 = round2_first = round2_reads = extended = ext = ext_bases = support = support_stats = None
     polish = polish_bases = polish_stats = pairs = pair_stats = lib_pool_off = lib_pool_rows = lib_pool_ids = None
-    pair_anchors = pair_anchor_stats = lib_taghits = None
+    pair_anchors = pair_anchor_stats = lib_taghits = gap_span = gap_span_stats = None
 
 
 # anchor mode -> its pick, its pick over the contigs from an index on, its extended fill; do its picks leave a selection per contig
@@ -98,7 +100,8 @@ class Pipeline:
                  key_column=True, probe_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False,
                  extended_fill=False, ext_base_cap=None, rescue_round=False, read_support=False, support_k=None, polish=False,
                  polish_seed=16, polish_max_mismatch=4, polish_min_overlap=48, polish_min_votes=2, pair_span=False, pair_seed=16,
-                 pair_max_mismatch=4, pair_min_overlap=48, pair_z=3, pair_anchors=False, pair_min_pairs=8):
+                 pair_max_mismatch=4, pair_min_overlap=48, pair_z=3, pair_anchors=False, pair_min_pairs=8, gap_span=False, span_z=3,
+                 span_shift=1000, span_min_pairs=8):
         """gf: a GapFill whose gaps (and flanks, when a library is screened) are set.  k_pairs: [(k, k_velvet)] of
         assemble_gaps.py:87-122.  The screen runs at the SMALLEST k of the list: a read that shares a 51-mer with a flank shares
         its 31-mers too, so this is the superset every assembly k needs (the reference recruits once, then assembles at every k).
@@ -127,7 +130,11 @@ class Pipeline:
         of the fill (Results.pairs [n_lib, n_gaps], .pair_stats); it keeps the pools' read ids (keep_read_ids).
         pair_anchors with pair_min_pairs (pair_anchors.py; only with pair_span, not with tag_ahead): behind each library's pair span, the
         mates the tagger found anchored in a flank paired, at their draft coordinates, with the other mate's placement on the fill: the
-        insert-size deviation per column of the fill (Results.pair_anchors [n_lib, n_gaps], .pair_anchor_stats)."""
+        insert-size deviation per column of the fill (Results.pair_anchors [n_lib, n_gaps], .pair_anchor_stats).
+        gap_span with span_z, span_shift, span_min_pairs (gap_span.py): per library, behind its tagger pass and on the tagger's stream, the
+        read pairs whose mates map cleanly on either side of a gap, for EVERY gap, open or closed: their number and the sums of their
+        template lengths (Results.gap_span [n_lib, n_gaps], .gap_span_stats; gap_span.estimate turns a record into a gap size).  It reads the
+        libraries' records and the gap table only, so it goes with every other option, tag_ahead included; single rank."""
         # what the options exclude, before anything touches gf or the library
         single_rank = int(world) == 1 and not force_exchange
         k_round2 = min([int(a) for a, _ in k_pairs if 16 <= int(a) <= 64], default=None)
@@ -144,6 +151,7 @@ class Pipeline:
                          *FR.refusals("pair_span", pair_span, single_rank, second_round),
                          (pair_anchors and not pair_span, "pair_anchors needs pair_span: it reads the pair span's placements"),
                          *FR.refusals("pair_anchors", pair_anchors, single_rank, second_round),
+                         (gap_span and not single_rank, "gap_span runs on a single rank: the sums are additive over ranks, and that reduction is left out"),
                          (extended_fill and not single_rank, "extended_fill runs on a single rank"),
                          (extended_fill and len(k_pairs) > B.EXT_MAX_PAIRS, "extended_fill: at most %d (k, kv) pairs" % B.EXT_MAX_PAIRS)):
             if bad:
@@ -159,6 +167,7 @@ class Pipeline:
         self.pairs = PSP.PairSpan(self, pair_seed, pair_max_mismatch, pair_min_overlap, pair_z, read_len) if pair_span else None
         self.anchored = PAN.PairAnchors(self, pair_min_pairs, read_len) if pair_anchors else None        # (launched by self.pairs, per library)
         self.after_pick = [r for r in (self.support, self.polish, self.pairs, self.anchored) if r is not None]      # (the order they run in)
+        self.gap_span = GSP.GapSpan(self, span_z, span_shift, span_min_pairs) if gap_span else None      # (launched behind every tagger pass, per library)
         self.gf, self.lib, self.h = gf, B.lib(), gf.handle
         self.n_gaps, self.L, self.kk = int(n_gaps), int(read_len), [(int(a), int(b)) for a, b in k_pairs]
         self.rb = self.lib.gf_packed_read_bytes(self.L)
@@ -218,6 +227,8 @@ class Pipeline:
         more (the device calls report their counts beyond the capacity) and sizes again; a STEP that outgrows them later fails loudly
         in fetch()."""
         assert not self.prepared
+        if self.gap_span is not None:
+            self.gap_span.check_library(lb)        # (ValueError before anything touches the library)
         dev = self.dev
         lb.h2 = lb.tag_ctx.handle if lb.tag_ctx is not None else self.h
         lb.second_stream = lb.h2.value != self.h.value
@@ -287,6 +298,11 @@ class Pipeline:
             self.tagger(lb)
 
     def tagger(self, lb):
+        self._tag(lb)
+        if self.gap_span is not None:      # the same records once more, on the same stream: the pairs that span a gap
+            self.gap_span.enqueue(lb)
+
+    def _tag(self, lb):
         if self.key_column and lb.d_rec_keys is not None:
             self._chk(self.lib.gf_tag_alignments_keys_dev(lb.h2, lb.d_recs.data_ptr(), lb.d_rec_keys.data_ptr(), lb.n_recs, lb.is_mean, lb.is_sd, self.clip_dist,
                                                           self.anchor_mapq, lb.d_thits.data_ptr(), lb.hit_cap, lb.cp + 4 * CNT_TAG, lb.d_low.data_ptr(),
@@ -365,6 +381,8 @@ class Pipeline:
         lib, h, dev, world, n_gaps, rb = self.lib, self.h, self.dev, self.world, self.n_gaps, self.rb
         n_lib = len(self.libs)
         assert n_lib >= 1
+        if self.gap_span is not None:      # (before the first tagger pass: every pass, the sizing ones included, leaves the records)
+            self.gap_span.prepare()
         torch.cuda.synchronize()
         for attempt in range(4):
             self.screen_dropped = 0
@@ -731,6 +749,8 @@ class Pipeline:
             self.ext.fetch(r)
         for rnd in self.after_pick if self.kk else ():
             rnd.fetch(r)
+        if self.gap_span is not None:
+            self.gap_span.fetch(r)
         if pools:
             r.pool_off = r.asm_off_t.cpu().numpy().astype(np.int64)
             r.pool_rows = r.asm_pool_t[:r.asm_rows_total * self.rb].cpu().numpy().reshape(-1, self.rb)

@@ -928,6 +928,49 @@ int gf_fill_pairs_anchored_dev(gf_ctx* ctx, const void* d_pool_off, const void* 
                                const void* d_recs, size_t n_recs, const void* d_taghits, const void* d_n_taghits, size_t hit_cap, int is_mean,
                                int is_sd, int z, int min_pairs, void* d_anchor, void* d_rec, void* d_stats);
 
+/* ---- gap size from the gap-spanning read pairs (csrc/gap_span.hip; definition and host twin: gappadder_amd/gap_span.py).
+ * One library's records against the gap table of gf_set_gaps, for EVERY gap, open or closed; it needs neither the recruitment nor a contig.
+ * With dist2 = is_mean + 3 * is_sd (the tagger's own window: the call shares the tagger's bin map for that dist2), lo = is_mean - z * is_sd -
+ * shift, hi = is_mean + z * is_sd + shift: record A is a CANDIDATE of gap g = [start, end) on scaffold s iff flag & 1, flag & (4 | 8 | 0x100 |
+ * 0x800) == 0, flag & 0x10 == 0 and flag & 0x20 != 0 (A forward, its mate reverse), ref == mate_ref == s < n_scaffolds, pos >= 1,
+ * mate_pos >= 1, tlen > 0, and with A0 = pos - 1, M0 = mate_pos - 1, M1 = A0 + tlen: A0 + read_len <= start, start - A0 <= dist2,
+ * end <= M0 < M1.  The mate's own MAPQ and clip flag are not in A's record and are not consulted.  A candidate lands in exactly one
+ * counter, tested in this order: n_multi (end[g - 1] > A0 or start[g + 1] < M1, each for a neighbour on the same scaffold), n_clipped
+ * (clipflag != 0), n_lowq (mapq < min_mapq), n_low (tlen < lo), n_high (tlen > hi), else accepted: n, sum, sum_sq, tlen_min, tlen_max.
+ * d_keys_or_null: the library's key column (gf_alnrec_keys_dev; n + 1 entries) — streamed instead of the records, which are then fetched
+ * only for what passes the bin maps; a key that disagrees with its record drops the record.  A record with ref >= n_scaffolds or '*', on
+ * a scaffold without gaps or beyond the bin map's span is ignored and indexes nothing.  z >= 1, shift >= 0, is_mean >= 0, is_sd >= 0,
+ * 1 <= read_len, 0 <= min_mapq <= 255, hi < 2^20 (sum_sq then fits 64 bits for every n < 2^32): GF_E_UNSUPPORTED otherwise; GF_E_STATE
+ * without gaps.  d_rec: gf_gap_span per gap; d_stats: u32[GF_GS_WORDS]; both are cleared and set by the call, on the context's stream,
+ * without a host synchronisation (but for the first use of a dist2 on the context, which builds its bin map as the tagger would). */
+typedef struct {
+    uint32_t flags;      /* GF_GS_F_PAIRS iff n >= 1 */
+    uint32_t n_cand;     /* candidates: the seven counters below together */
+    uint32_t n;          /* accepted pairs */
+    uint32_t n_multi;
+    uint32_t n_clipped;
+    uint32_t n_lowq;
+    uint32_t n_low;
+    uint32_t n_high;
+    uint32_t tlen_min;   /* of the accepted pairs; 0 when n == 0 */
+    uint32_t tlen_max;
+    int64_t sum;         /* of the accepted pairs' tlen */
+    uint64_t sum_sq;     /* ... of tlen^2 */
+    uint64_t reserved;
+} gf_gap_span;
+#define GF_GS_F_PAIRS 1
+#define GF_GS_CANDIDATES 0     /* u64 each, over the gaps: candidates, accepted, multi, clipped, lowq, low, high */
+#define GF_GS_ACCEPTED 2
+#define GF_GS_MULTI 4
+#define GF_GS_CLIPPED 6
+#define GF_GS_LOWQ 8
+#define GF_GS_LOW 10
+#define GF_GS_HIGH 12
+#define GF_GS_GAPS_WITH_PAIRS 14   /* u32: gaps with n >= 1 */
+#define GF_GS_WORDS 16
+int gf_gap_span_dev(gf_ctx* ctx, const void* d_recs, const void* d_keys_or_null, size_t n, int read_len, int is_mean, int is_sd, int z,
+                    int shift, int min_mapq, void* d_rec, void* d_stats);
+
 /* ---- the second assembly round inside the step (assemble_gaps.py:328-368 with collect_both_unmapped_reads.py's recruitment; DESIGN.md
  * "Second round").  Predicate (the CLI's kmer_recruit_unmapped): a both-unmapped pair is recruited for an open gap when one of its reads shares
  * a canonical k-mer with one of the gap's round-1 contigs; k-mers touching a non-ACGT contig base or an N-masked read base do not count.
@@ -1047,6 +1090,7 @@ int gf_memset_dev(gf_ctx* ctx, void* d_ptr, int value, size_t bytes);
 #define GF_KERNEL_POLISH 12  /* consensus polish of the closed gaps */
 #define GF_KERNEL_PAIRS 13  /* pair-span check of the closed gaps */
 #define GF_KERNEL_ANCHORS 14  /* anchored pair span of the closed gaps */
+#define GF_KERNEL_GAPSPAN 15  /* gap-size measurement from the gap-spanning pairs */
 int gf_timing_enable(gf_ctx* ctx, int on);
 int gf_timing_read(gf_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int gf_timing_reset(gf_ctx* ctx);
