@@ -128,6 +128,25 @@ class ProbeColumnGeom(C.Structure):
         return (self.n_reads, self.read_len, self.k, self.first, self.stride, self.np, self.ext)
 
 
+class TagLayout(C.Structure):
+    """gf_tag_layout: the linear layout a library's 4-byte key column was built for (include/gapfill_hip.h)."""
+    _fields_ = [("n_recs", C.c_uint64), ("span", C.c_uint64), ("checksum", C.c_uint64), ("n_scaffolds", C.c_uint32),
+                ("granule_log2", C.c_uint32), ("use", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def key(self):
+        """What a column and its tag maps depend on (not `use`, which is advice, nor the reserved word)."""
+        return (self.n_recs, self.n_scaffolds, self.granule_log2, self.checksum)
+
+
+def linkeys_layout(n, n_scaffolds):
+    """The parts of a linear key column of n records (gf_alnrec_linkeys_bytes), in 32-bit words: (key words, first plane word, plane words,
+    first base word, words in all)."""
+    key_words = ((n + 3) & ~3) + 4
+    plane_at = (key_words * 4 + 31) // 32 * 8
+    plane_words = (n + 255) // 256 * 8
+    return key_words, plane_at, plane_words, plane_at + plane_words, plane_at + plane_words + n_scaffolds + 1
+
+
 class MergeCaps(C.Structure):
     """gf_mcaps: capacities of gf_merge_sets' output lists."""
     _fields_ = [(n, C.c_size_t) for n in ("edges", "news", "path_bytes", "seq_bytes", "finals")]
@@ -210,6 +229,11 @@ def lib():
         "gf_tag_low_mapq_compact_dev": (i32, [vp, vp, vp, sz, vp, sz, vp, sz, vp]),
         "gf_alnrec_keys_dev": (i32, [vp, vp, sz, vp]),
         "gf_tag_alignments_keys_dev": (i32, [vp, vp, vp, sz, i32, i32, i32, i32, vp, sz, vp, vp, sz, vp]),
+        "gf_tag_layout_from_ends": (i32, [vp, u32, C.c_uint64, C.POINTER(TagLayout), vp]),
+        "gf_alnrec_linkeys_bytes": (sz, [sz, u32]),
+        "gf_alnrec_linkeys_dev": (i32, [vp, vp, sz, vp, sz, C.POINTER(TagLayout)]),
+        "gf_tag_alignments_linkeys_dev": (i32, [vp, vp, vp, C.POINTER(TagLayout), vp, sz, i32, i32, i32, i32, vp, sz, vp, vp, sz, vp]),
+        "gf_tag_last_launch": (i32, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
         "gf_assemble": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, i32, i32, i32, vp, sz, szp, vp, sz, szp]),
         "gf_assemble_dev": (i32, [vp, vp, vp, vp, sz, sz, i32, i32, i32, i32, i32, vp, sz, vp, vp, sz, vp, vp]),
         "gf_assemble_multi_dev": (i32, [vp, vp, vp, vp, sz, sz, i32, vp, vp, i32, i32, i32, vp, sz, vp, vp, sz, vp, vp]),

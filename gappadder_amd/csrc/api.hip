@@ -466,6 +466,37 @@ int gf_tag_alignments_keys_dev(gf_ctx* ctx, const void* d_recs, const void* d_ke
     return launch_tag(ctx, d_recs, n, insert_size, sd, clip_dist, anchor_mapq, d_out, cap, d_n_out, d_low, low_cap, d_n_low, d_keys);
 }
 
+int gf_tag_layout_from_ends(const uint32_t* ends, uint32_t n_scaffolds, uint64_t n_recs, gf_tag_layout* out, uint32_t* base_or_null) {
+    if (!out || (n_scaffolds && !ends)) return GF_E_INVAL;
+    return tag_layout_from_ends(ends, n_scaffolds, n_recs, out, base_or_null);
+}
+
+size_t gf_alnrec_linkeys_bytes(size_t n, uint32_t n_scaffolds) {
+    return lin_col(n, n_scaffolds).bytes;
+}
+
+int gf_alnrec_linkeys_dev(gf_ctx* ctx, const void* d_recs, size_t n, void* d_col, size_t col_bytes, gf_tag_layout* built_for) {
+    if (!ctx || !d_col || !built_for || (n && !d_recs)) return GF_E_INVAL;
+    if (col_bytes < lin_col(n, ctx->n_scaffolds).bytes) return GF_E_NOSPACE;
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_alnrec_linkeys(ctx, d_recs, n, d_col, built_for);
+}
+
+int gf_tag_alignments_linkeys_dev(gf_ctx* ctx, const void* d_recs, const void* d_col, const gf_tag_layout* built_for, const void* d_keys_or_null, size_t n,
+                                  int insert_size, int sd, int clip_dist, int anchor_mapq, void* d_out, size_t cap, void* d_n_out, void* d_low,
+                                  size_t low_cap, void* d_n_low) {
+    if (!ctx || !d_n_out || (n && !d_recs) || (cap && !d_out) || (d_col && !built_for)) return GF_E_INVAL;
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_tag(ctx, d_recs, n, insert_size, sd, clip_dist, anchor_mapq, d_out, cap, d_n_out, d_low, low_cap, d_n_low, d_keys_or_null, d_col, built_for);
+}
+
+int gf_tag_last_launch(gf_ctx* ctx, int* waves_per_workgroup, int* stream_form) {
+    if (!ctx) return GF_E_INVAL;
+    if (waves_per_workgroup) *waves_per_workgroup = ctx->tag_last_nw;
+    if (stream_form) *stream_form = ctx->tag_last_form;
+    return GF_OK;
+}
+
 int gf_gap_span_dev(gf_ctx* ctx, const void* d_recs, const void* d_keys_or_null, size_t n, int read_len, int is_mean, int is_sd, int z, int shift,
                     int min_mapq, void* d_rec, void* d_stats) {
     if (!ctx || !d_rec || !d_stats || (n && !d_recs)) return GF_E_INVAL;

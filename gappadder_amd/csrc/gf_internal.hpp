@@ -152,14 +152,19 @@ struct gf_ctx {
     void* asm_dbg = nullptr;  // diagnostic: device buffer for per-gap phase stamps (option asm_dbg_ptr)
     // tagger bin maps, one per dist2 (a pipeline tags every library with its own window; the four last used stay): the device copy is
     // [bits | n_scaffolds + 1 bit offsets | per bin: the first gap of the scaffold whose right window reaches the bin]
+    // A map for a library's LINEAR layout (gf_tag_layout; lin_granule > 0) is indexed by `linear key >> shift` instead: its middle part is the
+    // layout's base[] (n_scaffolds + 1 words), its bin_first has n_bins entries, and (granule, checksum of base[]) are part of the cache key.
     struct TagMap {
         int dist2 = -1, shift = 0;
         uint32_t words = 0, fine_words = 0, fine_shift = 0;
+        uint32_t lin_granule = 0, n_bins = 0, fine_bins = 0;
+        uint64_t lin_checksum = 0;
         uint64_t used = 0;
         gf::DevBuf map, fine;
     };
     std::vector<TagMap> tag_maps;
     uint64_t tag_map_clock = 0;
+    int tag_last_nw = 0, tag_last_form = 0;   // the last launch_tag: waves per workgroup; 0 records, 1 8-byte keys, 2 linear keys (gf_tag_last_launch)
     // tagger: bits of the LDS bin map and of the global one behind it; non-temporal record loads.  Measured on the C4 layout (200 M
     // records, rocprof): 2^25-bit global map 2.24 ms; + nt loads (the record stream no longer evicts the map from the L2s) 1.90 ms;
     // 2^23 bits + nt 1.82 ms; 32 / 64 KiB LDS maps 2.85 / 3.13 ms (fewer workgroups per CU)
@@ -249,11 +254,19 @@ int launch_screen(gf_ctx* ctx, const FlankIndex& ix, const void* d_reads, const 
                   const gf_probe_geom* built_for = nullptr);
 // tagger.hip
 int launch_tag(gf_ctx* ctx, const void* d_recs, size_t n, int insert_size, int sd, int clip_dist, int anchor_mapq,
-               void* d_out, size_t cap, void* d_n_out, void* d_low, size_t low_cap, void* d_n_low, const void* d_keys = nullptr);
+               void* d_out, size_t cap, void* d_n_out, void* d_low, size_t low_cap, void* d_n_low, const void* d_keys = nullptr,
+               const void* d_lin = nullptr, const gf_tag_layout* lin_for = nullptr);
 int launch_alnrec_keys(gf_ctx* ctx, const void* d_recs, size_t n, void* d_keys);
+// the linear key column (gf_tag_layout; layout of the buffer: LinCol)
+struct LinCol { size_t key_words, plane_off, plane_words, base_off, bytes; };   // offsets in bytes; the keys start at 0
+LinCol lin_col(size_t n, uint32_t n_scaffolds);
+int tag_layout_from_ends(const uint32_t* ends, uint32_t n_scaffolds, uint64_t n_recs, gf_tag_layout* out, uint32_t* base_or_null);
+int launch_alnrec_linkeys(gf_ctx* ctx, const void* d_recs, size_t n, void* d_col, gf_tag_layout* built_for);
 // the coarse (and, where it pays, fine) bin map of the gap windows for one dist2, built on first use and kept (the four last used): the
 // tagger's, shared with the gap-span pass (gap_span.hip), which asks for the tagger's own dist2 so that a library keeps ONE map
-int ensure_bin_map(gf_ctx* ctx, int dist2, gf_ctx::TagMap** out);
+// lay + d_base (the base[] words of a linear key column): the map of that layout instead; GF_E_UNSUPPORTED where the map's bins would be
+// wider than the layout's granule, GF_E_INVAL where base[] is not what the layout was built from
+int ensure_bin_map(gf_ctx* ctx, int dist2, gf_ctx::TagMap** out, const gf_tag_layout* lay = nullptr, const uint32_t* d_base = nullptr);
 // gap_span.hip
 int launch_gap_span(gf_ctx* ctx, const void* d_recs, const void* d_keys, size_t n, int read_len, int is_mean, int is_sd, int z, int shift,
                     int min_mapq, void* d_rec, void* d_stats);

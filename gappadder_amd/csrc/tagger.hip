@@ -8,6 +8,7 @@
 // low_mapq_kernel restates collect_discordant_low_mapq_reads.py:4-84: MAPQ==0 records, focal_region[p] = the
 // LAST discordant mate position q (sorted file order) with q-199 <= p <= q+299, one hit per row of q.
 #include <cstring>
+#include <type_traits>
 
 #include "gf_internal.hpp"
 
@@ -42,6 +43,13 @@ struct TagParams {
     uint32_t low_cap;
     uint32_t* n_low;
     gf_lowrec* low_stage;     // LOWSTAGE entries per wave of the launch: where a wave collects its MAPQ==0 records (see flush_low)
+    // LIN variants: the linear key column (gf_alnrec_linkeys_dev) — base[ref] + pos per record, 0xFFFFFFFF where the record takes no part —,
+    // and its MAPQ-0 bit plane (8 words per 256 records).  The maps are then indexed by key >> shift: n_bins / fine_bins bins, bin_first per
+    // bin of the line, and bin_off holds the layout's base[] (n_scaffolds + 1 words; staged behind the bits when off_words > 0).
+    const uint32_t* lin_keys;
+    const uint32_t* lin_plane;
+    uint64_t lin_units;       // 16-byte units of the column that hold a record: (n + 3) / 4
+    uint32_t plane_words, n_bins, fine_bins;
 };
 
 // A single global counter serialises returning atomics at ~11 ns each (MI355X_MICROARCH.md "dequeue"/"fanin" rows), so hits are
@@ -87,6 +95,7 @@ constexpr uint32_t LIVEQ = 96;   // per wave: < 64 waiting + what one step adds 
 // 79 % of their cycles in a kernel that only streams) — but queued with 12 bytes each and sifted 64 at a time; the few that pass
 // load their record again and join the queue of the window search.
 struct CandRec { uint32_t pos, ref, rec; };
+struct CandLin { uint32_t lin, rec; };   // the linear key column's: the key is (scaffold, position) in one word
 constexpr uint32_t CANDQ = 96;
 __device__ __forceinline__ void tag_wave_sync() {   // LDS hand-off between lanes of ONE wave (in-order LDS: compiler fence only)
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
@@ -102,13 +111,19 @@ constexpr int TAG_UNROLL = 8;  // 8 KiB (256 records) per wave and stage, two st
 // KEYS: the stream is the 8-byte KEY COLUMN of the records — {pos, ref | (mapq == 0) << 31}, built once at ingest — instead of the 32-byte
 // records themselves: 99 % of the records are decided by (scaffold, position) alone, and the by-product needs one more bit; the full record is
 // fetched only for what passes the bin maps (the path the fine-map queue already had).  A quarter of the bytes per record for the stream.
-template <int NW, bool BINS_LDS, bool NT = false, bool FINEQ = false, bool KEYS = false>
+// LIN (with KEYS): the stream is the 4-byte LINEAR key column — base[ref] + pos, the scaffolds laid end to end on granule boundaries no bin
+// crosses — and the MAPQ-0 bit comes from a bit plane: half the bytes per record again, and the bin test is one LDS read of bins[key >> shift]
+// without the two per-scaffold offsets.  A candidate waits as {key, record}; (scaffold, position) come back with the 32-byte record for what
+// passes, and for the MAPQ-0 by-product (2 % of the records) from a search of base[], made 64 entries at a time when the LDS buffer leaves.
+template <int NW, bool BINS_LDS, bool NT = false, bool FINEQ = false, bool KEYS = false, bool LIN = false>
 __global__ __launch_bounds__(64 * NW) void tag_kernel(TagParams P) {
+    static_assert(!LIN || (KEYS && BINS_LDS), "the linear key column is a key column, tested against the staged map");
     constexpr bool CQ = FINEQ || KEYS;   // records that pass the LDS map wait in the candidate queue (fine map, then the record's fetch)
+    using Cand = std::conditional_t<LIN, CandLin, CandRec>;
     extern __shared__ uint32_t bins_lds[];  // the whole bin map (16 or 64 KiB), staged once per workgroup
     __shared__ gf_taghit whits[NW][WHCAP];
     __shared__ LiveRec liveq[NW][LIVEQ];
-    __shared__ CandRec candq[CQ ? NW : 1][CQ ? CANDQ : 1];
+    __shared__ Cand candq[CQ ? NW : 1][CQ ? CANDQ : 1];
     // MAPQ==0 records (2 % of a library) leave through ONE counter, and returning atomics on one address are served at ~11-15 ns
     // each: flushing a 64-entry LDS buffer per wave straight to the list, the 900 M records of C4 needed 360 000 of them — 4 of the
     // kernel's 5.2 ms; the stream ran at 4.9 instead of 6.0 TB/s.  The LDS buffer (whole 768-byte runs: single 12-byte stores left
@@ -120,10 +135,12 @@ __global__ __launch_bounds__(64 * NW) void tag_kernel(TagParams P) {
     WaveHits hb{whits[threadIdx.x >> 6], 0};
     if (BINS_LDS) for (uint32_t i = threadIdx.x; i < P.bin_words + P.off_words; i += blockDim.x) bins_lds[i] = P.bin_bits[i];   // (bits, then offsets: one array)
     const uint32_t* bins = BINS_LDS ? bins_lds : P.bin_bits;
-    const uint32_t* boff = BINS_LDS && P.off_words ? bins_lds + P.bin_words : P.bin_off;
+    const uint32_t* boff = BINS_LDS && P.off_words ? bins_lds + P.bin_words : P.bin_off;   // (LIN: base[], not bit offsets)
     __syncthreads();
     const uint32_t lane = threadIdx.x & 63;
-    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    // (LIN: the wave's number as a value the compiler knows to be wave-uniform, so that what derives from it stays out of the vector registers)
+    const uint64_t wave = LIN ? (uint64_t)blockIdx.x * NW + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))
+                              : ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     gf_lowrec* const wlow = lowbuf[threadIdx.x >> 6];
     gf_lowrec* const wstage = P.low ? P.low_stage + wave * LOWSTAGE : nullptr;
     auto flush_stage = [&]() {
@@ -141,6 +158,21 @@ __global__ __launch_bounds__(64 * NW) void tag_kernel(TagParams P) {
     };
     auto flush_low = [&]() {   // LDS buffer -> staging slice
         if (stage_n + low_n > LOWSTAGE) flush_stage();
+        if constexpr (LIN) {
+            // the buffer holds {key, -, record}: the scaffold is the last one whose base is <= key (empty scaffolds share their base with
+            // the next one and are stepped over), one search per entry with every lane of the flush at work
+            tag_wave_sync();
+            if (lane < low_n) {
+                const gf_lowrec e = wlow[lane];
+                uint32_t lo = 0, hi = P.n_scaffolds;          // invariant: base[lo] <= key, base[hi] > key (the line ends above every key)
+                while (hi - lo > 1) {
+                    const uint32_t mid = (lo + hi) >> 1;
+                    if (boff[mid] <= e.pos) lo = mid; else hi = mid;
+                }
+                wlow[lane] = gf_lowrec{e.pos - boff[lo], lo, e.rec};
+            }
+            tag_wave_sync();
+        }
         const uint32_t* src32 = reinterpret_cast<const uint32_t*>(wlow);
         uint32_t* dst32 = reinterpret_cast<uint32_t*>(wstage + stage_n);
         for (uint32_t i = lane; i < 3 * low_n; i += 64) dst32[i] = src32[i];
@@ -160,9 +192,14 @@ __global__ __launch_bounds__(64 * NW) void tag_kernel(TagParams P) {
             r.pos = q.pos; r.ref = q.ref; r.tlen = q.tlen; r.mate_ref = q.mate_ref;
             r.flag = (uint16_t)(q.meta & 0xFFFF); r.mapq = (uint8_t)((q.meta >> 16) & 0xFF); r.clipflag = (uint8_t)(q.meta >> 24);
             rec = q.rec;
-            g_end = P.scaf_off[r.ref + 1];
+            g_end = !LIN || r.ref < P.n_scaffolds ? P.scaf_off[r.ref + 1] : 0;
             // the first gap whose right window reaches the record's BIN (one load; the map's third part) — gaps between it and the first
             // one whose window reaches POS itself (end + dist2 > pos; two gaps within one bin) fall through the walk below untagged
+            if constexpr (LIN) {
+                // (the fetched record says where it lies; a record that does not belong to the column it was listed from finds no bin)
+                const uint32_t bi = r.ref < P.n_scaffolds ? (boff[r.ref] + r.pos) >> P.bin_shift : P.n_bins;
+                if (bi < P.n_bins) g = P.bin_first[bi]; else g = g_end = 0;
+            } else
             g = P.bin_first[boff[r.ref] + (r.pos >> P.bin_shift)];
         }
         const int64_t pos = r.pos;
@@ -214,14 +251,20 @@ __global__ __launch_bounds__(64 * NW) void tag_kernel(TagParams P) {
     const uint64_t chunk = 64ull * TAG_UNROLL;             // halves per wave iteration
     const uint4* src = reinterpret_cast<const uint4*>(P.recs);
     // ---- per-wave queue of records that passed the LDS map and wait for the fine map (FINEQ)
-    CandRec* wcand = candq[CQ ? threadIdx.x >> 6 : 0];
+    Cand* wcand = candq[CQ ? threadIdx.x >> 6 : 0];
     uint32_t cand_n = 0;   // wave-uniform
     auto sift = [&]() {    // fine-map test of the last min(64, cand_n) queued records, one per lane
         const uint32_t base = cand_n > 64 ? cand_n - 64 : 0;
         bool live = base + lane < cand_n;
-        CandRec c = {};
+        Cand c = {};
         if (live) {
             c = wcand[base + lane];
+            if constexpr (LIN) {
+                if (P.fine_bits) {
+                    const uint32_t fb = c.lin >> P.fine_shift;
+                    live = fb < P.fine_bins && ((P.fine_bits[fb >> 5] >> (fb & 31)) & 1u);
+                }
+            } else
             if (FINEQ || P.fine_bits) {   // (KEYS without a fine map: the queue only gathers the records to fetch)
                 const uint32_t f0 = P.fine_off[c.ref], fi = c.pos >> P.fine_shift, fb = f0 + fi;
                 live = fi < P.fine_off[c.ref + 1] - f0 && ((P.fine_bits[fb >> 5] >> (fb & 31)) & 1u);
@@ -244,7 +287,76 @@ __global__ __launch_bounds__(64 * NW) void tag_kernel(TagParams P) {
             if (live_n >= 64) drain();
         }
     };
-    if constexpr (KEYS) {
+    if constexpr (LIN) {
+        // the linear key column: 16 bytes = four records per lane and load, TAG_UNROLL loads (2 048 records per wave: the same 8 KiB) in flight
+        // behind the chunk at work, and with them the 256 bytes of the MAPQ-0 bit plane that go with a chunk: one load per wave, a word per
+        // lane; the four bits of a lane's records come from the word of lane 8 u + lane / 8.  (Plain loops and no closure, as below.)
+        typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+        const u32x4* ksrc4 = reinterpret_cast<const u32x4*>(P.lin_keys);
+        // (32-bit unit indices from a wave index the compiler knows to be uniform: a record index fits 32 bits, so a unit's does, and the loop's
+        //  bookkeeping stays out of the vector registers — the 16-wave form has 128 of them, 64 hold keys)
+        const uint32_t n_k16 = (uint32_t)P.lin_units, kchunk = 64u * TAG_UNROLL;
+        const uint32_t wv = (uint32_t)wave, stride = gridDim.x * NW * kchunk;
+        u32x4 kn[TAG_UNROLL];
+        uint32_t pn = 0;
+#pragma unroll
+        for (int u = 0; u < TAG_UNROLL; ++u) {
+            const uint32_t h = wv * kchunk + 64u * u + lane;
+            kn[u] = h < n_k16 ? __builtin_nontemporal_load(ksrc4 + h) : u32x4{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+        }
+        if (P.low) {
+            const uint32_t w = ((wv * kchunk) >> 3) + lane;
+            if (w < P.plane_words) pn = P.lin_plane[w];
+        }
+        for (uint32_t h0 = wv * kchunk; h0 < n_k16; h0 += stride) {
+            u32x4 v[TAG_UNROLL];
+#pragma unroll
+            for (int u = 0; u < TAG_UNROLL; ++u) v[u] = kn[u];
+            const uint32_t pl = pn;
+#pragma unroll
+            for (int u = 0; u < TAG_UNROLL; ++u) {
+                const uint32_t h = h0 + stride + 64u * u + lane;
+                kn[u] = h < n_k16 ? __builtin_nontemporal_load(ksrc4 + h) : u32x4{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+            }
+            pn = 0;
+            if (P.low) {
+                const uint32_t w = ((h0 + stride) >> 3) + lane;
+                if (w < P.plane_words) pn = P.lin_plane[w];
+            }
+#pragma unroll
+            for (int u = 0; u < TAG_UNROLL; ++u) {
+                const uint32_t pw = P.low ? __shfl(pl, 8 * u + (int)(lane >> 3)) >> ((lane & 7u) * 4u) : 0u;
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const uint32_t rec = 4u * (h0 + 64u * u + lane) + q;
+                    const uint32_t lin = q == 0 ? v[u].x : q == 1 ? v[u].y : q == 2 ? v[u].z : v[u].w;
+                    if (P.low) {   // wave-uniform: compact the MAPQ==0 records for the second hop ({key, -, record} until the buffer leaves)
+                        const bool z = ((pw >> q) & 1u) && !(P.dbg & 1u);
+                        const unsigned long long zb = __ballot(z);
+                        if (zb) {
+                            const uint32_t cnt = (uint32_t)__popcll(zb);
+                            if (low_n + cnt > LOWBUF) flush_low();
+                            if (z) wlow[low_n + __popcll(zb & ((1ull << lane) - 1))] = gf_lowrec{lin, 0u, (uint32_t)rec};
+                            low_n += cnt;
+                        }
+                    }
+                    // the pad, unplaced records and unknown scaffolds carry the key 0xFFFFFFFF: a bin behind the last one
+                    const uint32_t bi = lin >> P.bin_shift;
+                    bool live = bi < P.n_bins && !(P.dbg & 2u);
+                    if (live) live = (bins[bi >> 5] >> (bi & 31)) & 1u;
+                    if (P.dbg & 4u) live = false;
+                    const unsigned long long cb = __ballot(live);
+                    if (!cb) continue;
+                    const uint32_t cnt = (uint32_t)__popcll(cb);
+                    if (cand_n + cnt > CANDQ) sift();                  // (cand_n < 64 on entry: one sift empties the queue)
+                    if (live) wcand[cand_n + __popcll(cb & ((1ull << lane) - 1))] = CandLin{lin, (uint32_t)rec};
+                    cand_n += cnt;
+                    tag_wave_sync();
+                    if (cand_n >= 64) sift();
+                }
+            }
+        }
+    } else if constexpr (KEYS) {
         // the key column: 16 bytes = two records per lane and load, TAG_UNROLL loads (1 024 records per wave) in flight behind the chunk at work
         const uint4* ksrc = reinterpret_cast<const uint4*>(P.keys);
         const uint64_t n_k16 = (P.n + 1) / 2;
@@ -410,6 +522,124 @@ __global__ __launch_bounds__(256) void alnrec_keys_kernel(const gf_alnrec* recs,
     keys[i] = k;
 }
 
+// ---- the linear key column (gf_tag_layout)
+// exclusive end of every scaffold: max(pos) + 1 over the placed records.  A wave walks ENDS_RUN consecutive records, 64 at a time, every lane
+// keeping the maximum of the scaffold it is on (it hands the maximum over when its scaffold changes).  A BAM is sorted, so at the end the lanes
+// of a wave are on one scaffold as a rule: one atomic per wave and run then — a wave per 64 records and its atomic, 14 M of them on 620
+// addresses at C4, took 370 ms —, one per lane where the run straddles a boundary.
+constexpr uint32_t ENDS_RUN = 4096;
+__global__ __launch_bounds__(256) void alnrec_ends_kernel(const gf_alnrec* recs, uint64_t n, uint32_t n_scaffolds, uint32_t* ends) {
+    const uint64_t wave = ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    uint32_t ref = 0xFFFFFFFFu, end = 0;
+    for (uint32_t it = 0; it < ENDS_RUN / 64; ++it) {
+        const uint64_t i = wave * ENDS_RUN + 64ull * it + (threadIdx.x & 63);
+        if (i >= n) break;
+        const uint4 a = reinterpret_cast<const uint4*>(recs)[2 * i];
+        if (a.w >= n_scaffolds) continue;
+        const uint32_t e = a.x == 0xFFFFFFFFu ? a.x : a.x + 1;
+        if (a.w != ref) {
+            if (ref != 0xFFFFFFFFu) atomicMax(ends + ref, end);
+            ref = a.w;
+            end = e;
+        } else if (e > end) end = e;
+    }
+    const unsigned long long placed = __ballot(ref != 0xFFFFFFFFu);
+    if (!placed) return;
+    const uint32_t ref0 = __shfl(ref, __ffsll((long long)placed) - 1);
+    if (__all(ref == ref0 || ref == 0xFFFFFFFFu)) {
+        for (int d = 32; d; d >>= 1) { const uint32_t o = __shfl_xor(end, d); end = o > end ? o : end; }
+        if ((threadIdx.x & 63) == 0) atomicMax(ends + ref0, end);
+    } else if (ref != 0xFFFFFFFFu) atomicMax(ends + ref, end);
+}
+
+// keys and bit plane: thread i writes key i (the pad included) and, as lanes 0 and 32 of its wave, the plane words of the wave's 64 records
+__global__ __launch_bounds__(256) void alnrec_linkeys_kernel(const gf_alnrec* recs, uint64_t n, uint32_t n_scaffolds, const uint32_t* base,
+                                                             uint32_t* keys, uint64_t key_words, uint32_t* plane, uint64_t plane_words) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t key = 0xFFFFFFFFu;
+    bool z = false;
+    if (i < n) {
+        const uint4 a = reinterpret_cast<const uint4*>(recs)[2 * i], b = reinterpret_cast<const uint4*>(recs)[2 * i + 1];
+        if (a.w < n_scaffolds) {
+            key = base[a.w] + a.x;
+            z = ((b.y >> 16) & 0xFFu) == 0;
+        }
+    }
+    if (i < key_words) keys[i] = key;
+    const unsigned long long zb = __ballot(z);
+    const uint32_t lane = threadIdx.x & 63;
+    if ((lane & 31) == 0 && (i >> 5) < plane_words) plane[i >> 5] = (uint32_t)(zb >> lane);
+}
+
+LinCol lin_col(size_t n, uint32_t n_scaffolds) {
+    LinCol c;
+    c.key_words = ((n + 3) & ~(size_t)3) + 4;                   // the next multiple of 4 keys plus one 16-byte load
+    c.plane_off = (c.key_words * 4 + 31) & ~(size_t)31;
+    c.plane_words = (n + 255) / 256 * 8;                        // a whole 32-byte piece per 256 records
+    c.base_off = c.plane_off + c.plane_words * 4;
+    c.bytes = c.base_off + ((size_t)n_scaffolds + 1) * 4;
+    return c;
+}
+
+constexpr int LIN_GRANULE_MAX = 20, LIN_GRANULE_MIN = 6, LIN_LDS_BITS_LOG2 = 17;   // (6: the narrowest bins ensure_bin_map makes; 17: its default)
+static uint64_t lin_checksum(const uint32_t* base, size_t n_words) {
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (size_t i = 0; i < n_words; ++i)
+        for (int b = 0; b < 4; ++b) { h ^= (base[i] >> (8 * b)) & 0xFFu; h *= 0x100000001b3ull; }
+    return h;
+}
+
+int tag_layout_from_ends(const uint32_t* ends, uint32_t n_scaffolds, uint64_t n_recs, gf_tag_layout* out, uint32_t* base_out) {
+    gf_tag_layout L = {};
+    L.n_recs = n_recs;
+    L.n_scaffolds = n_scaffolds;
+    std::vector<uint32_t> base((size_t)n_scaffolds + 1, 0);
+    // the largest granule whose line fits 32 bits with the sentinel's bin to spare and is no narrower than the bins of the default LDS map
+    // over that line (a wider granule wastes more of the line per scaffold: many small scaffolds end up with a small one)
+    for (int a = LIN_GRANULE_MAX; a >= LIN_GRANULE_MIN && !L.use; --a) {
+        const uint64_t gr = 1ull << a;
+        uint64_t total = 0;
+        for (uint32_t s = 0; s < n_scaffolds; ++s) total += ((uint64_t)ends[s] + gr - 1) & ~(gr - 1);
+        if (total >= (1ull << 32) - gr) continue;
+        int need = LIN_GRANULE_MIN;
+        while ((total >> need) + 1 > (1ull << LIN_LDS_BITS_LOG2)) ++need;
+        if (need > a) continue;
+        L.use = 1;
+        L.granule_log2 = (uint32_t)a;
+        L.span = total;
+        uint64_t at = 0;
+        for (uint32_t s = 0; s < n_scaffolds; ++s) { base[s] = (uint32_t)at; at += ((uint64_t)ends[s] + gr - 1) & ~(gr - 1); }
+        base[n_scaffolds] = (uint32_t)at;
+    }
+    L.checksum = L.use ? lin_checksum(base.data(), base.size()) : 0;
+    *out = L;
+    if (base_out && L.use) memcpy(base_out, base.data(), base.size() * 4);
+    return GF_OK;
+}
+
+int launch_alnrec_linkeys(gf_ctx* ctx, const void* d_recs, size_t n, void* d_col, gf_tag_layout* built_for) {
+    if (n >= 0xFFFFFFFFull) return GF_E_INVAL;
+    const uint32_t ns = ctx->n_scaffolds;
+    const LinCol c = lin_col(n, ns);
+    uint32_t* d_base = (uint32_t*)((uint8_t*)d_col + c.base_off);
+    std::vector<uint32_t> ends((size_t)ns + 1, 0), base((size_t)ns + 1, 0);
+    LaunchTimer tm(ctx, GF_KERNEL_INGEST);
+    GF_HIP(ctx, hipMemsetAsync(d_base, 0, ((size_t)ns + 1) * 4, ctx->stream));   // (the ends are measured in the place of base[])
+    if (n) hipLaunchKernelGGL(alnrec_ends_kernel, dim3((unsigned)((n + 4 * ENDS_RUN - 1) / (4 * ENDS_RUN))), dim3(256), 0, ctx->stream, (const gf_alnrec*)d_recs, (uint64_t)n, ns, d_base);
+    GF_HIP(ctx, hipGetLastError());
+    GF_HIP(ctx, hipMemcpyAsync(ends.data(), d_base, ((size_t)ns + 1) * 4, hipMemcpyDeviceToHost, ctx->stream));
+    GF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int rc = tag_layout_from_ends(ends.data(), ns, n, built_for, base.data());
+    if (rc || !built_for->use) return rc;
+    GF_HIP(ctx, hipMemcpyAsync(d_base, base.data(), base.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    const size_t threads = std::max(c.key_words, c.plane_words * 32);
+    hipLaunchKernelGGL(alnrec_linkeys_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, ctx->stream, (const gf_alnrec*)d_recs, (uint64_t)n,
+                       ns, d_base, (uint32_t*)d_col, (uint64_t)c.key_words, (uint32_t*)((uint8_t*)d_col + c.plane_off), (uint64_t)c.plane_words);
+    GF_HIP(ctx, hipGetLastError());
+    GF_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (base goes out of scope)
+    return GF_OK;
+}
+
 // (gf_internal.hpp: HOP_NEAR_LOG2, HOP_NEAR_SHIFT, hop_near_bit)
 struct LowParams {
     const gf_alnrec* recs;     // full records ...
@@ -569,9 +799,27 @@ void drop_tag_maps(gf_ctx* ctx) {
 
 // Coarse bin map of the gap windows for one dist2 (host build: n_gaps work; kept until the gaps change, the four last used dist2).
 // Bits cover, per scaffold, positions 0 .. last window end; everything beyond has no window.
-int ensure_bin_map(gf_ctx* ctx, int dist2, gf_ctx::TagMap** out) {
+// With a layout (lay, d_base: a linear key column's) the map is indexed by `key >> shift` over the line of scaffolds instead: a gap's windows
+// are clamped to its own scaffold's stretch [base[s], base[s + 1]) — a left window that starts below position 0 must not reach the scaffold
+// before, a right window that passes the scaffold's last record not the one behind —, the bits end with the last window of the line, and the
+// word behind the last bin is zero: the sentinel key, and every key behind the last window, tests as "no window".
+int ensure_bin_map(gf_ctx* ctx, int dist2, gf_ctx::TagMap** out, const gf_tag_layout* lay, const uint32_t* d_base) {
+    const bool lin = lay != nullptr;
+    const uint32_t lin_granule = lin ? lay->granule_log2 : 0;
+    const uint64_t lin_checksum_want = lin ? lay->checksum : 0;
+    if (lin && (!lay->use || !d_base || lay->n_scaffolds != ctx->n_scaffolds || lin_granule < (uint32_t)LIN_GRANULE_MIN || lin_granule > (uint32_t)LIN_GRANULE_MAX))
+        return GF_E_INVAL;
     for (gf_ctx::TagMap& m : ctx->tag_maps)
-        if (m.dist2 == dist2 && m.map.p) { m.used = ++ctx->tag_map_clock; *out = &m; return GF_OK; }
+        if (m.dist2 == dist2 && m.map.p && m.lin_granule == lin_granule && m.lin_checksum == lin_checksum_want) { m.used = ++ctx->tag_map_clock; *out = &m; return GF_OK; }
+    std::vector<uint32_t> base;
+    if (lin) {   // the layout's base[], as the column carries it
+        base.resize((size_t)ctx->n_scaffolds + 1);
+        GF_HIP(ctx, hipMemcpyAsync(base.data(), d_base, base.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+        GF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        bool ok = lin_checksum(base.data(), base.size()) == lay->checksum && base[0] == 0 && base[ctx->n_scaffolds] == lay->span;
+        for (uint32_t s = 0; ok && s < ctx->n_scaffolds; ++s) ok = base[s] <= base[s + 1] && (base[s] & ((1u << lin_granule) - 1)) == 0;
+        if (!ok) return GF_E_INVAL;
+    }
     if (ctx->tag_maps.size() >= 4) {   // drop the one that was not used for the longest time
         size_t old = 0;
         for (size_t i = 1; i < ctx->tag_maps.size(); ++i) if (ctx->tag_maps[i].used < ctx->tag_maps[old].used) old = i;
@@ -582,27 +830,45 @@ int ensure_bin_map(gf_ctx* ctx, int dist2, gf_ctx::TagMap** out) {
     }
     gf_ctx::TagMap M;
     const int64_t d2 = dist2 > 0 ? dist2 : 0;
+    // positions lo .. hi (inclusive) that the windows of a gap cover — of the scaffold, or of the line: false when there are none
+    auto window = [&](const gf_gap& g, int64_t& lo, int64_t& hi) {
+        lo = std::max<int64_t>(0, (int64_t)g.start - d2 + 1);
+        hi = (int64_t)g.end + d2 - 1;
+        if (d2 == 0) return false;
+        if (!lin) return true;
+        const int64_t len = (int64_t)base[g.scaffold + 1] - (int64_t)base[g.scaffold];
+        hi = std::min(hi, len - 1);
+        lo += base[g.scaffold];
+        hi += base[g.scaffold];
+        return lo <= hi;
+    };
     std::vector<uint64_t> span(ctx->n_scaffolds, 0);  // exclusive end of the covered positions per scaffold
     for (const gf_gap& g : ctx->gaps) span[g.scaffold] = std::max<uint64_t>(span[g.scaffold], (uint64_t)g.end + d2);
-    auto nbits = [&](int sh) { uint64_t t = 0; for (uint64_t v : span) t += (v >> sh) + (v ? 1 : 0); return t; };
-    // one map = bit words followed by the n_scaffolds+1 bit offsets
+    uint64_t lin_end = 0;                             // ... and of the line
+    if (lin) for (const gf_gap& g : ctx->gaps) { int64_t lo, hi; if (window(g, lo, hi)) lin_end = std::max<uint64_t>(lin_end, (uint64_t)hi + 1); }
+    auto nbits = [&](int sh) {
+        if (lin) return (lin_end >> sh) + (lin_end ? 1 : 0);
+        uint64_t t = 0; for (uint64_t v : span) t += (v >> sh) + (v ? 1 : 0); return t;
+    };
+    // one map = bit words followed by the n_scaffolds+1 bit offsets (the layout's base[] in their place for a line)
     auto build = [&](int shift, std::vector<uint32_t>& h, uint32_t& words) {
         std::vector<uint32_t> off(ctx->n_scaffolds + 1, 0);
         for (uint32_t s = 0; s < ctx->n_scaffolds; ++s) off[s + 1] = off[s] + (uint32_t)((span[s] >> shift) + (span[s] ? 1 : 0));
-        words = (off[ctx->n_scaffolds] + 31) / 32 + 1;
+        words = (uint32_t)(((lin ? nbits(shift) : (uint64_t)off[ctx->n_scaffolds]) + 31) / 32 + 1);
         h.assign(words + off.size(), 0);
         for (const gf_gap& g : ctx->gaps) {
-            if (d2 == 0) break;
-            const int64_t lo = std::max<int64_t>(0, (int64_t)g.start - d2 + 1), hi = (int64_t)g.end + d2 - 1;
+            int64_t lo, hi;
+            if (!window(g, lo, hi)) continue;
             for (int64_t b = lo >> shift; b <= (hi >> shift); ++b) {
-                const uint32_t bit = off[g.scaffold] + (uint32_t)b;
+                const uint32_t bit = (lin ? 0u : off[g.scaffold]) + (uint32_t)b;
                 h[bit >> 5] |= 1u << (bit & 31);
             }
         }
-        for (size_t i = 0; i < off.size(); ++i) h[words + i] = off[i];
+        for (size_t i = 0; i < off.size(); ++i) h[words + i] = lin ? base[i] : off[i];
     };
     int shift = 6;
     while (nbits(shift) > (1u << ctx->tag_bins_log2)) ++shift;  // <= 16 KiB of LDS by default (measured: an 8 KiB map sends more records down the slow path and loses)
+    if (lin && shift > (int)lin_granule) return GF_E_UNSUPPORTED;   // a bin would cover two scaffolds
     uint32_t words = 0;
     std::vector<uint32_t> h;
     build(shift, h, words);
@@ -623,13 +889,24 @@ int ensure_bin_map(gf_ctx* ctx, int dist2, gf_ctx::TagMap** out) {
     // Behind the offsets: per bin, the first gap of the scaffold whose RIGHT window still reaches the bin's first position
     // (end + dist2 > bin << shift; ends ascend) — where the window search of a record in that bin starts.  It replaces a binary
     // search over the scaffold's gaps (five dependent loads at 32 gaps per scaffold) by one load.
+    const uint32_t n_bins = lin ? (uint32_t)nbits(shift) : 0;
     {
         const size_t n_off = (size_t)ctx->n_scaffolds + 1;
-        const uint32_t total_bits = h[words + ctx->n_scaffolds];
+        const uint32_t total_bits = lin ? n_bins : h[words + ctx->n_scaffolds];
         std::vector<uint32_t> first(total_bits, 0);
         size_t g = 0;
         for (uint32_t s = 0; s < ctx->n_scaffolds; ++s) {
             while (g < ctx->gaps.size() && ctx->gaps[g].scaffold < s) ++g;
+            if (lin) {   // the scaffold's bins of the line (granule >= bin: they are its own), positions counted from its base
+                if (base[s + 1] == base[s]) continue;
+                const uint64_t b_first = base[s] >> shift, b_last = std::min<uint64_t>(((uint64_t)base[s + 1] - 1) >> shift, (uint64_t)n_bins - 1);
+                for (uint64_t b = b_first; b <= b_last && n_bins; ++b) {
+                    const int64_t p = (int64_t)((b << shift) - base[s]);
+                    while (g < ctx->gaps.size() && ctx->gaps[g].scaffold == s && (int64_t)ctx->gaps[g].end + d2 <= p) ++g;
+                    first[b] = (uint32_t)g;
+                }
+                continue;
+            }
             const uint32_t b0 = h[words + s], nb = h[words + s + 1] - b0;
             for (uint32_t b = 0; b < nb; ++b) {
                 while (g < ctx->gaps.size() && ctx->gaps[g].scaffold == s && (int64_t)ctx->gaps[g].end + d2 <= ((int64_t)b << shift)) ++g;
@@ -666,12 +943,16 @@ int ensure_bin_map(gf_ctx* ctx, int dist2, gf_ctx::TagMap** out) {
                 GF_HIP(ctx, hipStreamSynchronize(ctx->stream));
                 M.fine_words = fw;
                 M.fine_shift = fs;
+                M.fine_bins = lin ? (uint32_t)nbits(fs) : 0;
             }
         }
     }
     M.dist2 = dist2;
     M.shift = shift;
     M.words = words;
+    M.lin_granule = lin_granule;
+    M.lin_checksum = lin_checksum_want;
+    M.n_bins = n_bins;
     M.used = ++ctx->tag_map_clock;
     ctx->tag_maps.push_back(M);
     *out = &ctx->tag_maps.back();
@@ -686,7 +967,8 @@ int launch_alnrec_keys(gf_ctx* ctx, const void* d_recs, size_t n, void* d_keys) 
 }
 
 int launch_tag(gf_ctx* ctx, const void* d_recs, size_t n, int insert_size, int sd, int clip_dist, int anchor_mapq,
-               void* d_out, size_t cap, void* d_n_out, void* d_low, size_t low_cap, void* d_n_low, const void* d_keys) {
+               void* d_out, size_t cap, void* d_n_out, void* d_low, size_t low_cap, void* d_n_low, const void* d_keys, const void* d_lin,
+               const gf_tag_layout* lin_for) {
     if (!ctx->d_gaps) return GF_E_STATE;
     if (n >= 0xFFFFFFFFull || cap > 0xFFFFFFFFull) return GF_E_INVAL;
     zero_regions(ctx, ZeroList{{(uint32_t*)d_n_out, (uint32_t*)d_n_low, nullptr, nullptr}, {1, d_n_low ? 1u : 0u, 0, 0}});
@@ -712,8 +994,25 @@ int launch_tag(gf_ctx* ctx, const void* d_recs, size_t n, int insert_size, int s
     P.cap = (uint32_t)cap;
     P.n_out = (uint32_t*)d_n_out;
     gf_ctx::TagMap* M = nullptr;
-    int rc = ensure_bin_map(ctx, P.dist2, &M);
+    int rc = GF_OK;
+    // The linear key column is streamed only when it was built for exactly this call (record count, scaffolds; ensure_bin_map checks base[]
+    // against the layout's checksum) and the map's bins fit its granule; a stale column or a map it cannot serve is refused, and the call
+    // answers from the 8-byte column or the records.
+    bool lin = d_lin && lin_for && lin_for->use && !ctx->tag_light && lin_for->n_recs == n && lin_for->n_scaffolds == ctx->n_scaffolds;
+    const LinCol lc = lin_col(n, ctx->n_scaffolds);
+    if (lin) {
+        rc = ensure_bin_map(ctx, P.dist2, &M, lin_for, (const uint32_t*)((const uint8_t*)d_lin + lc.base_off));
+        if (rc == GF_E_UNSUPPORTED || rc == GF_E_INVAL) { lin = false; M = nullptr; }
+        else if (rc) return rc;
+    }
+    if (!lin) rc = ensure_bin_map(ctx, P.dist2, &M);
     if (rc) return rc;
+    P.lin_keys = lin ? (const uint32_t*)d_lin : nullptr;
+    P.lin_plane = lin ? (const uint32_t*)((const uint8_t*)d_lin + lc.plane_off) : nullptr;
+    P.lin_units = (n + 3) / 4;
+    P.plane_words = (uint32_t)lc.plane_words;
+    P.n_bins = M->n_bins;
+    P.fine_bins = M->fine_bins;
     P.bin_bits = (const uint32_t*)M->map.p;
     P.bin_off = P.bin_bits + M->words;
     P.bin_first = P.bin_off + ctx->n_scaffolds + 1;
@@ -744,6 +1043,12 @@ int launch_tag(gf_ctx* ctx, const void* d_recs, size_t n, int insert_size, int s
     }
     {
         LaunchTimer tm(ctx, GF_KERNEL_TAG);
+        ctx->tag_last_nw = (int)nw;
+        ctx->tag_last_form = lin ? 2 : d_keys && !ctx->tag_light ? 1 : 0;
+        if (lin) {   // the linear key column as the stream (gf_tag_alignments_linkeys_dev)
+            if (big_map) hipLaunchKernelGGL((tag_kernel<16, true, true, false, true, true>), dim3(grid), dim3(1024), lds_map, ctx->stream, P);
+            else hipLaunchKernelGGL((tag_kernel<4, true, true, false, true, true>), dim3(grid), dim3(256), lds_map, ctx->stream, P);
+        } else
         if (d_keys && !ctx->tag_light) {   // the key column as the stream (gf_tag_alignments_keys_dev)
             if (big_map) hipLaunchKernelGGL((tag_kernel<16, true, true, false, true>), dim3(grid), dim3(1024), lds_map, ctx->stream, P);
             else hipLaunchKernelGGL((tag_kernel<4, true, true, false, true>), dim3(grid), dim3(256), lds_map, ctx->stream, P);

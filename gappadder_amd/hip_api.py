@@ -16,7 +16,7 @@ class GapFill:
         if rc:
             raise B.GapFillError(rc, "gf_init(device=%d)" % device)
         self._h = h
-        self.n_gaps = 0
+        self.n_gaps = self.n_scaffolds = 0
 
     def close(self):
         if getattr(self, "_h", None):
@@ -51,7 +51,7 @@ class GapFill:
         else:
             rc = self._L.gf_set_gaps(self._h, B._p(gaps), len(gaps), int(n_scaffolds), None, None)
         self._chk(rc, "gf_set_gaps")
-        self.n_gaps = len(gaps)
+        self.n_gaps, self.n_scaffolds = len(gaps), int(n_scaffolds)
         self.flanks = [(l, r) for l, r in flanks] if flanks is not None else None    # (Pipeline.picked_sequences cuts exact-mode picks with them)
 
     @staticmethod

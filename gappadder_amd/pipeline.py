@@ -64,7 +64,7 @@ class DeviceLibrary:
     over all ranks, `first_pair` = this rank's first pair (contiguous shards)."""
 
     def __init__(self, name, is_mean, is_sd, n_reads, d_reads, d_recs, n_recs=None, pull_mates=1, d_nmask=None, n_total=None,
-                 first_pair=0, tag_ctx=None, screen=True, d_rec_keys=None, d_probes=None, probe_geom=None):
+                 first_pair=0, tag_ctx=None, screen=True, d_rec_keys=None, d_probes=None, probe_geom=None, d_lin_keys=None, lin_layout=None):
         self.name, self.is_mean, self.is_sd, self.pull_mates = name, int(is_mean), int(is_sd), int(pull_mates)
         self.n_reads, self.d_reads, self.d_recs, self.d_nmask = int(n_reads), d_reads, d_recs, d_nmask
         self.n_recs = int(n_reads if n_recs is None else n_recs)
@@ -73,6 +73,9 @@ class DeviceLibrary:
         self.tag_ctx = tag_ctx          # a second GapFill (second stream) for the tagger + second hop, or None: the pipeline's
         self.screen = bool(screen)      # False: alignment-based recruitment only (the reference's own mode)
         self.d_rec_keys = d_rec_keys    # the records' key column (gf_alnrec_keys_dev); None: Pipeline.add_library builds it
+        # the records' 4-byte linear key column and the layout it was built for (gf_alnrec_linkeys_dev); None: Pipeline.add_library builds it
+        # where the draft fits one 32-bit line
+        self.d_lin_keys, self.lin_layout = d_lin_keys, lin_layout
         # the reads' probe column and the geometry it was built for (gf_read_probes_dev, or the file path's packing kernels); None:
         # Pipeline.add_library builds it where it pays
         self.d_probes, self.probe_geom = d_probes, probe_geom
@@ -97,7 +100,7 @@ PICKS = {"exact": ("gf_pick_anchored2_dev", "gf_pick_anchored2_from_dev", "gf_pi
 class Pipeline:
     def __init__(self, gf, n_gaps, read_len, k_pairs, device=None, world=1, rank=0, backend="nccl", force_exchange=False,
                  min_count=2, min_contig=40, anchors=(30, 15), clip_dist=250, anchor_mapq=30, k_screen=None, keep_read_ids=False,
-                 key_column=True, probe_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False,
+                 key_column=True, linear_keys=True, probe_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False,
                  extended_fill=False, ext_base_cap=None, rescue_round=False, read_support=False, support_k=None, polish=False,
                  polish_seed=16, polish_max_mismatch=4, polish_min_overlap=48, polish_min_votes=2, pair_span=False, pair_seed=16,
                  pair_max_mismatch=4, pair_min_overlap=48, pair_z=3, pair_anchors=False, pair_min_pairs=8, gap_span=False, span_z=3,
@@ -110,6 +113,10 @@ class Pipeline:
         ({pos, scaffold | MAPQ-0 bit}, built once when a library is added: 7.2 GB for C4's 900 M records) and the tagger streams THAT —
         a record far from every gap, 99 % of a BAM, is decided by (scaffold, position) alone (the reference's `focal_region.has_key(POS)`,
         collect_reads_for_gaps.py:104) — fetching the 32-byte record only of what passes its bin maps.
+        linear_keys (with key_column): where the scaffolds of the draft, laid end to end on granule boundaries, fit one 32-bit line (a draft
+        below 4 Gb: gf_tag_layout), the library keeps a 4-byte key per record instead — its position on that line — with the MAPQ-0 bit in a
+        bit plane (3.7 GB for C4), and the tagger streams that; the 8-byte column is then built only for a consumer of its own (gap_span)
+        or where the line does not fit.  Same hits either way.
         probe_column: the screened libraries keep, beside the packed reads, the 16-mers the filter's first pass probes — np 4-byte words per
         read, built once when a library is added (k = 51 on 150 bases: 12 of a read's 38 bytes, 10.8 GB for C4's 900 M reads) — and that
         pass streams THEM; only where 4 * np is at most half a packed read and the column fits (else nothing is built and the pass reads
@@ -181,6 +188,7 @@ class Pipeline:
         self.k_screen = int(k_screen) if k_screen else (min(a for a, _ in self.kk) if self.kk else 31)
         self.keep_read_ids = bool(keep_read_ids) or bool(pair_span)
         self.key_column = bool(key_column)
+        self.linear_keys = self.key_column and bool(linear_keys)
         self.probe_column = bool(probe_column)
         # merge_in_step: the contig-merge round (assemble_gaps.py:301-306 run_contigs_merge: dedup + ContigsMerger per gap) runs INSIDE the
         # step, on the device, for the gaps the first pick leaves open, followed by a second pick over the merged contigs — the reference
@@ -237,7 +245,10 @@ class Pipeline:
         lb.d_cnt = torch.zeros(32, dtype=torch.int32, device=dev)
         lb.cp = lb.d_cnt.data_ptr()
         lb.d_ids = None
-        if self.key_column and lb.d_rec_keys is None:
+        if self.linear_keys:
+            self._linear_keys(lb)
+        # the 8-byte column: where there is no linear one, and for a consumer of its own (gap_span reads lb.d_rec_keys)
+        if self.key_column and lb.d_rec_keys is None and (lb.d_lin_keys is None or self.gap_span is not None):
             lb.d_rec_keys = torch.empty(lb.n_recs + 1, dtype=torch.int64, device=dev)
             torch.cuda.synchronize()
             self._chk(self.lib.gf_alnrec_keys_dev(self.h, lb.d_recs.data_ptr(), lb.n_recs, lb.d_rec_keys.data_ptr()), "gf_alnrec_keys_dev")
@@ -246,6 +257,29 @@ class Pipeline:
             self._probe_column(lb)
         self.libs.append(lb)
         return lb
+
+    def _linear_keys(self, lb):
+        """The library's linear key column for THIS context's scaffolds: kept when it was built for the library's record count and these
+        scaffolds (the tagger checks base[] against the layout's checksum at every map it builds), built otherwise; None where the draft
+        does not fit one 32-bit line or the column does not fit the device (the 8-byte column then serves)."""
+        ns = self.gf.n_scaffolds
+        if lb.d_lin_keys is not None and lb.lin_layout is not None and lb.lin_layout.use and \
+                (lb.lin_layout.n_recs, lb.lin_layout.n_scaffolds) == (lb.n_recs, ns):
+            return
+        lb.d_lin_keys = lb.lin_layout = None
+        if not lb.n_recs or not ns:
+            return
+        try:
+            d_col = torch.empty(self.lib.gf_alnrec_linkeys_bytes(lb.n_recs, ns) // 4, dtype=torch.int32, device=self.dev)
+        except torch.cuda.OutOfMemoryError:
+            return
+        torch.cuda.synchronize()
+        lay = B.TagLayout()
+        self._chk(self.lib.gf_alnrec_linkeys_dev(self.h, lb.d_recs.data_ptr(), lb.n_recs, d_col.data_ptr(), 4 * d_col.numel(), C.byref(lay)),
+                  "gf_alnrec_linkeys_dev")
+        self.gf.sync()
+        if lay.use:
+            lb.d_lin_keys, lb.lin_layout = d_col, lay
 
     def _probe_column(self, lb):
         """The library's probe column for THIS pipeline's screen (k_screen, read length, the library's reads): kept when it was built for
@@ -303,6 +337,13 @@ class Pipeline:
             self.gap_span.enqueue(lb)
 
     def _tag(self, lb):
+        if self.linear_keys and lb.d_lin_keys is not None:   # (the library checks the layout again: a stale column is not used)
+            keys8 = lb.d_rec_keys.data_ptr() if lb.d_rec_keys is not None else None
+            self._chk(self.lib.gf_tag_alignments_linkeys_dev(lb.h2, lb.d_recs.data_ptr(), lb.d_lin_keys.data_ptr(), C.byref(lb.lin_layout), keys8,
+                                                             lb.n_recs, lb.is_mean, lb.is_sd, self.clip_dist, self.anchor_mapq, lb.d_thits.data_ptr(),
+                                                             lb.hit_cap, lb.cp + 4 * CNT_TAG, lb.d_low.data_ptr(), lb.hit_cap, lb.cp + 4 * CNT_LOW),
+                      "gf_tag_alignments_linkeys_dev")
+            return
         if self.key_column and lb.d_rec_keys is not None:
             self._chk(self.lib.gf_tag_alignments_keys_dev(lb.h2, lb.d_recs.data_ptr(), lb.d_rec_keys.data_ptr(), lb.n_recs, lb.is_mean, lb.is_sd, self.clip_dist,
                                                           self.anchor_mapq, lb.d_thits.data_ptr(), lb.hit_cap, lb.cp + 4 * CNT_TAG, lb.d_low.data_ptr(),

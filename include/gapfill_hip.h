@@ -394,6 +394,40 @@ int gf_alnrec_keys_dev(gf_ctx* ctx, const void* d_recs, size_t n, void* d_keys /
 int gf_tag_alignments_keys_dev(gf_ctx* ctx, const void* d_recs, const void* d_keys, size_t n, int insert_size, int sd, int clip_dist,
                                int anchor_mapq, void* d_out, size_t cap, void* d_n_out, void* d_low /* gf_lowrec or NULL */, size_t low_cap,
                                void* d_n_low /* u32 or NULL */);
+/* The same pass over a LINEAR KEY COLUMN: 4 bytes per record.  The scaffolds of the draft are laid end to end — scaffold s starts at base[s], the
+ * prefix sum of the scaffolds' ends (max(pos) + 1 over the library's placed records), each rounded up to a granule of 2^granule_log2 — and a
+ * record's key is base[ref] + pos, 0xFFFFFFFF for an unplaced record, a scaffold the context does not know and the pad.  Every tag map bins with
+ * a shift of at most granule_log2, so no bin covers two scaffolds and "which bin of which scaffold" is one shift of the key.  The MAPQ-0 bit
+ * of the 8-byte key moves to a bit plane, one bit per record.
+ *   gf_tag_layout_from_ends  the layout of given scaffold ends (host only, no context): base[] (n_scaffolds + 1 words, optional), the largest
+ *                          granule for which the whole line stays below 2^32 - 2^granule_log2 and the default LDS map's bins are no wider than
+ *                          a granule; `use` = 0 when there is none (a draft beyond 4 Gb): the 8-byte column then serves
+ *   gf_alnrec_linkeys_bytes  bytes of the column: [keys: n rounded up to 4, + 4 | plane: 32 bytes per 256 records, from a 32-byte boundary |
+ *                          base: n_scaffolds + 1 words]
+ *   gf_alnrec_linkeys_dev  measures the ends (one pass over the records), lays the scaffolds out and, where built_for->use comes back 1, writes
+ *                          the column (a second pass)
+ *   gf_tag_alignments_linkeys_dev  gf_tag_alignments_keys_dev on the linear column when it was built for THIS call — record count, scaffold
+ *                          count, a checksum of base[] — and the maps' bins fit its granule; otherwise the call answers from d_keys_or_null
+ *                          (the 8-byte column) or, without one, from the records.  Same hits and MAPQ-0 list either way. */
+typedef struct {
+    uint64_t n_recs;
+    uint64_t span;            /* base[n_scaffolds]: the length of the line */
+    uint64_t checksum;        /* FNV-1a (64 bit) over the n_scaffolds + 1 words of base[], low byte first */
+    uint32_t n_scaffolds;
+    uint32_t granule_log2;
+    uint32_t use;             /* 1: a column of this layout can be built and streamed; 0: keep none */
+    uint32_t reserved;
+} gf_tag_layout;
+int gf_tag_layout_from_ends(const uint32_t* ends, uint32_t n_scaffolds, uint64_t n_recs, gf_tag_layout* out, uint32_t* base_or_null);
+size_t gf_alnrec_linkeys_bytes(size_t n, uint32_t n_scaffolds);
+int gf_alnrec_linkeys_dev(gf_ctx* ctx, const void* d_recs, size_t n, void* d_col, size_t col_bytes /* >= gf_alnrec_linkeys_bytes: GF_E_NOSPACE */,
+                          gf_tag_layout* built_for);
+int gf_tag_alignments_linkeys_dev(gf_ctx* ctx, const void* d_recs, const void* d_col, const gf_tag_layout* built_for, const void* d_keys_or_null,
+                                  size_t n, int insert_size, int sd, int clip_dist, int anchor_mapq, void* d_out, size_t cap, void* d_n_out,
+                                  void* d_low /* gf_lowrec or NULL */, size_t low_cap, void* d_n_low /* u32 or NULL */);
+/* What the last tagger pass on this context launched: waves per workgroup (1, 4 or 16) and what it streamed — 0 the records, 1 the 8-byte key
+ * column, 2 the linear key column. */
+int gf_tag_last_launch(gf_ctx* ctx, int* waves_per_workgroup, int* stream_form);
 int gf_tag_low_mapq_compact_dev(gf_ctx* ctx, const void* d_low, const void* d_n_low, size_t low_cap, const gf_dpos* table,
                                 size_t n_rows, void* d_out, size_t cap, void* d_n_out);
 /* The second-hop table itself on the device (replaces collect_discordant_regions_v2 + sort(1) + the per-scaffold split,

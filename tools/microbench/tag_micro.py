@@ -1,5 +1,7 @@
-"""micro-benchmark: tagger kernel time on the C4 layout (200 M records): the 32-byte record stream against the 8-byte key column, with /
-without the MAPQ-0 by-product, short and long inserts; GF_DIAGNOSTICS=1 adds the key-column kernel with parts switched off (tag_dbg)."""
+"""micro-benchmark: tagger kernel time on the C4 layout (200 M records): the 32-byte record stream against the 8-byte key column and the
+4-byte linear key column, with / without the MAPQ-0 by-product, short and long inserts; GF_DIAGNOSTICS=1 adds the two key-column kernels with
+parts switched off (tag_dbg)."""
+import ctypes as C
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np, torch
@@ -26,16 +28,27 @@ d_keys = torch.empty(n + 1, dtype=torch.int64, device=dev)
 torch.cuda.synchronize()
 assert lib.gf_alnrec_keys_dev(gf.handle, d_recs.data_ptr(), n, d_keys.data_ptr()) == 0
 gf.sync()
+d_lin = torch.empty(lib.gf_alnrec_linkeys_bytes(n, 620) // 4, dtype=torch.int32, device=dev)
+lay = B.TagLayout()
+torch.cuda.synchronize()
+assert lib.gf_alnrec_linkeys_dev(gf.handle, d_recs.data_ptr(), n, d_lin.data_ptr(), 4 * d_lin.numel(), C.byref(lay)) == 0 and lay.use == 1
+gf.sync()
 diag = bool(os.environ.get("GF_DIAGNOSTICS"))
 for ins, sd in ((300, 30), (5000, 500)):
-    for name, keyed, low, dbg in [("records", 0, 1, 0), ("keys", 1, 1, 0), ("keys, no by-product", 1, 0, 0)] + \
-                                 ([("keys dbg: by-product off in the kernel", 1, 1, 1), ("keys dbg: nothing passes the bin map", 1, 1, 2),
-                                   ("keys dbg: stream only", 1, 1, 3), ("keys dbg: candidates dropped", 1, 1, 4)] if diag else []):
+    variants = [("records", 0, 1, 0), ("keys", 1, 1, 0), ("keys, no by-product", 1, 0, 0), ("linear keys", 2, 1, 0),
+                ("linear keys, no by-product", 2, 0, 0)]
+    for w, k in (("keys", 1), ("linear keys", 2)) if diag else ():
+        variants += [("%s dbg: by-product off in the kernel" % w, k, 1, 1), ("%s dbg: nothing passes the bin map" % w, k, 1, 2),
+                     ("%s dbg: stream only" % w, k, 1, 3), ("%s dbg: candidates dropped" % w, k, 1, 4)]
+    for name, keyed, low, dbg in variants:
         if diag:
             gf.set_option("tag_dbg", dbg)
         for it in range(4):
             lo = (d_low.data_ptr(), cap, d_cnt.data_ptr() + 4) if low else (None, 0, None)
-            if keyed:
+            if keyed == 2:
+                rc = lib.gf_tag_alignments_linkeys_dev(gf.handle, d_recs.data_ptr(), d_lin.data_ptr(), C.byref(lay), None, n, ins, sd, 250, 30, d_out.data_ptr(), cap,
+                                                       d_cnt.data_ptr(), *lo)
+            elif keyed:
                 rc = lib.gf_tag_alignments_keys_dev(gf.handle, d_recs.data_ptr(), d_keys.data_ptr(), n, ins, sd, 250, 30, d_out.data_ptr(), cap, d_cnt.data_ptr(), *lo)
             else:
                 rc = lib.gf_tag_alignments_low_dev(gf.handle, d_recs.data_ptr(), n, ins, sd, 250, 30, d_out.data_ptr(), cap, d_cnt.data_ptr(), *lo)
