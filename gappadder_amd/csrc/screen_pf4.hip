@@ -676,12 +676,17 @@ __global__ __launch_bounds__(1024) void pf4_probe_kernel(Part4Params Q) {
             const uint32_t n = Q.count[(size_t)b * Q.n_writers + w];
             const uint32_t* src = Q.pairs + ((size_t)b * Q.n_writers + w) * Q.cap;
             constexpr int PB = 16;   // entries per lane and trip: four 16-byte loads (eight: 0.86 vs 0.81 ms per 675 M pairs) (lane = four consecutive entries of each 1 024-byte row)
-            uint4 nx4[PB / 4];
+            u32x4 nx4[PB / 4];
+            // The pairs pass through ONCE (10.8 GB per launch at C4) and are loaded NON-TEMPORALLY, as the tagger loads its key stream: they do
+            // not take the L2s' lines from the exact set's.  Measured at C4 (rocprofv3, 7 dispatches per build, all builds in one session):
+            // 2.78 -> 2.41-2.44 ms per launch; the fetched bytes hardly move (15.4 -> 15.3 GB), so it is not the bytes that the time follows —
+            // with the set laid out by bucket and an XCD working on two buckets at a time (tried, not kept) the fetches fell to 11.1 GB and
+            // the time stayed 2.44 ms (2.50 without these loads): DESIGN.md §4.
             auto fetch = [&](uint32_t i0) {
 #pragma unroll
                 for (int c = 0; c < PB / 4; ++c) {
                     const uint32_t at = i0 + (c * 64 + lane) * 4;
-                    nx4[c] = at < n ? *reinterpret_cast<const uint4*>(src + at) : make_uint4(0, 0, 0, 0);   // (a part's capacity is a multiple of 64 entries)
+                    nx4[c] = at < n ? __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src) + (at >> 2)) : u32x4{0, 0, 0, 0};   // (a part's capacity is a multiple of 64 entries)
                 }
             };
             fetch(0);
@@ -705,9 +710,13 @@ __global__ __launch_bounds__(1024) void pf4_probe_kernel(Part4Params Q) {
                     passm |= ((wd[u] >> b1) & (wd[u] >> b2) & (wd[u] >> s16_bit3_of(b1, b2)) & 1u) << u;
                 }
                 if (i0 + PB * 64 > n) {   // the part's last trip: entries behind its end do not count
+                    uint32_t keep = 0;   // (per load its first min(4, n - at) entries: no sixteen mask constants in registers)
 #pragma unroll
-                    for (int u = 0; u < PB; ++u)
-                        if (i0 + ((u >> 2) * 64 + lane) * 4 + (u & 3) >= n) passm &= ~(1u << u);
+                    for (int c = 0; c < PB / 4; ++c) {
+                        const uint32_t at = i0 + (c * 64 + lane) * 4, k = at >= n ? 0u : n - at < 4u ? n - at : 4u;
+                        keep |= ((1u << k) - 1u) << (4 * c);
+                    }
+                    passm &= keep;
                 }
                 // The passing entries (1.2 % at C4: a dozen per trip, nearly all lanes none or one) leave lane by lane, lowest bit first: one
                 // round per entry of the lane that holds most — two on average — where a ballot per entry SLOT ran sixteen rounds, nine of
