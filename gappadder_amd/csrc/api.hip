@@ -267,6 +267,12 @@ int gf_set_option(gf_ctx* ctx, const char* name, long value) {
     if (!strcmp(name, "tag_nt")) { ctx->tag_nt = value != 0; return GF_OK; }
     if (!strcmp(name, "screen_keep_cand")) { if (value && !getenv("GF_DIAGNOSTICS")) return GF_E_UNSUPPORTED; ctx->screen_keep_cand = value != 0; return GF_OK; }
     if (!strcmp(name, "screen_pf4_cap8")) { ctx->screen_pf4_cap8 = (int)value; return GF_OK; }
+    if (!strcmp(name, "screen_pf4_writers")) {
+        if (value < 0 || value > 256) return GF_E_INVAL;
+        if (value && !getenv("GF_DIAGNOSTICS")) return GF_E_UNSUPPORTED;
+        ctx->screen_pf4_writers = (int)value;
+        return GF_OK;
+    }
     if (!strcmp(name, "screen_ext")) { ctx->screen_ext = value != 0; return GF_OK; }
     if (!strcmp(name, "screen_verify_batch")) { ctx->screen_verify_batch = (int)value; return GF_OK; }
     if (!strcmp(name, "screen_verify_ext")) { ctx->screen_verify_ext = value != 0; return GF_OK; }

@@ -131,6 +131,7 @@ struct gf_ctx {
     int screen_keep_cand = 0;    // diagnostics (option screen_keep_cand, refused unless GF_DIAGNOSTICS is set): keep a copy of the partitioned filter's candidate list
     gf_screen_view screen_view = {};   // the last partitioned filter's workspace (gf_screen_debug_view)
     int screen_pf4_cap8 = 0;     // tests: capacity of the 4-byte filter's pair list (0: sized from the reads)
+    int screen_pf4_writers = 0;  // tests (option screen_pf4_writers, refused unless GF_DIAGNOSTICS is set): at most this many pass-A writers (0: automatic) — few writers make long parts on small inputs
     int screen_lds_log2_max = 20;   // coarse LDS bitmap of the screen: at most 2^20 bits (128 KiB)
     int tag_dbg = 0;             // diagnostics of the key-column tagger (option tag_dbg, refused unless GF_DIAGNOSTICS is set)
     int tag_light = 0;           // alignment tagger: one-wave workgroups, bin map through L1/L2 (runs beside the k-mer filter)

@@ -460,6 +460,7 @@ ScreenPlan plan_screen(const gf_ctx* ctx, const FlankIndex& ix, size_t n_reads, 
     const size_t tiles_wg = (size_t)PF2_WAVES * PF2_TILES;      // tiles per workgroup and iteration
     // (the pair list carries the writer in 8 bits; an empty read set plans like one tile — nothing is launched for it)
     S.n_writers = (uint32_t)std::max<size_t>(std::min<size_t>(std::min<size_t>((tiles64 + tiles_wg - 1) / tiles_wg, (size_t)ctx->n_cu), 256), 1);
+    if (ctx->screen_pf4_writers > 0) S.n_writers = std::min(S.n_writers, (uint32_t)ctx->screen_pf4_writers);   // tests: long parts on small inputs (several trips of pass B)
     S.tiles_wg = (uint32_t)tiles_wg;
     const size_t n_iter = (tiles64 + (size_t)S.n_writers * tiles_wg - 1) / ((size_t)S.n_writers * tiles_wg);
     const double pairs_w = (double)n_iter * tiles_wg * 64.0 * np;

@@ -112,6 +112,8 @@ int gf_stream_wait_after_filter(gf_ctx* waiter, gf_ctx* producer);
  * partitioned filter drops seeds whose neighbouring bases are none of the flanks'; 0: 16-base seeds as they are),
  * "screen_verify_ext" (1: seed-and-extend verification when min_hits == 1), "screen_verify_gate",
  * "screen_verify_batch", "screen_stream_policy", "screen_lds_log2_max", "screen_pf4_cap8",
+ * "screen_pf4_writers" (a test aid, refused unless GF_DIAGNOSTICS is set: at most this many writers in the partitioned filter's first pass,
+ * 0 = automatic),
  * "asm_keyslot", "asm_precount", "asm_ranked", "asm_lds_pool_kb", "asm_threads" (threads per gap: 1024 / 512 / 256; 0 = automatic:
  * 512 — two gaps per CU — when there are >= 8 gaps per CU and asm_max_pool_reads says that most pools fit half a CU's LDS, the gaps
  * that do not are handed to a second launch with 1024), "asm_stats_ptr" (device u64[4] the assembly adds its window / k-mer / survivor / node counts to), "asm_dbg_ptr".
