@@ -42,6 +42,7 @@ struct AsmParams {
     uint32_t* nodes;           // 3 words per instance: per-node meta + succ[2] when they do not fit in LDS
     uint32_t* jump;            // 4 words per instance: the unitig-ranking pairs of the oriented nodes when they do not fit in LDS
     uint32_t simplify;         // rounds of tip clipping + bubble popping (0: raw unitigs)
+    uint32_t er_jump;          // 1: error-removal candidates walk a jump table over the unitig links where the pairs live in LDS (option asm_er_jump; 0: the plain walk)
     uint32_t tiebreak_counts;  // 1: between equal coverage the side with fewer WEAK nodes wins (option asm_tiebreak; 0: that rule is off)
     uint32_t slice_rows;       // > 0: the workspace holds one slice of this many pool rows per workgroup
     uint64_t slice_base;       // ... the first of them starts at this instance offset
@@ -1409,26 +1410,51 @@ __device__ __forceinline__ void assemble_body(const AsmParams& P, AsmShared<NT>&
         //      BUBBLE (<= 2 kv nodes between two junctions that an alternative path of the same length also joins).  Candidates are
         //      short, so heads WALK the links (no ranking needed yet): a decision only sets the KILL bit of X's end nodes; after the
         //      barrier the arcs into X are cleared at their sources, X's nodes die, and the junctions that lost a branch re-link.
-        // unitig headed by h: tail and node count, false when it has more than `limit` nodes
         // (cov = coverage sum << 32 | nodes that are not weak: "more coverage, then fewer weak nodes" is one 64-bit comparison
         //  between unitigs of the same node count — the only ones whose coverage is ever compared)
         auto cov_of = [&](uint32_t m) -> unsigned long long {
             return ((unsigned long long)(m >> M_MULT_SHIFT) << 32) | ((m & M_WEAK) ? 0u : 1u);   // (nmeta carries no fingerprint)
         };
         // (a round has a dozen candidates per gap — 9 at C4, 38 at C5's k = 31 — and lasts as long as the slowest one's chain of walks and
-        //  look-ups: a step of the walk asks for the node's successor and its coverage TOGETHER, one LDS round trip instead of two)
-        auto walk = [&](uint32_t h, uint32_t limit, uint32_t& tail, uint32_t& n, unsigned long long& cov) -> bool {
+        //  look-ups: 34 of the phase's 49 us at C4 were the evaluation of round 0, most of it one lane chasing succ through LDS for up to
+        //  2 kv nodes per walk, the gap's other threads at the barrier)
+        // JUMP TABLE (plan 0, option asm_er_jump): the ranking's pair workspace is idle here, one 32-bit word per oriented node — {steps, target}:
+        // `target` lies `steps` links ahead along succ, steps == 0 exactly for a tail.  Built from succ by all threads at the top of a round
+        // (never older than a change to succ), refined by ER_JUMP_ROUNDS rounds of pointer doubling — a FIXED number: isolated cycles are
+        // among the oriented nodes and just stop.  Words are read and written whole, so the in-place, unsynchronised update keeps "target is
+        // steps ahead" in any order of the threads (the ranking's argument).  A walk follows the jumps: the count never overshoots the
+        // unitig's true length, so "more than limit" is the plain walk's answer, reached in limit / 2^rounds hops; otherwise it ends on the
+        // tail with the exact count.  (Measured at C4: build 5 us, evaluation 34 -> 18 us; 3 / 4 / 5 rounds within 1 us of each other.)
+        // Plans 1 and 2 keep the pairs in the global slice: their walks chase succ as before.
+        constexpr int ER_JUMP_ROUNDS = 4;
+        bool er_jump = false;                             // this round's walks use the table (workgroup-uniform)
+        const Pairs JT{true, Joff, nullptr};              // (in use only where j_lds holds: the LDS side at compile time)
+        // The coverage sum does not ride along a walk (one word per node is all plan 0 has, and two live 64-bit sums per candidate cost
+        // scratch): `beats` fetches it with a plain walk of unitigs that have qualified — at most `limit` nodes, always for a bubble, for a
+        // tip only between equal node counts.
+        auto cov_sum = [&](uint32_t h) -> unsigned long long {
+            unsigned long long cov = 0;
+            for (uint32_t cur = h; cur != EMPTY32; cur = succ_get(cur)) cov += cov_of(nmeta.get(cur >> 1));
+            return cov;
+        };
+        // unitig headed by h: tail and node count, false when it has more than `limit` nodes
+        auto walk = [&](uint32_t h, uint32_t limit, uint32_t& tail, uint32_t& n) -> bool {
             uint32_t cur = h;
             n = 1;
-            cov = 0;                             // the coverage sum rides along: no second walk when two unitigs are compared
             for (;;) {
-                const uint32_t nx = succ_get(cur);
-                const uint32_t m = nmeta.get(cur >> 1);
-                cov += cov_of(m);
-                if (nx == EMPTY32) break;
-                if (n == limit) return false;
+                uint32_t st, nx;
+                if (er_jump) {
+                    const unsigned long long w = JT.load(cur);
+                    st = (uint32_t)(w >> 32);
+                    nx = (uint32_t)w;
+                } else {
+                    nx = succ_get(cur);
+                    st = nx != EMPTY32;
+                }
+                if (!st) break;
+                n += st;
+                if (n > limit) return false;
                 cur = nx;
-                ++n;
             }
             tail = cur;
             return true;
@@ -1439,9 +1465,10 @@ __device__ __forceinline__ void assemble_body(const AsmParams& P, AsmShared<NT>&
             const K128 a = node_seq(h), b = node_seq(t ^ 1u);
             return b < a ? b : a;
         };
-        // does the unitig headed by y (tail ty, ny nodes, coverage cy) beat the one headed by x?
-        auto beats = [&](uint32_t y, uint32_t ty, uint32_t ny, unsigned long long cy, uint32_t x, uint32_t tx, uint32_t nx, unsigned long long cx, bool with_len) __attribute__((always_inline)) -> bool {
+        // does the unitig headed by y (tail ty, ny nodes) beat the one headed by x?
+        auto beats = [&](uint32_t y, uint32_t ty, uint32_t ny, uint32_t x, uint32_t tx, uint32_t nx, bool with_len) __attribute__((always_inline)) -> bool {
             if (with_len && ny != nx) return ny > nx;
+            const unsigned long long cy = cov_sum(y), cx = cov_sum(x);
             if (cy != cx) return cy > cx;     // equal node counts here: more coverage, then fewer weak nodes
             return uni_key(y, ty) < uni_key(x, tx);
         };
@@ -1463,14 +1490,32 @@ __device__ __forceinline__ void assemble_body(const AsmParams& P, AsmShared<NT>&
             const uint32_t n_cand = s_cand;
             const bool er_lds = graph_lds && n_cand <= ERQ;      // the queue went through LDS
             if (!er_lds) wg_phase_sync();
+            er_jump = P.er_jump && j_lds && n_cand <= ERQ && n_cand;    // (beyond ERQ the queue's overflow lies in these words)
+            if (er_jump) {
+                for (uint32_t o = tid; o < n_or; o += ASM_THREADS) {
+                    const uint32_t nx = succ_get(o);
+                    JT.store(o, nx == EMPTY32 ? (unsigned long long)o : (1ull << 32) | nx);
+                }
+                __syncthreads();
+                for (int jr = 0; jr < ER_JUMP_ROUNDS; ++jr) {
+                    for (uint32_t o = tid; o < n_or; o += ASM_THREADS) {
+                        const unsigned long long a0 = JT.load(o);
+                        if (!(a0 >> 32)) continue;
+                        const unsigned long long a1 = JT.load((uint32_t)a0);
+                        const uint32_t st = (uint32_t)(a0 >> 32) + (uint32_t)(a1 >> 32);
+                        if (!(a1 >> 32) || st > 0xFFFFu) continue;      // (a cycle's counts grow without end: they stay within the half word)
+                        JT.store(o, ((unsigned long long)st << 32) | (uint32_t)a1);
+                    }
+                    __syncthreads();
+                }
+            }
             // dealt round-robin over the WAVES (candidate q -> wave q mod 16): every wave gets as few divergent lanes as possible and
             // all waves' latency chains overlap (packing them into the first waves measured slower than no queue at all)
             for (uint32_t qi = (tid & 63) * (ASM_THREADS / 64) + (tid >> 6); qi < n_cand; qi += ASM_THREADS) {
                 const uint32_t o = qi < ERQ ? s_erq[qi] : (uint32_t)J.load(qi);
                 const uint32_t ib = inb(o);
                 uint32_t t, n;
-                unsigned long long cx;
-                if (!walk(o, 2 * PKV, t, n, cx)) continue;
+                if (!walk(o, 2 * PKV, t, n)) continue;
                 const K128 hs = node_seq(o);
                 const uint32_t p = find_oriented(shift_in_front(hs, __ffs(ib) - 1, kv));
                 if (p == EMPTY32) continue;
@@ -1485,9 +1530,8 @@ __device__ __forceinline__ void assemble_body(const AsmParams& P, AsmShared<NT>&
                         const uint32_t y = find_oriented(shift_in(ps, c, kv));
                         if (y == EMPTY32 || y == o || has_pred(y) || y == (t ^ 1u)) continue;
                         uint32_t ty, ny;
-                        unsigned long long cy;
-                        const bool tip_shaped = walk(y, PKV, ty, ny, cy) && outb(ty) == 0 && __popc(inb(y)) == 1;
-                        if (!tip_shaped || beats(y, ty, ny, cy, o, t, n, cx, true)) go = true;
+                        const bool tip_shaped = walk(y, PKV, ty, ny) && outb(ty) == 0 && __popc(inb(y)) == 1;
+                        if (!tip_shaped || beats(y, ty, ny, o, t, n, true)) go = true;
                     }
                 } else if (__popc(tb) == 1) {                                   // BUBBLE (n <= 2 kv by the walk)
                     const uint32_t s = find_oriented(shift_in(node_seq(t), __ffs(tb) - 1, kv));
@@ -1504,8 +1548,7 @@ __device__ __forceinline__ void assemble_body(const AsmParams& P, AsmShared<NT>&
                             const uint32_t y = find_oriented(shift_in(node_seq(q), c, kv));
                             if (y == EMPTY32 || has_pred(y) || y == o || y == (t ^ 1u)) continue;
                             uint32_t ty, ny;
-                            unsigned long long cy;
-                            if (!walk(y, rem, ty, ny, cy)) continue;             // more nodes than remain
+                            if (!walk(y, rem, ty, ny)) continue;             // more nodes than remain
                             if (ny == rem) {
                                 const uint32_t yb = outb(ty);
                                 bool reaches = false;
@@ -1513,7 +1556,7 @@ __device__ __forceinline__ void assemble_body(const AsmParams& P, AsmShared<NT>&
                                 for (uint32_t c2 = 0; c2 < 4; ++c2)
                                     if (((yb >> c2) & 1u) && find_oriented(shift_in(tys, c2, kv)) == s) reaches = true;
                                 if (!reaches) continue;
-                                if (sp >= 1 || beats(y, ty, ny, cy, o, t, n, cx, false)) go = true;
+                                if (sp >= 1 || beats(y, ty, ny, o, t, n, false)) go = true;
                             } else if (sp + 1 < 4) {
                                 ++sp;
                                 st_q[sp] = ty; st_rem[sp] = rem - ny; st_c[sp] = 0;
@@ -1956,6 +1999,7 @@ AsmParams asm_params(const gf_ctx* ctx, const AsmGeom& G, const AsmIO& io, int k
     P.jump = (uint32_t*)ctx->asm_jump.p;
     P.simplify = (uint32_t)std::max(0, ctx->asm_simplify);
     P.tiebreak_counts = ctx->asm_tiebreak ? 1u : 0u;
+    P.er_jump = ctx->asm_er_jump ? 1u : 0u;
     P.slice_rows = (uint32_t)G.slice_rows;
     P.contigs = (gf_contig*)io.d_contigs;
     P.contig_cap = (uint32_t)io.contig_cap;

@@ -142,6 +142,7 @@ struct gf_ctx {
     long asm_max_pool_reads = 0; // > 0: no pool has more rows than this (the assembly workspace is then one slice per workgroup, not per row)
     long asm_big_pool_reads = 131072;   // ... and pools beyond asm_max_pool_reads go to a second launch whose slices hold this many rows (a pool beyond this sets its gap_error)
     int asm_tiebreak = 1;        // error removal, equal coverage: 1 = fewer weak nodes (k-mers seen <= min_count + 1 times) win; 0 = sequence order alone
+    int asm_er_jump = 1;         // error removal: candidates walk a jump table over the unitig links where the pairs live in LDS (option asm_er_jump; 0, the plain walk, is refused unless GF_DIAGNOSTICS is set)
     int asm_keyslot = 1;         // count phase: key-in-slot LDS table when k <= 31 and min_count <= 2 (0: instance ids)
     int asm_ranked = 1;          // count phase: ranked (perfect-hash) table behind the pre-count (k > 32, LDS)
     int asm_last_threads = 0;    // the last launch_assemble: threads per gap of its main launch ...
