@@ -89,7 +89,7 @@ __device__ __forceinline__ HopBuckets hop_buckets(uint32_t n_scaffolds, uint32_t
     return h;
 }
 __device__ __forceinline__ uint32_t hop_bucket_of(const HopBuckets& h, unsigned long long key) {
-    const uint32_t sub = (uint32_t)key >> h.pos_shift;
+    const uint32_t sub = h.pos_shift < 32 ? (uint32_t)key >> h.pos_shift : 0u;   // (no sub-buckets and a position >= 2^31: a shift of 32)
     return ((uint32_t)(key >> 32) << h.sub_bits) | (sub < (1u << h.sub_bits) ? sub : (1u << h.sub_bits) - 1u);
 }
 __global__ __launch_bounds__(256) void hop_bucket_count_kernel(const unsigned long long* keys, const uint32_t* n_rows, uint32_t row_cap, uint32_t n_scaffolds,
@@ -221,8 +221,9 @@ __global__ __launch_bounds__(256) void hop_rows_kernel(const unsigned long long*
 
 // Union of several SORTED tables (one per source rank; gf_second_hop_table_dev leaves each sorted by (mate scaffold, mate position)):
 // a row's place in the union is its index in its own part + the rows of the parts before it that are <= its key + the rows of the
-// parts behind it that are < its key — a binary search per other part, no second sort.  (Round 3 re-sorted the padded union with a
-// radix sort on every rank and step: 0.9 ms at C4 that did not shrink with the number of ranks.)
+// parts behind it that are < its key — a binary search per other part, no second sort.  The union is therefore the stable merge of the
+// parts: among equal keys an earlier part comes first and the rows of one part keep their order.  (Round 3 re-sorted the padded union
+// with a radix sort on every rank and step: 0.9 ms at C4 that did not shrink with the number of ranks.)
 __device__ __forceinline__ unsigned long long dpos_key(const gf_dpos& d) { return ((unsigned long long)d.mate_scaffold << 32) | d.mate_pos; }
 __global__ __launch_bounds__(256) void hop_merge_kernel(const gf_dpos* rows_all, const uint32_t* row_gap_all, const uint32_t* n_rows_all,
                                                         uint32_t n_parts, uint32_t part_cap, gf_dpos* rows, uint32_t* row_gap, uint32_t row_cap,

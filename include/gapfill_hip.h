@@ -435,15 +435,20 @@ int gf_tag_low_mapq_compact_dev(gf_ctx* ctx, const void* d_low, const void* d_n_
 /* The second-hop table itself on the device (replaces collect_discordant_regions_v2 + sort(1) + the per-scaffold split,
  * run_multi_threads_discordant.py:19-122): one row per DISCORDANT tagger hit whose mate lies on a known scaffold,
  * {mate_ref, mate_pos of the hit's record; scaffold, idx_in_scaffold of the hit's gap}, sorted by (mate scaffold, mate
- * position) with one radix sort.  d_rows (gf_dpos[row_cap]) and d_row_gap (u32[row_cap]: index of each row's gap, for
+ * position): a counting sort into at most 2^14 buckets of (scaffold, top bits of the position), then one wave's bitonic
+ * network per bucket — no library sort.  d_rows (gf_dpos[row_cap]) and d_row_gap (u32[row_cap]: index of each row's gap, for
  * gf_pool_keys_from_second_hop_dev) are the caller's device buffers; *d_n_rows (device u32) = rows found — more than row_cap
- * means the table is truncated (size row_cap from the number of tagger hits).  Rows with equal (scaffold, position) keep no
- * particular order (the reference's -k3n -k4n): they produce the same hits. */
+ * means the table is truncated (size row_cap from the number of tagger hits; which rows it then holds is unspecified).
+ * Rows with equal (scaffold, position) are ordered by gap index: the reference's -k3n -k4n for gaps listed in scaffold
+ * order, so the table is the reference's file row for row. */
 int gf_second_hop_table_dev(gf_ctx* ctx, const void* d_recs, const void* d_taghits, const void* d_n_taghits, size_t hit_cap,
                             void* d_rows, void* d_row_gap, size_t row_cap, void* d_n_rows);
 /* Multi-GPU runs shard the reads, but the second hop links a MAPQ-0 record to discordant mates of ANY read: every rank builds the
  * rows of its records (gf_second_hop_table_dev), the ranks all-gather rows / row gaps / counts (fixed part_cap slots), and this
- * call concatenates the n_parts slots and sorts them again — the table of a single-process run up to the order of equal keys.
+ * call merges the n_parts sorted slots by rank (a row's place = its index in its own slot + the rows <= its key in earlier slots
+ * + the rows < its key in later slots; nothing is sorted again) — the table of a single-process run up to the order of equal
+ * keys: among them an earlier slot comes first and the rows of one slot keep their order.  A count above part_cap is read as
+ * part_cap; *d_n_rows = the clamped total, of which the first row_cap rows are written.
  * d_rows_all: gf_dpos [n_parts][part_cap]; d_row_gap_all: u32 [n_parts][part_cap]; d_n_rows_all: u32 [n_parts]. */
 int gf_second_hop_table_merge_dev(gf_ctx* ctx, const void* d_rows_all, const void* d_row_gap_all, const void* d_n_rows_all, int n_parts,
                                   size_t part_cap, void* d_rows, void* d_row_gap, size_t row_cap, void* d_n_rows);
