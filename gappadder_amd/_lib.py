@@ -234,6 +234,7 @@ def lib():
         "gf_alnrec_linkeys_dev": (i32, [vp, vp, sz, vp, sz, C.POINTER(TagLayout)]),
         "gf_tag_alignments_linkeys_dev": (i32, [vp, vp, vp, C.POINTER(TagLayout), vp, sz, i32, i32, i32, i32, vp, sz, vp, vp, sz, vp]),
         "gf_tag_last_launch": (i32, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "gf_tag_kernel": (C.c_char_p, [vp]),
         "gf_assemble": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, i32, i32, i32, vp, sz, szp, vp, sz, szp]),
         "gf_assemble_dev": (i32, [vp, vp, vp, vp, sz, sz, i32, i32, i32, i32, i32, vp, sz, vp, vp, sz, vp, vp]),
         "gf_assemble_multi_dev": (i32, [vp, vp, vp, vp, sz, sz, i32, vp, vp, i32, i32, i32, vp, sz, vp, vp, sz, vp, vp]),

@@ -270,7 +270,6 @@ int gf_set_option(gf_ctx* ctx, const char* name, long value) {
     }
     if (!strcmp(name, "tag_bins_log2")) { ctx->tag_bins_log2 = std::max(13, std::min(19, (int)value)); drop_tag_maps(ctx); return GF_OK; }
     if (!strcmp(name, "tag_fine_log2")) { ctx->tag_fine_log2 = std::max(20, std::min(28, (int)value)); drop_tag_maps(ctx); return GF_OK; }
-    if (!strcmp(name, "tag_nt")) { ctx->tag_nt = value != 0; return GF_OK; }
     if (!strcmp(name, "screen_keep_cand")) { if (value && !getenv("GF_DIAGNOSTICS")) return GF_E_UNSUPPORTED; ctx->screen_keep_cand = value != 0; return GF_OK; }
     if (!strcmp(name, "screen_pf4_cap8")) { ctx->screen_pf4_cap8 = (int)value; return GF_OK; }
     if (!strcmp(name, "screen_pf4_writers")) {
@@ -508,6 +507,8 @@ int gf_tag_last_launch(gf_ctx* ctx, int* waves_per_workgroup, int* stream_form) 
     if (stream_form) *stream_form = ctx->tag_last_form;
     return GF_OK;
 }
+
+const char* gf_tag_kernel(gf_ctx* ctx) { return ctx ? ctx->tag_kernel.c_str() : ""; }
 
 int gf_gap_span_dev(gf_ctx* ctx, const void* d_recs, const void* d_keys_or_null, size_t n, int read_len, int is_mean, int is_sd, int z, int shift,
                     int min_mapq, void* d_rec, void* d_stats) {

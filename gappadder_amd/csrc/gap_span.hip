@@ -23,7 +23,7 @@ struct SpanParams {
     const uint32_t* scaf_off;
     uint32_t n_scaffolds;
     int32_t read_len, dist2, lo, hi, min_mapq;
-    const uint32_t* bin_bits;   // the tagger's map for dist2 (tagger.hip, ensure_bin_map): bits, offsets, first gap per bin
+    const uint32_t* bin_bits;   // the tagger's map for dist2 (tag_map.hip, ensure_bin_map): bits, offsets, first gap per bin
     const uint32_t* bin_off;
     const uint32_t* bin_first;
     uint32_t bin_shift, bin_words, off_words;

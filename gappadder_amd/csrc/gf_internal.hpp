@@ -166,11 +166,11 @@ struct gf_ctx {
     };
     std::vector<TagMap> tag_maps;
     uint64_t tag_map_clock = 0;
-    int tag_last_nw = 0, tag_last_form = 0;   // the last launch_tag: waves per workgroup; 0 records, 1 8-byte keys, 2 linear keys (gf_tag_last_launch)
-    // tagger: bits of the LDS bin map and of the global one behind it; non-temporal record loads.  Measured on the C4 layout (200 M
-    // records, rocprof): 2^25-bit global map 2.24 ms; + nt loads (the record stream no longer evicts the map from the L2s) 1.90 ms;
-    // 2^23 bits + nt 1.82 ms; 32 / 64 KiB LDS maps 2.85 / 3.13 ms (fewer workgroups per CU)
-    int tag_bins_log2 = 17, tag_fine_log2 = 23, tag_nt = 1;
+    int tag_last_nw = 0, tag_last_form = 0;   // the last launch_tag's plan: waves per workgroup; 0 records, 1 8-byte keys, 2 linear keys (gf_tag_last_launch)
+    std::string tag_kernel;                   // ... and the kernel it launched, "+fine" behind it where the map had a fine map (gf_tag_kernel)
+    // tagger: bits of the LDS bin map and of the global one behind it.  Measured on the C4 layout (200 M records, rocprof, non-temporal
+    // record loads: tagger.hip): 2^25-bit global map 1.90 ms; 2^23 bits 1.82 ms; 32 / 64 KiB LDS maps 2.85 / 3.13 ms (fewer workgroups per CU)
+    int tag_bins_log2 = 17, tag_fine_log2 = 23;
     // second-hop table cache
     std::vector<uint32_t> low_rows, rowgap_rows;
     std::map<int, gf::DevBuf> anchor_tabs;   // by anchor length: the flank anchors of gf_pick_anchored_dev (dropped by gf_set_gaps)
@@ -191,7 +191,7 @@ namespace gf {
 
 int set_hip_error(gf_ctx* ctx, hipError_t e, const char* what);
 int ensure(gf_ctx* ctx, DevBuf& b, size_t bytes);
-void drop_tag_maps(gf_ctx* ctx);   // (tagger.hip) frees the tagger's bin maps: the gaps or the map sizes changed
+void drop_tag_maps(gf_ctx* ctx);   // (tag_map.hip) frees the tagger's bin maps: the gaps or the map sizes changed
 
 #define GF_HIP(ctx, call)                                          \
     do {                                                           \
@@ -254,10 +254,11 @@ int launch_read_probes(gf_ctx* ctx, const FlankIndex* ix_or_null, const void* d_
 int launch_screen(gf_ctx* ctx, const FlankIndex& ix, const void* d_reads, const void* d_nmask, size_t n_reads,
                   int read_len, int min_hits, void* d_out, size_t cap, void* d_n_out, const void* d_probes = nullptr,
                   const gf_probe_geom* built_for = nullptr);
-// tagger.hip
+// tagger.hip (the plan of its launch: tag_dev.hpp)
 int launch_tag(gf_ctx* ctx, const void* d_recs, size_t n, int insert_size, int sd, int clip_dist, int anchor_mapq,
                void* d_out, size_t cap, void* d_n_out, void* d_low, size_t low_cap, void* d_n_low, const void* d_keys = nullptr,
                const void* d_lin = nullptr, const gf_tag_layout* lin_for = nullptr);
+// tag_map.hip
 int launch_alnrec_keys(gf_ctx* ctx, const void* d_recs, size_t n, void* d_keys);
 // the linear key column (gf_tag_layout; layout of the buffer: LinCol)
 struct LinCol { size_t key_words, plane_off, plane_words, base_off, bytes; };   // offsets in bytes; the keys start at 0
@@ -272,10 +273,11 @@ int ensure_bin_map(gf_ctx* ctx, int dist2, gf_ctx::TagMap** out, const gf_tag_la
 // gap_span.hip
 int launch_gap_span(gf_ctx* ctx, const void* d_recs, const void* d_keys, size_t n, int read_len, int is_mean, int is_sd, int z, int shift,
                     int min_mapq, void* d_rec, void* d_stats);
+// tag_low.hip
 int launch_low_mapq(gf_ctx* ctx, const void* d_recs, size_t n, const gf_dpos* table, size_t n_rows, void* d_out,
                     size_t cap, void* d_n_out, const void* d_low, const void* d_n_low, size_t low_cap);
 
-// second hop: hashed bit map of the table rows' neighbourhoods (hop.hip builds it, tagger.hip asks it)
+// second hop: hashed bit map of the table rows' neighbourhoods (hop.hip builds it, tag_low.hip asks it)
 constexpr uint32_t HOP_NEAR_LOG2 = 22, HOP_NEAR_SHIFT = 9;
 __host__ __device__ inline uint32_t hop_near_bit(uint32_t scaffold, uint32_t bin) {
     return ((scaffold * 0x9E3779B1u) ^ (bin * 0x85EBCA77u) ^ (bin >> 13)) >> (32 - HOP_NEAR_LOG2);

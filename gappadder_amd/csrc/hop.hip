@@ -328,7 +328,7 @@ __global__ __launch_bounds__(256) void hop_table_soff_kernel(const gf_dpos* rows
     }
 }
 
-// tagger.hip; *d_n_out must be zero already
+// tag_low.hip; *d_n_out must be zero already
 int launch_low_mapq_devtable(gf_ctx* ctx, const void* d_low, const void* d_n_low, size_t low_cap, const uint32_t* upos, const uint32_t* urow,
                              const uint32_t* soff, const uint32_t* near_bits, void* d_out, size_t cap, void* d_n_out);
 

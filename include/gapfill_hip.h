@@ -430,6 +430,10 @@ int gf_tag_alignments_linkeys_dev(gf_ctx* ctx, const void* d_recs, const void* d
 /* What the last tagger pass on this context launched: waves per workgroup (1, 4 or 16) and what it streamed — 0 the records, 1 the 8-byte key
  * column, 2 the linear key column. */
 int gf_tag_last_launch(gf_ctx* ctx, int* waves_per_workgroup, int* stream_form);
+/* The kernel that pass launched, as a profiler names it without namespace and argument list — tag_kernel<waves, map staged in LDS, records
+ * queued in front of a fine map, stream form>, e.g. "tag_kernel<16, true, false, 2>" —, with "+fine" behind it where the bin map of that
+ * launch had a fine map behind it ("" before the first launch). */
+const char* gf_tag_kernel(gf_ctx* ctx);
 int gf_tag_low_mapq_compact_dev(gf_ctx* ctx, const void* d_low, const void* d_n_low, size_t low_cap, const gf_dpos* table,
                                 size_t n_rows, void* d_out, size_t cap, void* d_n_out);
 /* The second-hop table itself on the device (replaces collect_discordant_regions_v2 + sort(1) + the per-scaffold split,

@@ -1,4 +1,4 @@
-"""The device second hop (csrc/hop.hip + the look-up of csrc/tagger.hip) restated in plain numpy, and the directed inputs its tests use.
+"""The device second hop (csrc/hop.hip + the look-up of csrc/tag_low.hip) restated in plain numpy, and the directed inputs its tests use.
 
 Part 1 is the twin: what the three device calls must return, written from the reference's definitions (the inversion + sort(1) of
 run_multi_threads_discordant.py, the look-up of collect_discordant_low_mapq_reads.py) with sorts and searches of numpy — no project

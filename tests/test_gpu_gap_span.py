@@ -5,7 +5,7 @@ scaffolds and a scaffold without gaps, on two libraries (1 500 +/- 100 and 5 000
 lie closer together than L and some closer than dist2, and on gap tables large enough for every form of bin map the launch chooses among.
 
 Which form a case reaches is established by _map_form below, a restatement in Python of the rule the library builds its maps by
-(tagger.hip, ensure_bin_map: a 16-KiB map; the 64-KiB one when more than a tenth of its bins are set; a fine map behind it when more
+(tag_map.hip, ensure_bin_map: a 16-KiB map; the 64-KiB one when more than a tenth of its bins are set; a fine map behind it when more
 than a twentieth still is and the fine bins cover at most 0.6 of what the coarse ones do) — asserted per case:
   the hand-built table, the two-library table           the small LDS map (4-wave workgroups)
   9 000 gaps over 2.6 Gb, library 1 500 +/- 100         the 64-KiB map without a fine map (16-wave workgroups)

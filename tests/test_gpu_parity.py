@@ -453,7 +453,7 @@ def test_one_pass_tagger_with_mapq0_compaction_equals_two_passes(gf):
 
 
 def test_mapq0_list_survives_many_flushes_of_the_staging_slices(gf):
-    """The MAPQ-0 by-product of the tagger leaves through per-wave staging slices of 1 024 records (tagger.hip): with 12 M records,
+    """The MAPQ-0 by-product of the tagger leaves through per-wave staging slices of 1 024 records (tagger.hip, tag_kernel): with 12 M records,
     70 % of them MAPQ 0, every wave fills and empties its slice several times.  The list must hold exactly the MAPQ-0 records with a
     valid scaffold — each once, with its position and record index — and the tagger's hits must not change."""
     import torch

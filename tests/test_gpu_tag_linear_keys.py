@@ -1,7 +1,7 @@
 """The tagger on the 4-byte LINEAR key column (gf_alnrec_linkeys_dev, gf_tag_alignments_linkeys_dev): the column and its MAPQ-0 bit plane
 against the numpy twin (tag_linear_twin.py) word for word, and the tagging against the 8-byte-key entry, the record stream and the C oracle —
-both insert-size branches, the 4-wave and the 16-wave kernel, windows at the scaffolds' ends, stale columns, and one Pipeline.step with the
-linear column on and off."""
+both insert-size branches, the 4-wave and the 16-wave kernel, each without and behind a fine map, windows at the scaffolds' ends, stale columns,
+and one Pipeline.step with the linear column on and off."""
 import ctypes as C
 
 import numpy as np
@@ -89,12 +89,18 @@ def test_column_and_plane_equal_the_twin_word_for_word(gf, n):
 def _draft(kind):
     """(gaps, n_scaffolds, scaffold ends).  small: three scaffolds, the first exactly one granule long; a gap whose left window starts below 0,
     two gaps inside one 64-base bin, a gap whose right window passes the scaffold's last record, and a gap at the very start of the next
-    scaffold.  wide: 4 x 5 Mb with eight gaps each."""
+    scaffold.  wide: 4 x 5 Mb with eight gaps each.  many: 4 x 5 Mb with 100 gaps of 1 500 bases each, evenly spaced; vast: 64 x 5 Mb with 160
+    gaps of 200 bases each — the two whose LDS map (at 2^13 / 2^19 bins) has wide bins, more than a twentieth of them set, and so a fine map."""
     from gappadder_amd import _lib as B
     if kind == "small":
         ends = [G, 40_000, 50_000]
         rows = [(0, 100, 300), (0, 20_000, 20_010), (0, 20_020, 20_030), (0, 500_000, 501_000), (0, G - 400, G - 100),
                 (1, 5, 50), (1, 20_000, 21_000), (1, 39_700, 39_990), (2, 0, 40), (2, 25_000, 25_500)]
+    elif kind in ("many", "vast"):
+        n_scf, per, glen = {"many": (4, 100, 1500), "vast": (64, 160, 200)}[kind]
+        ends = [5_000_000] * n_scf
+        step = 5_000_000 // per
+        rows = [(s, step // 2 + step * j + 7 * s, step // 2 + step * j + 7 * s + glen) for s in range(n_scf) for j in range(per)]
     else:
         ends = [5_000_000] * 4
         rows = [(s, 300_000 + 600_000 * j + 1000 * s, 300_000 + 600_000 * j + 1000 * s + 1500) for s in range(4) for j in range(8)]
@@ -140,7 +146,7 @@ def _records(gaps, n_scaffolds, ends, dist2, n_far, seed):
 
 
 def _run(gf, entry, d_recs, n, is_, sd, d_col=None, lay=None, d_keys=None):
-    """(sorted hits, sorted MAPQ-0 list, (waves per workgroup, stream form)) of one tagger entry."""
+    """(sorted hits, sorted MAPQ-0 list, (waves per workgroup, stream form), gf_tag_kernel's name of the kernel) of one tagger entry."""
     import torch
     from gappadder_amd import _lib as B
     lib = B.lib()
@@ -165,7 +171,7 @@ def _run(gf, entry, d_recs, n, is_, sd, d_col=None, lay=None, d_keys=None):
     assert nh <= cap and nl <= cap
     hits = np.frombuffer(d_hits[:nh * 12].cpu().numpy().tobytes(), dtype=B.TAGHIT)
     low = np.frombuffer(d_low[:nl * 12].cpu().numpy().tobytes(), dtype=LOWREC)
-    return np.sort(hits, order=["rec", "gap", "kind", "to_mate"]), np.sort(low, order=["rec"]), (nw.value, form.value)
+    return np.sort(hits, order=["rec", "gap", "kind", "to_mate"]), np.sort(low, order=["rec"]), (nw.value, form.value), lib.gf_tag_kernel(gf.handle).decode()
 
 
 def _keys8(gf, d_recs, n):
@@ -183,10 +189,10 @@ def cases(gf):
     """Per (draft, insert size): the records, and the hits and the MAPQ-0 list they must give — from the C oracle and from numpy, computed once."""
     from oracle import c_oracle as CO
     out = {}
-    for kind in ("small", "wide"):
+    for kind, walk in (("small", 1), ("wide", 1), ("many", 7), ("vast", 157)):    # (records around every walk-th gap: a few thousand in all)
         gaps, ns, ends = _draft(kind)
-        for is_, sd in ((300, 30), (5000, 500)):
-            recs = _records(gaps, ns, ends, is_ + 3 * sd, 1200, seed=is_ + len(kind))
+        for is_, sd in ((300, 30), (5000, 500)) if walk == 1 else ((300, 30),):
+            recs = _records(gaps[::walk], ns, ends, is_ + 3 * sd, 1200, seed=is_ + len(kind))
             want = np.sort(CO.tag_alignments(recs, gaps, is_, sd).astype(_taghit()), order=["rec", "gap", "kind", "to_mate"])
             z = np.nonzero((recs["mapq"] == 0) & (recs["ref"] < ns))[0]
             low = np.zeros(len(z), dtype=LOWREC)
@@ -200,12 +206,17 @@ def _taghit():
     return B.TAGHIT
 
 
-@pytest.mark.parametrize("is_,sd", [(300, 30), (5000, 500)])
-@pytest.mark.parametrize("kind,bins_log2,waves", [("small", 17, 4), ("wide", 19, 16)])
+@pytest.mark.parametrize("kind,bins_log2,waves,is_,sd", [
+    ("small", 17, 4, 300, 30), ("small", 17, 4, 5000, 500), ("wide", 19, 16, 300, 30), ("wide", 19, 16, 5000, 500),
+    ("many", 13, 4, 300, 30), ("vast", 19, 16, 300, 30)])
 def test_tagging_equals_the_other_entries_and_the_oracle(gf, cases, kind, bins_log2, waves, is_, sd):
-    """Hit multiset and MAPQ-0 list of the linear entry = the 8-byte-key entry = the record stream (device and gf.tag_alignments) = the C oracle.
-    The small draft takes the 4-wave kernel; 4 x 5 Mb with 2^19 bins asked for gets a map above 32 KiB and the 16-wave kernel."""
+    """Hit multiset and MAPQ-0 list of the linear entry = the 8-byte-key entry = the record stream (device and gf.tag_alignments) = the C oracle,
+    each from the kernel the case is there for (gf_tag_kernel).  The small draft takes the 4-wave kernel; 4 x 5 Mb with 2^19 bins asked for gets
+    a map above 32 KiB and the 16-wave kernel; both maps have 64-base bins and no fine map.  many (2^13 bins: 4 096-base bins, an eighth set)
+    and vast (2^19 bins: 1 024-base bins, a sixteenth set — the form of the full-size benchmark) run the same two kernels behind a fine map:
+    the candidate queue's fine-map test, and for the records the queued form of the kernel."""
     gaps, ns, ends, recs, want, want_low = cases[kind, is_]
+    fine = kind in ("many", "vast")
     n = len(recs)
     gf.set_gaps(gaps, ns)
     gf.set_option("tag_bins_log2", bins_log2)
@@ -220,14 +231,17 @@ def test_tagging_equals_the_other_entries_and_the_oracle(gf, cases, kind, bins_l
     finally:
         gf.set_option("tag_bins_log2", 17)
     assert lin[2] == (waves, 2) and keys[2] == (waves, 1) and rec[2] == (waves, 0)
+    tail = "+fine" if fine else ""
+    assert lin[3] == "tag_kernel<%d, true, false, 2>%s" % (waves, tail) and keys[3] == "tag_kernel<%d, true, false, 1>%s" % (waves, tail)
+    assert rec[3] == "tag_kernel<%d, true, %s, 0>%s" % (waves, "true" if fine else "false", tail)
     assert len(want) > 200 and len(want_low) > 100
-    for hits, low, _ in (lin, keys, rec):
+    for hits, low, *_ in (lin, keys, rec):
         assert len(hits) == len(want) and (hits == want).all()
         assert len(low) == len(want_low) and (low == want_low).all()
     assert len(host) == len(want) and (host == want).all()
     # the edge gaps are hit from inside their own scaffold only: every hit's record lies on its gap's scaffold
     assert (recs["ref"][lin[0]["rec"]] == gaps["scaffold"][lin[0]["gap"]]).all()
-    edge = {"small": (0, 4, 5, 8), "wide": (0, 15)}[kind]
+    edge = {"small": (0, 4, 5, 8), "wide": (0, 15)}.get(kind, ())
     assert all((lin[0]["gap"] == g).any() for g in edge)
 
 
@@ -252,7 +266,7 @@ def test_a_stale_column_is_refused_and_the_call_answers_from_the_other_columns(g
         r8 = _run(gf, "lin", d_recs, n, 300, 30, d_col, bad, d_keys)
         r0 = _run(gf, "lin", d_recs, n, 300, 30, d_col, bad, None)
         assert r8[2] == (4, 1) and r0[2] == (4, 0)
-        for hits, low, _ in (r8, r0):
+        for hits, low, *_ in (r8, r0):
             assert len(hits) == len(want) and (hits == want).all() and len(low) == len(want_low) and (low == want_low).all()
     # a column built for one record less, asked about all of them
     _, d_col1, lay1, _ = _build(gf, recs, ns, n - 1)
