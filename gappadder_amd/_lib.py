@@ -35,7 +35,7 @@ assert CONTIG.itemsize == 32 and EXT_PICK.itemsize == 40 and GAP.itemsize == 16 
 GF_OK, GF_E_INVAL, GF_E_NODEV, GF_E_NOMEM, GF_E_NOSPACE, GF_E_STATE, GF_E_UNSUPPORTED, GF_E_FORMAT = 0, -1, -2, -3, -4, -5, -6, -7
 KIND_CLIP, KIND_DISCORDANT, KIND_UNMAP, KIND_LOWMAPQ = 0, 1, 2, 3
 KIND_NAMES = {KIND_CLIP: "clip", KIND_DISCORDANT: "discordant", KIND_UNMAP: "unmap"}
-KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT, KERNEL_POLISH, KERNEL_PAIRS, KERNEL_ANCHORS, KERNEL_GAPSPAN = range(16)
+KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT, KERNEL_POLISH, KERNEL_PAIRS, KERNEL_ANCHORS, KERNEL_GAPSPAN, KERNEL_POLISH_GAPPED = range(17)
 
 # words of the merge round's statistics (gf_merge_open_gaps_dev, u32[32])
 MG_N_PRE, MG_N_SETS, MG_SKIPPED, MG_N_PAIRS, MG_QC_FLAGS, MG_N_JOBS, MG_ERR, MG_N0, MG_N_EDGES, MG_SETS_WITH_JOBS = range(10)
@@ -82,6 +82,16 @@ assert FILL_POLISH.itemsize == 40
 PL_F_LONG, PL_F_NON_ACGT, PL_F_OVERFLOW = 1, 2, 4
 PL_MAX_CONTIG = 8192
 PL_GAPS, PL_MISMATCH, PL_SKIPPED_LONG, PL_SKIPPED_NON_ACGT, PL_CHANGED, PL_PLACED, PL_AMBIGUOUS, PL_BASES, PL_OVERFLOW, PL_WORDS = 0, 1, 2, 3, 4, 6, 8, 10, 12, 16
+
+# the indel-aware polish (gf_fill_polish_gapped_dev): the record — FILL_POLISH's 40 bytes, then the event counts —, its two flags, the
+# caps on distinct events and inserted bases per contig, and the statistics words beyond PL_*'s (u32[32]): u64 each accepted events,
+# inserted bases, deleted columns, rows placed split; gaps flagged EVENTS / INS_CAP
+FILL_POLISH_GAPPED = np.dtype(FILL_POLISH.descr + [(n, "<u4") for n in ("n_events", "n_inserted", "n_deleted", "reads_split", "events_seen",
+                                                                        "events_outside")])
+assert FILL_POLISH_GAPPED.itemsize == 64
+PL_F_EVENTS, PL_F_INS_CAP = 8, 16
+PLG_MAX_EVENTS, PLG_MAX_INSERTED, PLG_MAX_INDEL = 64, 64, 16
+PLG_EVENTS, PLG_INSERTED, PLG_DELETED, PLG_SPLIT, PLG_F_EVENTS, PLG_F_INS_CAP, PLG_WORDS = 16, 18, 20, 22, 24, 25, 32
 
 # the pair-span check of the closed gaps (gf_fill_pairs_dev): the record per (library, gap), its flags and the words of its statistics
 # (u32[16]): gaps examined, closed gaps whose contig does not carry the word's pick, gaps skipped for a contig too long / with a byte
@@ -269,6 +279,7 @@ def lib():
         "gf_pick_extended_gapped_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_fill_support_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
         "gf_fill_polish_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
+        "gf_fill_polish_gapped_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
         "gf_fill_pairs_dev": (i32, [vp, vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
         "gf_fill_pairs_anchored_dev": (i32, [vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, vp, vp, sz, vp, vp, sz, i32, i32, i32, i32, vp, vp, vp]),
         "gf_gap_span_dev": (i32, [vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp, vp]),

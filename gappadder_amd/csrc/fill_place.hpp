@@ -62,9 +62,10 @@ inline int pl_place_setup(const void* d_pool_packed, const void* d_nmask_or_null
 }
 
 // cnt accepted (strand, diagonal) pairs share the best key; strand and D are those of the first of them.  D is the diagonal on the array
-// of its strand: on the contig as stored for strand 0, on its reverse complement for strand 1
+// of its strand: on the contig as stored for strand 0, on its reverse complement for strand 1.  key: the best key itself, mismatches << 12
+// | (4095 - overlap), EMPTY32 without a pair (fill_place_split.hpp goes on from it)
 struct PlPlacement {
-    uint32_t cnt, strand;
+    uint32_t cnt, strand, key;
     int32_t D;
 };
 
@@ -217,6 +218,7 @@ __device__ __forceinline__ PlPlacement pl_place_row(const PlPlaceArgs& A, const 
     PlPlacement out;
     out.cnt = cnt;
     out.strand = bstrand;
+    out.key = best;
     out.D = bD;
     return out;
 }

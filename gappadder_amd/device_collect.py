@@ -118,6 +118,7 @@ def picked_names(res, kmers):
 
 SUPPORT_FIELDS = ("n_windows", "n_zero", "n_below", "min", "max", "zero_run", "sum")
 POLISH_FIELDS = ("len", "flags", "n_cols", "n_changed", "n_uncovered", "reads_placed", "reads_ambiguous")
+POLISH_INDEL_FIELDS = ("n_events", "n_inserted", "n_deleted", "reads_split", "events_seen", "events_outside")      # (with fill_polish_indels)
 
 
 def _tsv(names, header, rows_of):
@@ -134,10 +135,12 @@ def fill_support_tsv(res, kmers):
 def fill_polish_files(pipe, res, kmers):
     """(polished_seqs.fa, fill_polish.tsv) of a step with the polish round on, in gap order, one record / row per gap the device step
     closed, named as in picked_seqs.fa: the polished gap sequence (Pipeline.polished_sequences) in lines of 60, and the fields of the
-    gap's gf_fill_polish record (Results.polish) under a header line."""
+    gap's gf_fill_polish record (Results.polish) under a header line — with fill_polish_indels the six event fields of
+    gf_fill_polish_gapped as well."""
     names, seqs = picked_names(res, kmers), pipe.polished_sequences(res)
+    fields = POLISH_FIELDS + (POLISH_INDEL_FIELDS if res.polish.dtype == B.FILL_POLISH_GAPPED else ())
     fa = [">" + names[g] + "\n" + "".join(seqs[g][1][i:i + 60] + "\n" for i in range(0, len(seqs[g][1]), 60)) for g in sorted(names)]
-    return "".join(fa), _tsv(names, ("name",) + POLISH_FIELDS, lambda g, name: [[name] + [str(int(res.polish[g][f])) for f in POLISH_FIELDS]])
+    return "".join(fa), _tsv(names, ("name",) + fields, lambda g, name: [[name] + [str(int(res.polish[g][f])) for f in fields]])
 
 
 def fill_pairs_tsv(pipe, res, kmers):
@@ -542,6 +545,10 @@ class DeviceCollector:
         from . import polish as POL
         polish = round_keywords(cfg, L, "polish", "polish", ("seed", "max_mismatch", "min_overlap", "min_votes"), POL.check_params, "polish") \
             if cfg.get("fill_polish") and kk else {}
+        if polish and cfg.get("fill_polish_indels"):
+            from . import polish_gapped as PLG
+            polish = dict(round_keywords(cfg, L, "polish", "polish", ("seed", "max_mismatch", "min_overlap", "min_votes", "max_indel"),
+                                         PLG.check_params, "polish"), polish_indels=True)
         pairs = round_keywords(cfg, L, "pairs", "pair", ("seed", "max_mismatch", "min_overlap", "z"), PSP.check_params, "pair_span") \
             if cfg.get("fill_pairs") and kk else {}
         if pairs and cfg.get("fill_pairs_anchored"):

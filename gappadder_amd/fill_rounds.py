@@ -1,5 +1,5 @@
 """What the rounds that look at the closed fills after the last pick of the step share on the host (read_support.py, polish.py,
-pair_span.py, pair_anchors.py; the device side: csrc/fill_round.hpp, fill_body.hpp, fill_place.hpp): the twins' walk over a step's
+polish_gapped.py, pair_span.py, pair_anchors.py; the device side: csrc/fill_round.hpp, fill_body.hpp, fill_place.hpp, fill_place_split.hpp): the twins' walk over a step's
 Results (closed_fills, pool_reads), the placing rounds' skip classification and parameter check (skip_flag, check_placement), and the
 base of the round objects the Pipeline holds (FillRound).  A rule about closed fills exists once here and once on the device."""
 import numpy as np

@@ -59,6 +59,11 @@ def parse_configuration(path):
     # extension: consensus polish of the fills the device step closes (polish.py): {wf}polished_seqs.fa — picked_seqs.fa's cut of the
     # winning contig after the gap's own reads have voted on every column of the fill — and {wf}fill_polish.tsv, one row per closed gap
     cfg["fill_polish"] = bool(p.get("fill_polish", False))
+    # extension: with fill_polish, the indel-aware polish (polish_gapped.py): rows are placed with one indel of up to fill_polish_max_indel
+    # bases as well, polished_seqs.fa carries the result — which may differ in length — and fill_polish.tsv gains the six event columns
+    cfg["fill_polish_indels"] = bool(p.get("fill_polish_indels", False))
+    if cfg["fill_polish_indels"] and not cfg["fill_polish"]:
+        raise SystemExit("parameters.fill_polish_indels needs fill_polish: it is a mode of the polish round")
     # extension: pair-span check of the fills the device step closes (pair_span.py): {wf}fill_pairs.tsv, one row per closed gap and library
     cfg["fill_pairs"] = bool(p.get("fill_pairs", False))
     # extension: with fill_pairs, the anchored pair span (pair_anchors.py): {wf}fill_pairs_anchored.tsv, one row per closed gap and library —
@@ -67,7 +72,7 @@ def parse_configuration(path):
     if cfg["fill_pairs_anchored"] and not cfg["fill_pairs"]:
         raise SystemExit("parameters.fill_pairs_anchored needs fill_pairs: it reads the pair span's placements")
     # (name, default, lo, hi) of fill_<round>_<name>
-    for rnd, own in (("polish", (("min_votes", 2, 1, None),)), ("pairs", (("z", 3, 1, None), ("min_pairs", 8, 1, None)))):
+    for rnd, own in (("polish", (("min_votes", 2, 1, None), ("max_indel", 8, 1, 16))), ("pairs", (("z", 3, 1, None), ("min_pairs", 8, 1, None)))):
         for name, default, lo, hi in (("seed", 16, 12, 32), ("max_mismatch", 4, 0, 15), ("min_overlap", 48, 12, None)) + own:
             key = "fill_%s_%s" % (rnd, name)
             try:

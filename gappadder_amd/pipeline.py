@@ -24,6 +24,7 @@ What the reference does with files between processes —
     gf_pick_extended[_aligned|_gapped]_dev                             partial fills of the gaps every pick left open (extended_fill.py)
     gf_fill_support_dev                                        how the pool of every closed gap backs the k-mers of its fill (read_support.py)
     gf_fill_polish_dev                                         the pool of every closed gap piled up on its fill: a vote per column (polish.py)
+    gf_fill_polish_gapped_dev                                  ... with rows placed with one indel and votes on indel events (polish_gapped.py)
     gf_fill_pairs_dev                                          per library: the read pairs of every closed gap placed on its fill (pair_span.py)
     gf_gap_span_dev                                            per library, behind its tagger: the size of every gap from the pairs that span it (gap_span.py)
 
@@ -102,7 +103,8 @@ class Pipeline:
                  min_count=2, min_contig=40, anchors=(30, 15), clip_dist=250, anchor_mapq=30, k_screen=None, keep_read_ids=False,
                  key_column=True, linear_keys=True, probe_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False,
                  extended_fill=False, ext_base_cap=None, rescue_round=False, read_support=False, support_k=None, polish=False,
-                 polish_seed=16, polish_max_mismatch=4, polish_min_overlap=48, polish_min_votes=2, pair_span=False, pair_seed=16,
+                 polish_seed=16, polish_max_mismatch=4, polish_min_overlap=48, polish_min_votes=2, polish_indels=False, polish_max_indel=8,
+                 pair_span=False, pair_seed=16,
                  pair_max_mismatch=4, pair_min_overlap=48, pair_z=3, pair_anchors=False, pair_min_pairs=8, gap_span=False, span_z=3,
                  span_shift=1000, span_min_pairs=8):
         """gf: a GapFill whose gaps (and flanks, when a library is screened) are set.  k_pairs: [(k, k_velvet)] of
@@ -132,6 +134,9 @@ class Pipeline:
         polish_max_mismatch, polish_min_overlap, polish_min_votes (polish.py): last of all, the pool of every closed gap is piled up on
         its winning contig and every column of the fill takes a vote (Results.polish, .polish_bases, .polish_stats;
         polished_sequences); the step's contigs and picks stay as they are, and read_support keeps describing the UNPOLISHED fill.
+        polish_indels with polish_max_indel (polish_gapped.py; only with polish): the polish places rows with one indel of up to
+        polish_max_indel bases as well and votes on indel events, so the polished contig may change length; Results.polish then has
+        the 64-byte record gf_fill_polish_gapped and .polish_stats the event counts.
         pair_span with pair_seed, pair_max_mismatch, pair_min_overlap, pair_z (pair_span.py): after them, per library, the read pairs of
         every closed gap placed on its (unpolished) winning contig: inserts against is_mean -/+ pair_z * is_sd and the physical coverage
         of the fill (Results.pairs [n_lib, n_gaps], .pair_stats); it keeps the pools' read ids (keep_read_ids).
@@ -155,6 +160,7 @@ class Pipeline:
                          *FR.refusals("read_support", read_support, single_rank, second_round),
                          (read_support and support_k is None and k_round2 is None, "read_support needs support_k, or a k in 16..64 among k_pairs"),
                          *FR.refusals("polish", polish, single_rank, second_round),
+                         (polish_indels and not polish, "polish_indels needs polish: it is a mode of the polish round"),
                          *FR.refusals("pair_span", pair_span, single_rank, second_round),
                          (pair_anchors and not pair_span, "pair_anchors needs pair_span: it reads the pair span's placements"),
                          *FR.refusals("pair_anchors", pair_anchors, single_rank, second_round),
@@ -170,7 +176,11 @@ class Pipeline:
         self.rescue = RS.RescueRound(self) if rescue_round else None
         self.ext = EXT.ExtendedFill(self, int(ext_base_cap) if ext_base_cap is not None else None) if extended_fill else None
         self.support = SUP.ReadSupport(self, k_round2 if support_k is None else support_k) if read_support else None
-        self.polish = POL.FillPolish(self, polish_seed, polish_max_mismatch, polish_min_overlap, polish_min_votes, read_len) if polish else None
+        if polish and polish_indels:
+            from . import polish_gapped as PLG   # (here, not above: it builds on polish.py, which imports this module)
+        self.polish = (PLG.FillPolishGapped(self, polish_seed, polish_max_mismatch, polish_min_overlap, polish_min_votes, polish_max_indel, read_len)
+                       if polish and polish_indels else
+                       POL.FillPolish(self, polish_seed, polish_max_mismatch, polish_min_overlap, polish_min_votes, read_len) if polish else None)
         self.pairs = PSP.PairSpan(self, pair_seed, pair_max_mismatch, pair_min_overlap, pair_z, read_len) if pair_span else None
         self.anchored = PAN.PairAnchors(self, pair_min_pairs, read_len) if pair_anchors else None        # (launched by self.pairs, per library)
         self.after_pick = [r for r in (self.support, self.polish, self.pairs, self.anchored) if r is not None]      # (the order they run in)
@@ -919,7 +929,8 @@ class Pipeline:
     def polished_sequences(self, res):
         """picked_sequences after the polish round: {gap: (contig index, polished gap sequence, reverse?)} — the same cut, taken at the
         coordinates the UNPOLISHED contig gives (_pick_cut) and applied to the polished contig, which has the same length; the cut is
-        not searched again on the polished text."""
+        not searched again on the polished text.  With polish_indels the polished contig may differ in length: the cut is [b0, b1 + 1) of
+        the body the round located, every edit lies in [b0, b1], so the cut's end moves by the difference and its start stays."""
         from .pick_contigs import revcomp
         if res.polish is None:
             raise ValueError("polished_sequences needs the Results of a Pipeline(polish=True) step")
@@ -927,7 +938,12 @@ class Pipeline:
         for g in np.nonzero(res.best)[0]:
             ci, first, end, flip, rev = self._pick_cut(res, g)
             text = POL.polished_text(res, g)
-            if len(text) != int(res.contigs[ci]["length"]):
+            if res.polish.dtype == B.FILL_POLISH_GAPPED:
+                body = SUP.locate(res.best[g], contig_text(res, ci), self.gf.flanks[g] if self.gf.flanks is not None else None,
+                                   res.ctg_pick[ci] if res.ctg_pick is not None else None)
+                assert body is not None and first == body[0], (int(g), first, end, body)
+                end += len(text) - int(res.contigs[ci]["length"])
+            elif len(text) != int(res.contigs[ci]["length"]):
                 raise RuntimeError("gap %d: the polished contig has %d bases, the contig %d" % (g, len(text), int(res.contigs[ci]["length"])))
             out[int(g)] = (ci, revcomp(text[first:end]) if flip else text[first:end], rev)
         return out

@@ -156,6 +156,7 @@ def stats_of(words):
 
 class FillPolish(FR.FillRound):
     WHAT, RECORD = "polish", B.FILL_POLISH
+    STATS_OF = staticmethod(stats_of)            # (polish_gapped.py's round has more words)
 
     def __init__(self, pipe, seed=SEED, max_mismatch=MAX_MISMATCH, min_overlap=MIN_OVERLAP, min_votes=MIN_VOTES, read_len=None):
         super().__init__(pipe)
@@ -176,7 +177,7 @@ class FillPolish(FR.FillRound):
                                         self.d_rec.data_ptr(), self.d_bases.data_ptr(), self.base_cap, self.d_stats.data_ptr()), "gf_fill_polish_dev")
 
     def fetch(self, r):
-        r.polish_stats = stats_of(self.d_stats.cpu().numpy())
+        r.polish_stats = self.STATS_OF(self.d_stats.cpu().numpy())
         self.check_mismatches(r.polish_stats["mismatches"])
         if r.polish_stats["overflow"] or r.polish_stats["bases"] > self.base_cap:
             raise RuntimeError("polish: %d polished bases (cap %d)" % (r.polish_stats["bases"], self.base_cap))

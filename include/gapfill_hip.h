@@ -856,6 +856,53 @@ int gf_fill_polish_dev(gf_ctx* ctx, const void* d_pool_packed, const void* d_nma
                        const void* d_gap_best, const void* d_ctg_pick_or_null, int anchor_long, int anchor_short, int seed, int max_mismatch,
                        int min_overlap, int min_votes, void* d_polish, void* d_bases, size_t base_cap, void* d_stats);
 
+/* ---- indel-aware consensus polish of the closed gaps (csrc/fill_polish_gapped.hip, fill_place_split.hpp; definition and host twin:
+ * gappadder_amd/polish_gapped.py).  gf_fill_polish_dev's arguments and rules, plus max_indel (1..16, else
+ * GF_E_UNSUPPORTED): beside the gapless candidates a row has split candidates — two of its seeded diagonals at most max_indel apart, the
+ * breakpoint between a clean seed of the first and a clean seed of the second where the two parts differ from the contig least (leftmost
+ * column of the stored contig on a tie), at the cost of its mismatches plus two.  The one best candidate of a row (cost, then overlap)
+ * places it; a row placed split votes its columns and, once, its event: a deletion of contig columns [p, p + g) or an insertion of up
+ * to 16 read bases before column p, when it lies in the body.  An event with at least min_votes votes and more votes than placed rows
+ * that cross its site (p -/+ seed) in one piece without voting it passes; passing events are accepted by (votes descending, p, deletion
+ * first, length, bases) unless they touch an accepted one, insertions up to GF_PLG_MAX_INSERTED bases per contig (else
+ * GF_PL_F_INS_CAP); more than GF_PLG_MAX_EVENTS distinct events in one body: GF_PL_F_EVENTS, none applied.  The polished contig may
+ * be up to GF_PLG_MAX_INSERTED bases longer than the contig; its place in d_bases is taken from d_stats[GF_PL_BASES] once its length
+ * is known.  d_polish: gf_fill_polish_gapped per gap; d_stats: u32[GF_PLG_WORDS], gf_fill_polish_dev's words at their indices. */
+typedef struct {
+    uint64_t off;              /* the first 40 bytes: gf_fill_polish's fields with their meaning; len is the OUTPUT length */
+    uint32_t len;
+    uint32_t flags;            /* GF_PL_F_* */
+    uint32_t n_cols;
+    uint32_t n_changed;        /* substituted columns (whether or not an accepted deletion removes them) */
+    uint32_t n_uncovered;
+    uint32_t reads_placed;     /* rows placed, split ones included */
+    uint32_t reads_ambiguous;
+    uint32_t reserved;
+    uint32_t n_events;         /* events accepted */
+    uint32_t n_inserted;       /* bases they insert */
+    uint32_t n_deleted;        /* columns they delete */
+    uint32_t reads_split;      /* rows placed split */
+    uint32_t events_seen;      /* distinct in-body events (GF_PLG_MAX_EVENTS + 1 with GF_PL_F_EVENTS) */
+    uint32_t events_outside;   /* split rows whose event lies outside the body */
+} gf_fill_polish_gapped;
+#define GF_PL_F_EVENTS 8       /* more than GF_PLG_MAX_EVENTS distinct events in the body: none applied */
+#define GF_PL_F_INS_CAP 16     /* a passing insertion was dropped: more than GF_PLG_MAX_INSERTED inserted bases */
+#define GF_PLG_MAX_EVENTS 64
+#define GF_PLG_MAX_INSERTED 64
+#define GF_PLG_MAX_INDEL 16
+#define GF_PLG_EVENTS 16       /* u64: events accepted */
+#define GF_PLG_INSERTED 18     /* u64: bases inserted */
+#define GF_PLG_DELETED 20      /* u64: columns deleted */
+#define GF_PLG_SPLIT 22        /* u64: rows placed split */
+#define GF_PLG_F_EVENTS 24     /* gaps flagged GF_PL_F_EVENTS */
+#define GF_PLG_F_INS_CAP 25    /* gaps flagged GF_PL_F_INS_CAP */
+#define GF_PLG_WORDS 32
+int gf_fill_polish_gapped_dev(gf_ctx* ctx, const void* d_pool_packed, const void* d_nmask_or_null, const void* d_pool_off, size_t pool_rows,
+                              int read_len, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
+                              const void* d_gap_best, const void* d_ctg_pick_or_null, int anchor_long, int anchor_short, int seed,
+                              int max_mismatch, int min_overlap, int min_votes, int max_indel, void* d_polish, void* d_bases, size_t base_cap,
+                              void* d_stats);
+
 /* ---- pair-span check of the closed gaps (csrc/fill_pairs.hip; definition and host twin: gappadder_amd/pair_span.py).
  * One call per library, on THAT library's pool (gf_build_pools_dev: d_pool_packed, d_pool_off, d_pool_read_ids — read = 2 * pair + mate,
  * per gap ordered by (mate, pair), every read at most once per gap).  For every gap with d_gap_best != 0 the rows of the gap's slice are
@@ -1136,6 +1183,7 @@ int gf_memset_dev(gf_ctx* ctx, void* d_ptr, int value, size_t bytes);
 #define GF_KERNEL_PAIRS 13  /* pair-span check of the closed gaps */
 #define GF_KERNEL_ANCHORS 14  /* anchored pair span of the closed gaps */
 #define GF_KERNEL_GAPSPAN 15  /* gap-size measurement from the gap-spanning pairs */
+#define GF_KERNEL_POLISH_GAPPED 16  /* indel-aware consensus polish of the closed gaps */
 int gf_timing_enable(gf_ctx* ctx, int on);
 int gf_timing_read(gf_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int gf_timing_reset(gf_ctx* ctx);

@@ -108,22 +108,29 @@ def spread(ms):
     return {"ms": [round(x, 3) for x in ms], "median": round(float(np.median(ms)), 3), "min": round(min(ms), 3), "max": round(max(ms), 3)}
 
 
-def off_and_on(s, flags, on, steps, reps):
-    """The step with the round off and on (Pipeline keywords `on`): two prepared pipelines, a warm-up step each, then `reps` windows of
-    `steps` steps each, in turn.  Returns (the pipeline with the round on, {"ms_per_step_off": spread, "ms_per_step_on": spread})."""
-    pipes = {"off": s.pipeline(**flags), "on": s.pipeline(**on, **flags)}
+def in_turn(s, flags, settings, steps, reps):
+    """The step under several settings ({name: Pipeline keywords}): a prepared pipeline each, a warm-up step each, then `reps` windows of
+    `steps` steps each, in turn.  Returns ({name: pipeline}, {"ms_per_step_<name>": spread})."""
+    pipes = {name: s.pipeline(**kw, **flags) for name, kw in settings.items()}
     for pipe in pipes.values():
         pipe.prepare()
         pipe.step(1)
         pipe.barrier()
-    ms = {"off": [], "on": []}
+    ms = {name: [] for name in pipes}
     for _ in range(reps):
         for name, pipe in pipes.items():
             t0 = time.perf_counter()
             pipe.step(steps)
             pipe.barrier()
             ms[name].append((time.perf_counter() - t0) * 1e3 / steps)
-    return pipes["on"], {"ms_per_step_" + name: spread(v) for name, v in ms.items()}
+    return pipes, {"ms_per_step_" + name: spread(v) for name, v in ms.items()}
+
+
+def off_and_on(s, flags, on, steps, reps):
+    """The step with the round off and on (Pipeline keywords `on`): in_turn's protocol.  Returns (the pipeline with the round on,
+    {"ms_per_step_off": spread, "ms_per_step_on": spread})."""
+    pipes, ms = in_turn(s, flags, {"off": {}, "on": on}, steps, reps)
+    return pipes["on"], ms
 
 
 def round_ms(pipe, gf, enqueue, kernel, steps, reps=1):
