@@ -419,6 +419,34 @@ def evaluate_kat():
     print("evaluate_kat:", len(out), "cases,", sum(len(o["results"]) for o in out), "node pairs,",
           sum(1 for o in out for r in o["results"] if r[2]), "with an overlap")
 
+def evaluate_edge_kat():
+    """Known answers of the reference's own Evaluate (oracle/_ref/evaluate_kat, the recipe and record shape of evaluate_kat() above) on the
+    directed sets of tests/overlap_cases.py: every strict-mode family (limit, strips, ties, clip, params) with contigs of at most 2 100
+    bases -- for the limit and ties families the 2-kb scale models of their 8-kb cases, since the reference keeps a 16-byte-per-cell
+    table -- and every ordered node pair of each set.  The driver has no switch for Evaluate's relaxed mode, so the relax family is
+    pinned by the oracle alone (tests/test_gpu_overlap_edges.py).  -> tests/golden/evaluate_edge_kat.json.gz: sequences, parameters
+    and the reference's printed integers."""
+    subprocess.check_call(["make", "-s", "-C", os.path.join(REPO, "oracle"), "ref"])
+    exe = os.path.join(REPO, "oracle", "_ref", "evaluate_kat")
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import overlap_cases as OC
+    out = []
+    tmp = tempfile.mkdtemp(prefix="gp_eve_")
+    try:
+        for ci, (name, contigs, pr) in enumerate(OC.golden_sets()):
+            assert len(contigs) <= 5 and max(len(c) for c in contigs) <= OC.GOLDEN_MAXLEN, name
+            fa = os.path.join(tmp, "c%d.fa" % ci)
+            with open(fa, "w") as f:
+                f.write("".join(">c%d\n%s\n" % (i, s) for i, s in enumerate(contigs)))
+            lines = subprocess.check_output([exe, fa] + [repr(float(x)) for x in pr]).decode().strip().split("\n")
+            out.append({"name": name, "contigs": contigs, "params": list(pr), "results": [[int(x) for x in l.split()] for l in lines]})
+    finally:
+        shutil.rmtree(tmp, ignore_errors=True)
+    with gzip.GzipFile(os.path.join(HERE, "evaluate_edge_kat.json.gz"), "wb", mtime=0) as gzf:
+        gzf.write(json.dumps(out, sort_keys=True).encode())
+    print("evaluate_edge_kat:", len(out), "cases,", sum(len(o["results"]) for o in out), "node pairs,",
+          sum(1 for o in out for r in o["results"] if r[2]), "with an overlap")
+
 BWA_SHIM = '''#!/usr/bin/env python3
 # stand-in for `bwa index <fa>` / `bwa mem -T <score> -a <contigs.fa> <flanks.fa>`: serves the prepared SAM text <contigs.fa>.sam
 import os, sys
@@ -676,6 +704,7 @@ def main():
     kmerutils_kat()
     quickcheck_kat()
     evaluate_kat()
+    evaluate_edge_kat()
     pick_kat()
     merger_kat()
     for name, seed in (("twolib", 20260001), ("edge", 20260011), ("bounds", 20260031), ("c1", 20260001)):

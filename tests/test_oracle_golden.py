@@ -144,6 +144,53 @@ def test_overlap_evaluation_equals_the_reference():
     assert n_pairs >= 900 and n_ovl >= 100
 
 
+def test_overlap_evaluation_equals_the_reference_on_the_edge_vectors():
+    """The same comparison on tests/golden/evaluate_edge_kat.json.gz: the reference's Evaluate on the directed sets of
+    tests/overlap_cases.py at the 2-kb scale (strip lengths around 64 / 1 024 / 2 048, tied end cells, max_clip 0 .. 1 000 and
+    contigs shorter than it, a truncating mismatch score, overlaps around the class thresholds).  The file holds what the case
+    builder builds today, and the reference's answers reach the counts that keep the comparison from being vacuous."""
+    import gzip
+    from oracle import c_oracle as CO
+    import overlap_cases as OC
+    cases = json.loads(gzip.open(os.path.join(GOLDEN, "evaluate_edge_kat.json.gz"), "rt").read())
+    assert [(c["name"], c["contigs"], tuple(c["params"])) for c in cases] == OC.golden_sets()
+    n = dict.fromkeys(("res0", "res1", "res2", "nclip", "containment", "ties12", "single_base"), 0)
+    mine = OC.expected_all([dict(c, params=tuple(c["params"]), relax=False, pairs=OC.all_ordered(c["contigs"])) for c in cases])
+    for c, gots in zip(cases, mine):
+        nodes = CO.merger_nodes(c["contigs"])
+        assert [(r[0], r[1]) for r in c["results"]] == OC.all_ordered(c["contigs"])
+        for r, got in zip(c["results"], gots):
+            assert got["res"] == r[2], (c["name"], r, got)
+            if r[2]:
+                assert [got["row_end"], got["nclip"], got["overlap"], got["merged_len"], got["containment"]] == r[3:], (c["name"], r, got)
+                n["nclip"] += r[4] > 0
+                n["containment"] += r[7]
+                n["ties12"] += c["name"].startswith("ties/")
+            n["res%d" % r[2]] += 1
+            n["single_base"] += min(len(nodes[r[0]]), len(nodes[r[1]])) == 1
+    assert n["res0"] >= 20 and n["res1"] >= 5 and n["res2"] >= 20 and n["nclip"] >= 10 and n["containment"] >= 5, n
+    assert n["ties12"] >= OC.TIES_CLASS_1_2 and n["single_base"] >= 4, n
+
+
+def test_overlap_case_families_are_deterministic_and_within_budget():
+    """tests/overlap_cases.py: two builds are equal, every listed length takes part, no family lists more than twelve distinct pairs
+    of two nodes above 4 000 bases, the per-family minimum counts add up to the required totals, and the cheap strict families
+    reach theirs on the oracle's answers (the 8-kb families assert theirs where they are evaluated, in test_gpu_overlap_edges.py)."""
+    import overlap_cases as OC
+    fam = OC.families(True)
+    OC.families.cache_clear()
+    assert OC.families(True) == fam
+    lengths = {len(x) for cases in fam.values() for c in cases for x in c["contigs"]}
+    assert set(OC.LENGTHS) <= lengths
+    for name, cases in fam.items():
+        assert OC.big_pairs(cases) <= OC.BIG_PAIR_BUDGET, name
+        assert all(c["relax"] == name.startswith("relax_") for c in cases)
+    for k, v in OC.TOTALS.items():
+        assert sum(m.get(k, 0) for m in OC.MINIMUM.values()) >= v, k
+    for name in ("strips", "clip", "params"):
+        OC.check_minimum(name, fam[name], OC.expected_all(fam[name]))
+
+
 # ---- f-1: the contig picker (pick_contigs.py:64-358, 361-539), from flanks.sam on ----
 
 def test_picker_restatement_equals_the_reference_on_prepared_sam_files():
