@@ -35,7 +35,7 @@ assert CONTIG.itemsize == 32 and EXT_PICK.itemsize == 40 and GAP.itemsize == 16 
 GF_OK, GF_E_INVAL, GF_E_NODEV, GF_E_NOMEM, GF_E_NOSPACE, GF_E_STATE, GF_E_UNSUPPORTED, GF_E_FORMAT = 0, -1, -2, -3, -4, -5, -6, -7
 KIND_CLIP, KIND_DISCORDANT, KIND_UNMAP, KIND_LOWMAPQ = 0, 1, 2, 3
 KIND_NAMES = {KIND_CLIP: "clip", KIND_DISCORDANT: "discordant", KIND_UNMAP: "unmap"}
-KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT, KERNEL_POLISH, KERNEL_PAIRS, KERNEL_ANCHORS, KERNEL_GAPSPAN, KERNEL_POLISH_GAPPED = range(17)
+KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT, KERNEL_POLISH, KERNEL_PAIRS, KERNEL_ANCHORS, KERNEL_GAPSPAN, KERNEL_POLISH_GAPPED, KERNEL_PILEUP = range(18)
 
 # words of the merge round's statistics (gf_merge_open_gaps_dev, u32[32])
 MG_N_PRE, MG_N_SETS, MG_SKIPPED, MG_N_PAIRS, MG_QC_FLAGS, MG_N_JOBS, MG_ERR, MG_N0, MG_N_EDGES, MG_SETS_WITH_JOBS = range(10)
@@ -92,6 +92,19 @@ assert FILL_POLISH_GAPPED.itemsize == 64
 PL_F_EVENTS, PL_F_INS_CAP = 8, 16
 PLG_MAX_EVENTS, PLG_MAX_INSERTED, PLG_MAX_INDEL = 64, 64, 16
 PLG_EVENTS, PLG_INSERTED, PLG_DELETED, PLG_SPLIT, PLG_F_EVENTS, PLG_F_INS_CAP, PLG_WORDS = 16, 18, 20, 22, 24, 25, 32
+
+# the per-base pile-up of the closed gaps (gf_fill_pileup_dev): the record per gap (72 bytes), the track entry of a contig column (u16
+# fwd[4], rev[4]: a row of a [entries, 8] u16 array), the flags and the words of its statistics (u32[16]): gaps piled up, closed gaps whose
+# contig does not carry the word's pick, gaps skipped for a contig too long / with a byte that is no base, then u64 each: placed rows,
+# ambiguous rows, track entries handed out, low body columns; overflow
+FILL_PILEUP = np.dtype([("off", "<u8"), ("len", "<u4"), ("flags", "<u4"), ("n_cols", "<u4"), ("n_uncovered", "<u4"), ("n_thin", "<u4"),
+                        ("n_contested", "<u4"), ("n_minority", "<u4"), ("n_one_strand", "<u4"), ("low_run", "<u4"), ("low_run_col", "<u4"),
+                        ("min_depth_seen", "<u4"), ("min_depth_col", "<u4"), ("depth_sum", "<u8"), ("reads_placed", "<u4"),
+                        ("reads_ambiguous", "<u4")])
+assert FILL_PILEUP.itemsize == 72
+PU_ENTRY_BYTES = 16
+PU_F_LONG, PU_F_NON_ACGT, PU_F_OVERFLOW = 1, 2, 4
+PU_GAPS, PU_MISMATCH, PU_SKIPPED_LONG, PU_SKIPPED_NON_ACGT, PU_PLACED, PU_AMBIGUOUS, PU_ENTRIES, PU_LOW, PU_OVERFLOW, PU_WORDS = 0, 1, 2, 3, 4, 6, 8, 10, 12, 16
 
 # the pair-span check of the closed gaps (gf_fill_pairs_dev): the record per (library, gap), its flags and the words of its statistics
 # (u32[16]): gaps examined, closed gaps whose contig does not carry the word's pick, gaps skipped for a contig too long / with a byte
@@ -279,6 +292,7 @@ def lib():
         "gf_pick_extended_gapped_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_fill_support_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
         "gf_fill_polish_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
+        "gf_fill_pileup_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
         "gf_fill_polish_gapped_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
         "gf_fill_pairs_dev": (i32, [vp, vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
         "gf_fill_pairs_anchored_dev": (i32, [vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, vp, vp, sz, vp, vp, sz, i32, i32, i32, i32, vp, vp, vp]),

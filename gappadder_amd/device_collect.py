@@ -143,6 +143,35 @@ def fill_polish_files(pipe, res, kmers):
     return "".join(fa), _tsv(names, ("name",) + fields, lambda g, name: [[name] + [str(int(res.polish[g][f])) for f in fields]])
 
 
+PILEUP_FIELDS = B.FILL_PILEUP.names[1:]      # (not `off`: where a contig's entries lie in the track differs from run to run)
+
+
+def fill_pileup_files(pipe, res, kmers):
+    """The files of a step with the pile-up round on, {name: text}, in gap order, one record / row per gap the device step closed, named
+    as in picked_seqs.fa: fill_pileup.tsv (the fields of the gap's gf_fill_pileup record but `off`, under a header line); picked_seqs.fq
+    (the picked sequence with chr(33 + pileup.phred) per base); picked_seqs.masked.fa (the same sequence in lines of 60, the low columns
+    — pileup.is_low at the round's min_depth and min_agree — in lower case); and, with the plain polish, polished_seqs.fq: the polished
+    sequence, each base with ITS score from the same counters.  A contig the round skipped has no track: score 0, all lower case."""
+    from . import pileup as PU
+    names, conf = picked_names(res, kmers), pipe.fill_confidence(res)
+    md, ma = pipe.pileup.params[3:]
+    out = {"fill_pileup.tsv": _tsv(names, ("name",) + PILEUP_FIELDS, lambda g, name: [[name] + [str(int(res.pileup[g][f])) for f in PILEUP_FIELDS]])}
+    polished = pipe.polished_sequences(res) if res.polish is not None and res.polish.dtype == B.FILL_POLISH else None
+    fq, fa, pq = [], [], []
+    for g in sorted(names):
+        _, seq, entries, _ = conf[g]
+        low = PU.low_of(entries, seq, md, ma)
+        masked = "".join(c.lower() if l else c for c, l in zip(seq, low))
+        fq.append("@%s\n%s\n+\n%s\n" % (names[g], seq, PU.quality_string(entries, seq)))
+        fa.append(">" + names[g] + "\n" + "".join(masked[i:i + 60] + "\n" for i in range(0, len(masked), 60)))
+        if polished is not None:
+            pq.append("@%s\n%s\n+\n%s\n" % (names[g], polished[g][1], PU.quality_string(entries, polished[g][1])))
+    out["picked_seqs.fq"], out["picked_seqs.masked.fa"] = "".join(fq), "".join(fa)
+    if polished is not None:
+        out["polished_seqs.fq"] = "".join(pq)
+    return out
+
+
 def fill_pairs_tsv(pipe, res, kmers):
     """fill_pairs.tsv of a step with the pair-span round on: under a header line one row per gap the device step closed and library, in
     gap order and, per gap, library order: the library's index, the gap's name as in picked_seqs.fa, the fields of the gf_fill_pairs
@@ -549,6 +578,10 @@ class DeviceCollector:
             from . import polish_gapped as PLG
             polish = dict(round_keywords(cfg, L, "polish", "polish", ("seed", "max_mismatch", "min_overlap", "min_votes", "max_indel"),
                                          PLG.check_params, "polish"), polish_indels=True)
+        pileup = {}
+        if cfg.get("fill_pileup") and kk:
+            from . import pileup as PU
+            pileup = round_keywords(cfg, L, "pileup", "pileup", ("seed", "max_mismatch", "min_overlap", "min_depth", "min_agree"), PU.check_params, "pileup")
         pairs = round_keywords(cfg, L, "pairs", "pair", ("seed", "max_mismatch", "min_overlap", "z"), PSP.check_params, "pair_span") \
             if cfg.get("fill_pairs") and kk else {}
         if pairs and cfg.get("fill_pairs_anchored"):
@@ -566,7 +599,7 @@ class DeviceCollector:
                 raise SystemExit("parameters.gap_span_*: %s" % e)
         pipe = Pipeline(gf, len(gaps), L, kk, device=self.dev, anchor_mapq=self.anchor_mapq, clip_dist=self.clip_dist,
                         k_screen=k_screen or None, keep_read_ids=True, probe_column=False,
-                        read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"), **polish, **pairs, **span)
+                        read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"), **polish, **pileup, **pairs, **span)
         # (no probe column on the file path: a file-born library is screened once, and until the packing kernels write the column while
         # they hold the bases, building it is a pass of its own — 38 B read + 4 np written per read — that costs more than pass A saves)
         pipe.assemble_in_step = False
@@ -601,6 +634,8 @@ class DeviceCollector:
             files["fill_support.tsv"] = fill_support_tsv(res, cfg["kmers"])
         if res.polish is not None:
             files["polished_seqs.fa"], files["fill_polish.tsv"] = fill_polish_files(pipe, res, cfg["kmers"])
+        if res.pileup is not None:
+            files.update(fill_pileup_files(pipe, res, cfg["kmers"]))
         if res.pairs is not None:
             files["fill_pairs.tsv"] = fill_pairs_tsv(pipe, res, cfg["kmers"])
         if res.pair_anchors is not None:

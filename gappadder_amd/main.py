@@ -64,6 +64,13 @@ def parse_configuration(path):
     cfg["fill_polish_indels"] = bool(p.get("fill_polish_indels", False))
     if cfg["fill_polish_indels"] and not cfg["fill_polish"]:
         raise SystemExit("parameters.fill_polish_indels needs fill_polish: it is a mode of the polish round")
+    # extension: per-base confidence of the fills the device step closes (pileup.py): {wf}fill_pileup.tsv, one row per closed gap;
+    # {wf}picked_seqs.fq, picked_seqs.fa's sequences with a score per base from the pile-up of the gap's own reads (pileup.phred: monotone,
+    # not a calibrated probability); {wf}picked_seqs.masked.fa, the same sequences with the low columns (uncovered, thinner than
+    # fill_pileup_min_depth, or with less than fill_pileup_min_agree per cent of the votes for the base) in lower case; and, with the plain
+    # fill_polish, {wf}polished_seqs.fq, the polished base's score from the same counters.  With fill_polish_indels the polished text has
+    # other columns than the contig the reads were piled on: no polished FASTQ is written
+    cfg["fill_pileup"] = bool(p.get("fill_pileup", False))
     # extension: pair-span check of the fills the device step closes (pair_span.py): {wf}fill_pairs.tsv, one row per closed gap and library
     cfg["fill_pairs"] = bool(p.get("fill_pairs", False))
     # extension: with fill_pairs, the anchored pair span (pair_anchors.py): {wf}fill_pairs_anchored.tsv, one row per closed gap and library —
@@ -72,7 +79,8 @@ def parse_configuration(path):
     if cfg["fill_pairs_anchored"] and not cfg["fill_pairs"]:
         raise SystemExit("parameters.fill_pairs_anchored needs fill_pairs: it reads the pair span's placements")
     # (name, default, lo, hi) of fill_<round>_<name>
-    for rnd, own in (("polish", (("min_votes", 2, 1, None), ("max_indel", 8, 1, 16))), ("pairs", (("z", 3, 1, None), ("min_pairs", 8, 1, None)))):
+    for rnd, own in (("polish", (("min_votes", 2, 1, None), ("max_indel", 8, 1, 16))), ("pairs", (("z", 3, 1, None), ("min_pairs", 8, 1, None))),
+                     ("pileup", (("min_depth", 3, 1, None), ("min_agree", 80, 1, 100)))):
         for name, default, lo, hi in (("seed", 16, 12, 32), ("max_mismatch", 4, 0, 15), ("min_overlap", 48, 12, None)) + own:
             key = "fill_%s_%s" % (rnd, name)
             try:
@@ -207,7 +215,9 @@ def main_func(command, sf_config):
                     timings.pop(key, None)
         if not done:
             collect_per_scaffold(cfg, gf, sf_fai, sf_gap_pos, folders, anchor_mapq, clip_dist, wf)
-        for rnd, files in (("support", "no fill_support.tsv"), ("polish", "no polished_seqs.fa, no fill_polish.tsv"), ("pairs", "no fill_pairs.tsv")):
+        for rnd, files in (("support", "no fill_support.tsv"), ("polish", "no polished_seqs.fa, no fill_polish.tsv"), ("pairs", "no fill_pairs.tsv"),
+                           ("pileup", "no fill_pileup.tsv, no picked_seqs.fq, no picked_seqs.masked.fa" +      # (the polished FASTQ: only with the plain polish)
+                            (", no polished_seqs.fq" if cfg["fill_polish"] and not cfg["fill_polish_indels"] else ""))):
             if cfg["fill_" + rnd] and (first_round is None or getattr(first_round, rnd) is None):
                 sys.stderr.write("fill_%s: only the first assembly round of the device-resident Collect (-c All) computes it: %s\n" % (rnd, files))
         if cfg["fill_pairs_anchored"] and (first_round is None or first_round.pair_anchors is None):

@@ -25,6 +25,7 @@ What the reference does with files between processes —
     gf_fill_support_dev                                        how the pool of every closed gap backs the k-mers of its fill (read_support.py)
     gf_fill_polish_dev                                         the pool of every closed gap piled up on its fill: a vote per column (polish.py)
     gf_fill_polish_gapped_dev                                  ... with rows placed with one indel and votes on indel events (polish_gapped.py)
+    gf_fill_pileup_dev                                         the same pool piled up on the whole winning contig: eight counters per column, a record per gap (pileup.py)
     gf_fill_pairs_dev                                          per library: the read pairs of every closed gap placed on its fill (pair_span.py)
     gf_gap_span_dev                                            per library, behind its tagger: the size of every gap from the pairs that span it (gap_span.py)
 
@@ -88,7 +89,7 @@ class Results:
     the merge round and of the optional rounds are None unless the round ran."""
     merge = rescue = rescue_first = round2 = round2_first = round2_reads = extended = ext = ext_bases = support = support_stats = None
     polish = polish_bases = polish_stats = pairs = pair_stats = lib_pool_off = lib_pool_rows = lib_pool_ids = None
-    pair_anchors = pair_anchor_stats = lib_taghits = gap_span = gap_span_stats = None
+    pair_anchors = pair_anchor_stats = lib_taghits = gap_span = gap_span_stats = pileup = pileup_track = pileup_stats = None
 
 
 # anchor mode -> its pick, its pick over the contigs from an index on, its extended fill; do its picks leave a selection per contig
@@ -106,7 +107,8 @@ class Pipeline:
                  polish_seed=16, polish_max_mismatch=4, polish_min_overlap=48, polish_min_votes=2, polish_indels=False, polish_max_indel=8,
                  pair_span=False, pair_seed=16,
                  pair_max_mismatch=4, pair_min_overlap=48, pair_z=3, pair_anchors=False, pair_min_pairs=8, gap_span=False, span_z=3,
-                 span_shift=1000, span_min_pairs=8):
+                 span_shift=1000, span_min_pairs=8, pileup=False, pileup_seed=16, pileup_max_mismatch=4, pileup_min_overlap=48, pileup_min_depth=3,
+                 pileup_min_agree=80, pileup_track=True):
         """gf: a GapFill whose gaps (and flanks, when a library is screened) are set.  k_pairs: [(k, k_velvet)] of
         assemble_gaps.py:87-122.  The screen runs at the SMALLEST k of the list: a read that shares a 51-mer with a flank shares
         its 31-mers too, so this is the superset every assembly k needs (the reference recruits once, then assembles at every k).
@@ -137,6 +139,10 @@ class Pipeline:
         polish_indels with polish_max_indel (polish_gapped.py; only with polish): the polish places rows with one indel of up to
         polish_max_indel bases as well and votes on indel events, so the polished contig may change length; Results.polish then has
         the 64-byte record gf_fill_polish_gapped and .polish_stats the event counts.
+        pileup with pileup_seed, pileup_max_mismatch, pileup_min_overlap, pileup_min_depth, pileup_min_agree, pileup_track (pileup.py):
+        behind the polish, the same pool piled up on the (unpolished) winning contig once more, the eight counters (base x read strand)
+        of EVERY contig column kept in a track and the fill's weak columns summed up per gap (Results.pileup, .pileup_track [entries, 8]
+        u16, .pileup_stats; fill_confidence); pileup_track=False: the records alone, no track buffer.
         pair_span with pair_seed, pair_max_mismatch, pair_min_overlap, pair_z (pair_span.py): after them, per library, the read pairs of
         every closed gap placed on its (unpolished) winning contig: inserts against is_mean -/+ pair_z * is_sd and the physical coverage
         of the fill (Results.pairs [n_lib, n_gaps], .pair_stats); it keeps the pools' read ids (keep_read_ids).
@@ -161,6 +167,7 @@ class Pipeline:
                          (read_support and support_k is None and k_round2 is None, "read_support needs support_k, or a k in 16..64 among k_pairs"),
                          *FR.refusals("polish", polish, single_rank, second_round),
                          (polish_indels and not polish, "polish_indels needs polish: it is a mode of the polish round"),
+                         *FR.refusals("pileup", pileup, single_rank, second_round),
                          *FR.refusals("pair_span", pair_span, single_rank, second_round),
                          (pair_anchors and not pair_span, "pair_anchors needs pair_span: it reads the pair span's placements"),
                          *FR.refusals("pair_anchors", pair_anchors, single_rank, second_round),
@@ -181,9 +188,13 @@ class Pipeline:
         self.polish = (PLG.FillPolishGapped(self, polish_seed, polish_max_mismatch, polish_min_overlap, polish_min_votes, polish_max_indel, read_len)
                        if polish and polish_indels else
                        POL.FillPolish(self, polish_seed, polish_max_mismatch, polish_min_overlap, polish_min_votes, read_len) if polish else None)
+        if pileup:
+            from . import pileup as PU           # (here, not above: it builds on polish.py, which imports this module)
+        self.pileup = (PU.FillPileup(self, pileup_seed, pileup_max_mismatch, pileup_min_overlap, pileup_min_depth, pileup_min_agree, pileup_track,
+                                     read_len) if pileup else None)
         self.pairs = PSP.PairSpan(self, pair_seed, pair_max_mismatch, pair_min_overlap, pair_z, read_len) if pair_span else None
         self.anchored = PAN.PairAnchors(self, pair_min_pairs, read_len) if pair_anchors else None        # (launched by self.pairs, per library)
-        self.after_pick = [r for r in (self.support, self.polish, self.pairs, self.anchored) if r is not None]      # (the order they run in)
+        self.after_pick = [r for r in (self.support, self.polish, self.pileup, self.pairs, self.anchored) if r is not None]      # (the order they run in)
         self.gap_span = GSP.GapSpan(self, span_z, span_shift, span_min_pairs) if gap_span else None      # (launched behind every tagger pass, per library)
         self.gf, self.lib, self.h = gf, B.lib(), gf.handle
         self.n_gaps, self.L, self.kk = int(n_gaps), int(read_len), [(int(a), int(b)) for a, b in k_pairs]
@@ -946,6 +957,21 @@ class Pipeline:
             elif len(text) != int(res.contigs[ci]["length"]):
                 raise RuntimeError("gap %d: the polished contig has %d bases, the contig %d" % (g, len(text), int(res.contigs[ci]["length"])))
             out[int(g)] = (ci, revcomp(text[first:end]) if flip else text[first:end], rev)
+        return out
+
+    def fill_confidence(self, res):
+        """picked_sequences with the pile-up track of every base: {gap: (contig index, gap sequence, entries [len(sequence), 8] u16,
+        reverse?)} — the cut of _pick_cut taken from the gap's track and turned the way the sequence is written (pileup.oriented), so
+        that entry i belongs to base i.  A gap whose contig the round skipped (long, non-ACGT) has None for its entries."""
+        from . import pileup as PU
+        if res.pileup is None or res.pileup_track is None:
+            raise ValueError("fill_confidence needs the Results of a Pipeline(pileup=True) step with its track")
+        from .pick_contigs import revcomp
+        out = {}
+        for g in np.nonzero(res.best)[0]:            # (one _pick_cut per gap: text and track are cut from the same coordinates)
+            ci, first, end, flip, rev = self._pick_cut(res, g)
+            body, track = contig_text(res, ci)[first:end], PU.track_of(res, g)
+            out[int(g)] = (ci, revcomp(body) if flip else body, PU.oriented(track[first:end], flip) if track is not None else None, rev)
         return out
 
     def fixed_ms(self, steps):

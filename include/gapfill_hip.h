@@ -903,6 +903,59 @@ int gf_fill_polish_gapped_dev(gf_ctx* ctx, const void* d_pool_packed, const void
                               int max_mismatch, int min_overlap, int min_votes, int max_indel, void* d_polish, void* d_bases, size_t base_cap,
                               void* d_stats);
 
+/* ---- per-base pile-up of the closed gaps (csrc/fill_pileup.hip, fill_vote.hpp; definition and host twin: gappadder_amd/pileup.py,
+ * DESIGN.md §23).  gf_fill_polish_dev's pool, shared arguments, placement rule (seed, max_mismatch, min_overlap) and GF_PL_MISMATCH
+ * rule.  A placed row votes its unmasked bases on EVERY column of the winning contig c (as stored, n bases) it overlaps: counter
+ * fwd[b] when the row lies on c as stored, rev[b] when its reverse complement does, b the base as it reads on c.  The track entry of a
+ * column is u16 fwd[4], rev[4], each min(count, 65535); the n entries of a contig go to d_track at an offset taken from the u64
+ * counter d_stats[GF_PU_ENTRIES] (any order).  Over the body [b0, b1), with the unsaturated counts, depth = their sum, agree = fwd[cur]
+ * + rev[cur], alt = the largest fwd[b] + rev[b] over b != cur: a column is uncovered (depth 0), thin (0 < depth < min_depth), contested
+ * (depth >= min_depth and 100 * agree < min_agree * depth), minority (alt > agree), one_strand (depth >= min_depth and one strand's four
+ * counters all 0); low = uncovered, thin or contested.  low_run / low_run_col: the longest run of consecutive low body columns and its
+ * first column (body-relative, the smallest on a tie, 0 without one); min_depth_seen / min_depth_col likewise.  A contig of more than
+ * GF_PL_MAX_CONTIG bases, or with a byte other than A, C, G, T, is flagged and counted (n_cols set, everything else 0, no track).  A
+ * track that does not fit below track_cap_entries sets GF_PU_F_OVERFLOW (off = len = 0, nothing written, the summary still computed)
+ * and counts in d_stats[GF_PU_OVERFLOW].  d_track_or_null null with track_cap_entries 0: records only (off = len = 0, nothing handed
+ * out, no overflow).  min_depth >= 1, 1 <= min_agree <= 100, the placement rule as for gf_fill_polish_dev: GF_E_UNSUPPORTED otherwise.
+ * d_records: gf_fill_pileup per gap (every record is written; all zero for an open gap and a mismatch); d_stats: u32[GF_PU_WORDS]
+ * (set by the call).  The rows' placements are kept in a scratch array of the context (4 bytes per pool row).  GF_E_STATE without flanks. */
+typedef struct {
+    uint64_t off;              /* the first track entry of the contig in d_track */
+    uint32_t len;              /* its entries = the contig's bases; 0 when no track was written */
+    uint32_t flags;            /* GF_PU_F_* */
+    uint32_t n_cols;           /* body columns */
+    uint32_t n_uncovered;
+    uint32_t n_thin;
+    uint32_t n_contested;
+    uint32_t n_minority;
+    uint32_t n_one_strand;
+    uint32_t low_run;          /* the longest run of low body columns ... */
+    uint32_t low_run_col;      /* ... and its first column, body-relative */
+    uint32_t min_depth_seen;   /* the smallest depth of a body column ... */
+    uint32_t min_depth_col;    /* ... and the first column with it, body-relative */
+    uint64_t depth_sum;        /* the sum of the body columns' depths (unsaturated) */
+    uint32_t reads_placed;     /* rows placed (anywhere on the contig) */
+    uint32_t reads_ambiguous;  /* rows with more than one best placement */
+} gf_fill_pileup;              /* 72 bytes */
+#define GF_PU_F_LONG 1         /* skipped: more than GF_PL_MAX_CONTIG bases */
+#define GF_PU_F_NON_ACGT 2     /* skipped: a byte other than A, C, G, T */
+#define GF_PU_F_OVERFLOW 4     /* d_track is full: nothing was written */
+#define GF_PU_GAPS 0           /* gaps piled up (not skipped) */
+#define GF_PU_MISMATCH 1       /* closed gaps whose winning contig does not carry the word's pick */
+#define GF_PU_SKIPPED_LONG 2
+#define GF_PU_SKIPPED_NON_ACGT 3
+#define GF_PU_PLACED 4         /* u64: rows placed */
+#define GF_PU_AMBIGUOUS 6      /* u64: rows ambiguous */
+#define GF_PU_ENTRIES 8        /* u64: track entries handed out (beyond track_cap_entries: overflow) */
+#define GF_PU_LOW 10           /* u64: low body columns */
+#define GF_PU_OVERFLOW 12      /* contigs whose track did not fit */
+#define GF_PU_WORDS 16
+int gf_fill_pileup_dev(gf_ctx* ctx, const void* d_pool_packed, const void* d_nmask_or_null, const void* d_pool_off, size_t pool_rows,
+                       int read_len, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
+                       const void* d_gap_best, const void* d_ctg_pick_or_null, int anchor_long, int anchor_short, int seed, int max_mismatch,
+                       int min_overlap, int min_depth, int min_agree, void* d_records, void* d_track_or_null, size_t track_cap_entries,
+                       void* d_stats);
+
 /* ---- pair-span check of the closed gaps (csrc/fill_pairs.hip; definition and host twin: gappadder_amd/pair_span.py).
  * One call per library, on THAT library's pool (gf_build_pools_dev: d_pool_packed, d_pool_off, d_pool_read_ids — read = 2 * pair + mate,
  * per gap ordered by (mate, pair), every read at most once per gap).  For every gap with d_gap_best != 0 the rows of the gap's slice are
@@ -1184,6 +1237,7 @@ int gf_memset_dev(gf_ctx* ctx, void* d_ptr, int value, size_t bytes);
 #define GF_KERNEL_ANCHORS 14  /* anchored pair span of the closed gaps */
 #define GF_KERNEL_GAPSPAN 15  /* gap-size measurement from the gap-spanning pairs */
 #define GF_KERNEL_POLISH_GAPPED 16  /* indel-aware consensus polish of the closed gaps */
+#define GF_KERNEL_PILEUP 17  /* per-base pile-up of the closed gaps */
 int gf_timing_enable(gf_ctx* ctx, int on);
 int gf_timing_read(gf_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int gf_timing_reset(gf_ctx* ctx);
