@@ -35,7 +35,7 @@ assert CONTIG.itemsize == 32 and EXT_PICK.itemsize == 40 and GAP.itemsize == 16 
 GF_OK, GF_E_INVAL, GF_E_NODEV, GF_E_NOMEM, GF_E_NOSPACE, GF_E_STATE, GF_E_UNSUPPORTED, GF_E_FORMAT = 0, -1, -2, -3, -4, -5, -6, -7
 KIND_CLIP, KIND_DISCORDANT, KIND_UNMAP, KIND_LOWMAPQ = 0, 1, 2, 3
 KIND_NAMES = {KIND_CLIP: "clip", KIND_DISCORDANT: "discordant", KIND_UNMAP: "unmap"}
-KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT, KERNEL_POLISH, KERNEL_PAIRS, KERNEL_ANCHORS, KERNEL_GAPSPAN, KERNEL_POLISH_GAPPED, KERNEL_PILEUP = range(18)
+KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT, KERNEL_POLISH, KERNEL_PAIRS, KERNEL_ANCHORS, KERNEL_GAPSPAN, KERNEL_POLISH_GAPPED, KERNEL_PILEUP, KERNEL_JOIN = range(19)
 
 # words of the merge round's statistics (gf_merge_open_gaps_dev, u32[32])
 MG_N_PRE, MG_N_SETS, MG_SKIPPED, MG_N_PAIRS, MG_QC_FLAGS, MG_N_JOBS, MG_ERR, MG_N0, MG_N_EDGES, MG_SETS_WITH_JOBS = range(10)
@@ -128,6 +128,16 @@ FILL_ANCHORS = np.dtype([("flags", "<u4"), ("rows", "<u4"), ("n_anchored", "<u4"
 assert FILL_ANCHORS.itemsize == 112
 (PA_GAPS, PA_MISMATCH, PA_SKIPPED_LONG, PA_SKIPPED_NON_ACGT, PA_KEPT, PA_DROP_CLIPPED, PA_DROP_IN_GAP, PA_DROP_SECONDARY, PA_ABSENT,
  PA_DROP_OTHER, PA_ANCHORED, PA_PLACED, PA_PROPER, PA_IN_RANGE, PA_SPAN, PA_WORDS) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 14, 16, 18, 20
+
+# the flank-overlap joins of the open gaps (gf_pick_joins_dev): the record per gap (32 bytes, all zero: no join), its flags, the words of
+# its statistics (u32[16]) and the limits of its parameters
+FLANK_JOIN = np.dtype([("contig", "<u4"), ("left_pos", "<u4"), ("right_pos", "<u4"), ("overlap", "<u2"), ("m_left", "<u2"), ("m_right", "<u2"),
+                       ("m_flanks", "<u2"), ("n_candidates", "<u2"), ("n_accepted", "<u2"), ("o_min", "<u2"), ("o_max", "<u2"), ("level", "u1"),
+                       ("flags", "u1"), ("reserved", "<u2")])
+assert FLANK_JOIN.itemsize == 32
+FJ_F_REVERSE, FJ_F_AMBIGUOUS, FJ_F_MULTI = 1, 2, 4
+FJ_OPEN, FJ_JOINED, FJ_USABLE, FJ_CANDIDATES, FJ_FAR, FJ_SHORT_FLANK, FJ_NO_CONTEXT, FJ_MISMATCH, FJ_NO_ANCHORS, FJ_WORDS = 0, 1, 2, 3, 4, 5, 6, 7, 8, 16
+FJ_MAX_OVERLAP, FJ_MAX_CONTEXT, FJ_MAX_MISMATCH, FJ_FLANK_LIMIT = 1024, 255, 15, 65536
 
 # the gap-size measurement (gf_gap_span_dev): the record per (library, gap), its flag (n >= 1) and the words of its statistics (u32[16]):
 # u64 each: candidates, accepted, multi, clipped, lowq, low, high; then u32 gaps with n >= 1
@@ -289,6 +299,7 @@ def lib():
         "gf_round2_pools_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, vp, vp, vp, sz, vp, vp, vp, sz, vp]),
         "gf_pick_extended_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_pick_extended_aligned_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
+        "gf_pick_joins_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
         "gf_pick_extended_gapped_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_fill_support_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
         "gf_fill_polish_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),

@@ -97,13 +97,18 @@ def picked_names(res, kmers):
     """{gap: the header ContigsSelection gives the gap's sequence in picked_seqs.fa} for the gaps the device step closed: `{gap id}_{k}_{kv}_`
     + the winning contig's Velvet-style name in the gap's contigs.fa (its NODE number from assemble_gaps.first_round_order, the order
     set_first_round hands the step's contigs to the file writer in; kv as the configuration spells it)."""
-    from .assemble_gaps import first_round_order, velvet_kv
+    from .assemble_gaps import velvet_kv
     from .pipeline import decode_best
     spelled = {}
     for k, kv in kmers:
         spelled.setdefault((int(k), velvet_kv(int(kv))), int(kv))
+    return contig_names(res, {decode_best(res.best[g])[2]: int(g) for g in np.nonzero(res.best)[0]}, spelled)
+
+
+def contig_names(res, winners, spelled):
+    """picked_names for any choice of contigs: winners = {contig index: its gap}; spelled: {(k, velvet kv): kv as the configuration has it}."""
+    from .assemble_gaps import first_round_order
     ctg, out = res.contigs, {}
-    winners = {decode_best(res.best[g])[2]: int(g) for g in np.nonzero(res.best)[0]}
     last, node = None, 0
     for i in first_round_order(res):          # one pass over the list: a winner's NODE number is its place in its (gap, k, kv) group
         c = ctg[i]
@@ -221,6 +226,32 @@ def gap_span_tsv(pipe, res, gaps, kmers):
             fl = len(fills[g][1]) if g in fills else None
             cells += ["" if fl is None else str(fl), "" if fl is None or e is None else "%.2f" % (fl - e.est)]
             rows.append(cells)
+    return "".join("\t".join(c) + "\n" for c in rows)
+
+
+JOIN_FIELDS = B.FLANK_JOIN.names[:-1]          # (not the reserved word)
+JOIN_FLANK_CUT = 5                             # gnrt_pos_true_seqs.flanks leaves 5 bases between a flank and the N-run
+
+
+def flank_joins_tsv(res, gaps, kmers):
+    """flank_joins.tsv of a step with the flank-overlap joins on: under a header line one row per gap with a join (overlap > 0), in gap
+    order: the gap's key, G0 = end - start, the fields of its gf_flank_join record (Results.joins), usable (flank_joins.usable, and 0
+    where the gap starts less than 5 bases into the scaffold), the contig's name as picked_seqs.fa would spell it, and the draft
+    coordinates of the join, 0-based: cut_from = start - 5 (the end of the left flank) and resume_at = end + 5 + overlap — the joined
+    scaffold is seq[:cut_from] + seq[resume_at:] (put_gap_seq_back_to_scaffold's fifth argument)."""
+    from . import flank_joins as FJ
+    from .assemble_gaps import velvet_kv
+    joined = [int(g) for g in np.nonzero(res.joins["overlap"])[0]]
+    spelled = {}
+    for k, kv in kmers:
+        spelled.setdefault((int(k), velvet_kv(int(kv))), int(kv))
+    names = contig_names(res, {int(res.joins[g]["contig"]): g for g in joined}, spelled)
+    rows = [("gap", "G0") + JOIN_FIELDS + ("usable", "name", "cut_from", "resume_at")]
+    for g in joined:
+        rec, start, end = res.joins[g], int(gaps[g]["start"]), int(gaps[g]["end"])
+        ok = FJ.usable(rec) and start >= JOIN_FLANK_CUT
+        rows.append([res.keys[g], str(end - start)] + [str(int(rec[f])) for f in JOIN_FIELDS] +
+                    [str(int(ok)), names.get(g, res.keys[g]), str(start - JOIN_FLANK_CUT), str(end + JOIN_FLANK_CUT + int(rec["overlap"]))])
     return "".join("\t".join(c) + "\n" for c in rows)
 
 
@@ -597,9 +628,18 @@ class DeviceCollector:
                     GSP.window(is_, sd, GSP.Z, span["span_shift"])
             except ValueError as e:
                 raise SystemExit("parameters.gap_span_*: %s" % e)
+        joins = {}
+        if cfg.get("flank_joins") and kk:
+            from . import flank_joins as FJ
+            joins = dict(flank_joins=True, join_max_overlap=cfg.get("flank_joins_max_overlap", FJ.MAX_OVERLAP),
+                         join_min_context=cfg.get("flank_joins_min_context", FJ.MIN_CONTEXT), join_max_mismatch=cfg.get("flank_joins_max_mismatch", FJ.MAX_MISMATCH))
+            try:
+                FJ.check_params(joins["join_max_overlap"], joins["join_min_context"], joins["join_max_mismatch"])
+            except ValueError as e:
+                raise SystemExit("parameters.flank_joins_*: %s" % e)
         pipe = Pipeline(gf, len(gaps), L, kk, device=self.dev, anchor_mapq=self.anchor_mapq, clip_dist=self.clip_dist,
                         k_screen=k_screen or None, keep_read_ids=True, probe_column=False,
-                        read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"), **polish, **pileup, **pairs, **span)
+                        read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"), **polish, **pileup, **pairs, **span, **joins)
         # (no probe column on the file path: a file-born library is screened once, and until the packing kernels write the column while
         # they hold the bases, building it is a pass of its own — 38 B read + 4 np written per read — that costs more than pass A saves)
         pipe.assemble_in_step = False
@@ -642,6 +682,8 @@ class DeviceCollector:
             files["fill_pairs_anchored.tsv"] = fill_pairs_anchored_tsv(pipe, res, cfg["kmers"])
         if res.gap_span is not None:
             files["gap_span.tsv"] = gap_span_tsv(pipe, res, gaps, cfg["kmers"])
+        if res.joins is not None:
+            files["flank_joins.tsv"] = flank_joins_tsv(res, gaps, cfg["kmers"])
         for name, text in files.items():
             with open(cfg["wf"] + name, "w") as f:
                 f.write(text)

@@ -103,6 +103,18 @@ def parse_configuration(path):
         if isinstance(v, bool) or not isinstance(v, int) or v < lo:
             raise SystemExit("parameters.%s must be an integer, at least %d, not %r" % (key, lo, p[key]))
         cfg[key] = v
+    # extension: flank-overlap joins (flank_joins.py): the gaps the device step leaves open whose flanks OVERLAP on a contig that runs through
+    # the junction — nothing is missing there: {wf}flank_joins.tsv, one row per joined gap, which put_gap_seq_back_to_scaffold takes as its
+    # fifth argument; flank_joins_max_overlap: the longest overlap looked for; flank_joins_min_context: the bases beyond the overlap the
+    # contig and each flank must share; flank_joins_max_mismatch: the differences allowed on either side
+    cfg["flank_joins"] = bool(p.get("flank_joins", False))
+    for key, default, lo, hi in (("flank_joins_max_overlap", 256, 1, 1024), ("flank_joins_min_context", 30, 0, 255), ("flank_joins_max_mismatch", 2, 0, 15)):
+        v = p.get(key)
+        if v is None:
+            v = default
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
+            raise SystemExit("parameters.%s must be an integer in %d..%d, not %r" % (key, lo, hi, p[key]))
+        cfg[key] = v
     for path_, what in [(cfg["draft"], "draft genome")] + [(a[0], "bam") for a in cfg["alignments"]] + \
                        [(x, "raw reads") for pair in cfg["raw_reads"] for x in pair] + [(cfg["wf"], "working folder")]:
         if not os.path.exists(path_):
@@ -223,6 +235,8 @@ def main_func(command, sf_config):
         if cfg["fill_pairs_anchored"] and (first_round is None or first_round.pair_anchors is None):
             sys.stderr.write("fill_pairs_anchored: only the first assembly round of the device-resident Collect (-c All) computes it: "
                              "no fill_pairs_anchored.tsv\n")
+        if cfg["flank_joins"] and (first_round is None or first_round.joins is None):
+            sys.stderr.write("flank_joins: only the first assembly round of the device-resident Collect (-c All) computes it: no flank_joins.tsv\n")
         if cfg["gap_span"] and not done:
             sys.stderr.write("gap_span: only the device-resident Collect computes it: no gap_span.tsv\n")
         timings["stages_s"]["collect" + ("_and_first_assembly_round" if first_round is not None else "")] = time.perf_counter() - t0

@@ -21,6 +21,7 @@ What the reference does with files between processes —
       + gf_contigs_append_dev + gf_pick_*_from_dev             = round-1 rows + recruits, assembled and picked again
     gf_rescue_hq_keys_dev + gf_rescue_bridges_dev              rescue round for the gaps still open after the merge pick (rescue_round.py):
       + gf_merge_rescue_dev + gf_pick_*_from_dev               high-quality reads clipped at two contigs join the own contigs, merge, pick at 15
+    gf_pick_joins_dev                                          the open gaps whose flanks overlap on a contig that runs through the junction (flank_joins.py)
     gf_pick_extended[_aligned|_gapped]_dev                             partial fills of the gaps every pick left open (extended_fill.py)
     gf_fill_support_dev                                        how the pool of every closed gap backs the k-mers of its fill (read_support.py)
     gf_fill_polish_dev                                         the pool of every closed gap piled up on its fill: a vote per column (polish.py)
@@ -43,6 +44,7 @@ import torch
 
 from . import _lib as B
 from . import extended_fill as EXT
+from . import flank_joins as FJ
 from . import fill_rounds as FR
 from . import gap_span as GSP
 from . import pair_anchors as PAN
@@ -89,7 +91,7 @@ class Results:
     the merge round and of the optional rounds are None unless the round ran."""
     merge = rescue = rescue_first = round2 = round2_first = round2_reads = extended = ext = ext_bases = support = support_stats = None
     polish = polish_bases = polish_stats = pairs = pair_stats = lib_pool_off = lib_pool_rows = lib_pool_ids = None
-    pair_anchors = pair_anchor_stats = lib_taghits = gap_span = gap_span_stats = pileup = pileup_track = pileup_stats = None
+    pair_anchors = pair_anchor_stats = lib_taghits = gap_span = gap_span_stats = pileup = pileup_track = pileup_stats = joins = join_stats = None
 
 
 # anchor mode -> its pick, its pick over the contigs from an index on, its extended fill; do its picks leave a selection per contig
@@ -108,7 +110,7 @@ class Pipeline:
                  pair_span=False, pair_seed=16,
                  pair_max_mismatch=4, pair_min_overlap=48, pair_z=3, pair_anchors=False, pair_min_pairs=8, gap_span=False, span_z=3,
                  span_shift=1000, span_min_pairs=8, pileup=False, pileup_seed=16, pileup_max_mismatch=4, pileup_min_overlap=48, pileup_min_depth=3,
-                 pileup_min_agree=80, pileup_track=True):
+                 pileup_min_agree=80, pileup_track=True, flank_joins=False, join_max_overlap=256, join_min_context=30, join_max_mismatch=2):
         """gf: a GapFill whose gaps (and flanks, when a library is screened) are set.  k_pairs: [(k, k_velvet)] of
         assemble_gaps.py:87-122.  The screen runs at the SMALLEST k of the list: a read that shares a 51-mer with a flank shares
         its 31-mers too, so this is the superset every assembly k needs (the reference recruits once, then assembles at every k).
@@ -152,7 +154,12 @@ class Pipeline:
         gap_span with span_z, span_shift, span_min_pairs (gap_span.py): per library, behind its tagger pass and on the tagger's stream, the
         read pairs whose mates map cleanly on either side of a gap, for EVERY gap, open or closed: their number and the sums of their
         template lengths (Results.gap_span [n_lib, n_gaps], .gap_span_stats; gap_span.estimate turns a record into a gap size).  It reads the
-        libraries' records and the gap table only, so it goes with every other option, tag_ahead included; single rank."""
+        libraries' records and the gap table only, so it goes with every other option, tag_ahead included; single rank.
+        flank_joins with join_max_overlap, join_min_context, join_max_mismatch (flank_joins.py): after the last pick (behind the rescue
+        round, before the extended fill), every gap still open is looked at for a contig that carries both anchors OUT of order — the
+        flanks overlap, nothing is missing (Results.joins, gf_flank_join per gap; .join_stats; joined_gaps).  Exact anchors only; it reads
+        the step's contigs and the flanks and no pool, so it goes with second_round, merge_in_step, rescue_round and extended_fill;
+        single rank."""
         # what the options exclude, before anything touches gf or the library
         single_rank = int(world) == 1 and not force_exchange
         k_round2 = min([int(a) for a, _ in k_pairs if 16 <= int(a) <= 64], default=None)
@@ -172,6 +179,8 @@ class Pipeline:
                          (pair_anchors and not pair_span, "pair_anchors needs pair_span: it reads the pair span's placements"),
                          *FR.refusals("pair_anchors", pair_anchors, single_rank, second_round),
                          (gap_span and not single_rank, "gap_span runs on a single rank: the sums are additive over ranks, and that reduction is left out"),
+                         (flank_joins and anchor_mode in PICKS and anchor_mode != "exact", "flank_joins works with the exact anchors: not with anchor_mode %r" % (anchor_mode,)),
+                         (flank_joins and not single_rank, "flank_joins runs on a single rank"),
                          (extended_fill and not single_rank, "extended_fill runs on a single rank"),
                          (extended_fill and len(k_pairs) > B.EXT_MAX_PAIRS, "extended_fill: at most %d (k, kv) pairs" % B.EXT_MAX_PAIRS)):
             if bad:
@@ -181,6 +190,7 @@ class Pipeline:
         # the optional rounds, in the order the step runs them; None: off
         self.round2 = R2.SecondRound(self, k_round2) if second_round else None
         self.rescue = RS.RescueRound(self) if rescue_round else None
+        self.joins = FJ.FlankJoins(self, join_max_overlap, join_min_context, join_max_mismatch) if flank_joins else None
         self.ext = EXT.ExtendedFill(self, int(ext_base_cap) if ext_base_cap is not None else None) if extended_fill else None
         self.support = SUP.ReadSupport(self, k_round2 if support_k is None else support_k) if read_support else None
         if polish and polish_indels:
@@ -593,6 +603,8 @@ class Pipeline:
             self.round2.prepare()
         if self.rescue is not None:
             self.rescue.prepare()
+        if self.joins is not None:
+            self.joins.prepare()
         if self.ext is not None:        # (after the rounds: either may have grown the contig list its buffer is sized by)
             self.ext.prepare()
         for rnd in self.after_pick:     # (after the rounds: the polish's base buffer takes what the contig bases take)
@@ -721,6 +733,8 @@ class Pipeline:
             self.round2.enqueue()
         if self.rescue is not None:
             self.rescue.enqueue()
+        if self.joins is not None:
+            self.joins.enqueue()
         if self.ext is not None:
             self.ext.enqueue()
         # (neither the rescue's nor the extension's launches change d_best after the rescue's pick; every round here reads the step's
@@ -807,6 +821,8 @@ class Pipeline:
             r.merge["gaps_closed_by_merging"] = int(((r.best != 0) & (idx >= r.merge["contigs_before"]) & (idx < end)).sum())
         if self.round2 is not None:
             self.round2.fetch(r)
+        if self.joins is not None and self.kk:
+            self.joins.fetch(r)
         if self.ext is not None and self.kk:
             self.ext.fetch(r)
         for rnd in self.after_pick if self.kk else ():
@@ -842,6 +858,12 @@ class Pipeline:
                 raise RuntimeError("gap %d: the device's fill does not match its record" % g)
             out[int(g)] = d
         return out
+
+    def joined_gaps(self, res):
+        """{gap: overlap} of the usable flank-overlap joins of the last step (flank_joins.usable)."""
+        if res.joins is None:
+            raise ValueError("joined_gaps needs the Results of a Pipeline(flank_joins=True) step")
+        return {int(g): int(res.joins[g]["overlap"]) for g in np.nonzero(res.joins["overlap"])[0] if FJ.usable(res.joins[g])}
 
     def merge_open_gaps(self, res, max_set=128):
         """The reference merges a gap's contigs BEFORE it picks (assemble_gaps.py:301-306, 335-339: run_contigs_merge, then

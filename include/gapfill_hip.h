@@ -779,6 +779,54 @@ int gf_pick_extended_gapped_dev(gf_ctx* ctx, const void* d_contigs, const void* 
                                 const int* k_list, const int* kv_list, int n_k, const void* d_first, const void* d_gap_best, void* d_ext,
                                 void* d_bases, size_t base_cap, void* d_stats);
 
+/* ---- flank-overlap joins of the gaps no pick closed (csrc/pick_join.hip; definition and host twin: gappadder_amd/flank_joins.py,
+ * DESIGN.md §24).  A gap whose flanks overlap by o bases has no missing sequence: a contig that runs through the junction carries the
+ * right anchor BEFORE the end of the left one, which the pick (span >= 0) drops.  For every gap with d_gap_best == 0, every contig of it
+ * in [*d_first, min(*d_n_contigs, contig_cap)) (d_first NULL: from 0) and both strands (S = the contig, then its reverse complement):
+ * at anchor_len, and where S does not carry both anchors of that length (or the gap has none), at anchor_len_short (0: none),
+ * i = leftmost left anchor, j = rightmost right anchor; j >= i + a is the pick's case and skipped, else o = i + a - j is a candidate,
+ * rejected in this order as far (o > max_overlap), short flank (o + min_context beyond a flank), no context (j < min_context or
+ * i + a + min_context > |S|) or mismatch (more than max_mismatch differences between S and the left flank's last, or the right
+ * flank's first, o + min_context bytes); the accepted candidates of a gap compete by (longer anchor, fewer mismatches, smaller o,
+ * earlier contig, forward strand).  d_join: n_gaps gf_flank_join, written for every gap (all zero: closed, or no accepted candidate);
+ * d_stats: GF_FJ_WORDS u32, zeroed by the call.  8 <= anchor_len_short < anchor_len <= 32, 1 <= max_overlap <= 1024,
+ * 0 <= min_context <= 255, 0 <= max_mismatch <= 15: GF_E_INVAL otherwise; a flank of 65 536 bases or more: GF_E_UNSUPPORTED.  The
+ * contig list is read as every consumer reads it (contig_cap <= 2^31 - 1).  Writes nothing but d_join, d_stats and scratch of the
+ * context (24 bytes per gap; the flanks' last / first max_overlap + min_context bytes, built once per gf_set_gaps). */
+typedef struct {
+    uint32_t contig;                 /* the winner's index in the list */
+    uint32_t left_pos, right_pos;    /* i and j on the oriented strand */
+    uint16_t overlap;                /* o >= 1; 0: no join */
+    uint16_t m_left, m_right;        /* differences of S against the left / right flank over the o + min_context compared bytes */
+    uint16_t m_flanks;               /* differences between the flanks' own o overlapping bytes */
+    uint16_t n_candidates, n_accepted;   /* of the gap, over contigs and strands (saturating) */
+    uint16_t o_min, o_max;           /* over the accepted candidates */
+    uint8_t level;                   /* the winner's anchor length */
+    uint8_t flags;                   /* GF_FJ_F_* */
+    uint16_t reserved;
+} gf_flank_join;
+#define GF_FJ_F_REVERSE 1     /* the winner is the reverse strand */
+#define GF_FJ_F_AMBIGUOUS 2   /* the accepted candidates do not all have the same o */
+#define GF_FJ_F_MULTI 4       /* on the winner an anchor of its level occurs at more than one position */
+/* words of d_stats: open gaps seen, gaps joined, gaps with a usable join (joined, neither AMBIGUOUS nor MULTI), candidates, and of them
+ * far, short flank, no context, mismatch; open gaps without anchors of either length */
+#define GF_FJ_OPEN 0
+#define GF_FJ_JOINED 1
+#define GF_FJ_USABLE 2
+#define GF_FJ_CANDIDATES 3
+#define GF_FJ_FAR 4
+#define GF_FJ_SHORT_FLANK 5
+#define GF_FJ_NO_CONTEXT 6
+#define GF_FJ_MISMATCH 7
+#define GF_FJ_NO_ANCHORS 8
+#define GF_FJ_WORDS 16
+#define GF_FJ_MAX_OVERLAP 1024
+#define GF_FJ_MAX_CONTEXT 255
+#define GF_FJ_MAX_MISMATCH 15
+int gf_pick_joins_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int anchor_len,
+                      int anchor_len_short, int max_overlap, int min_context, int max_mismatch, const void* d_first, const void* d_gap_best,
+                      void* d_join, void* d_stats);
+
 /* ---- read support of the closed gaps (csrc/fill_support.hip; definition and host twin: gappadder_amd/read_support.py).
  * For every gap with d_gap_best != 0 one record that says how the k-mers of the gap's fill are backed by the gap's own pool: the
  * evaluated windows are the k-windows of the winning contig (as stored) that hold at least one base strictly between the two flank hits
@@ -1238,6 +1286,7 @@ int gf_memset_dev(gf_ctx* ctx, void* d_ptr, int value, size_t bytes);
 #define GF_KERNEL_GAPSPAN 15  /* gap-size measurement from the gap-spanning pairs */
 #define GF_KERNEL_POLISH_GAPPED 16  /* indel-aware consensus polish of the closed gaps */
 #define GF_KERNEL_PILEUP 17  /* per-base pile-up of the closed gaps */
+#define GF_KERNEL_JOIN 18  /* flank-overlap joins of the open gaps */
 int gf_timing_enable(gf_ctx* ctx, int on);
 int gf_timing_read(gf_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int gf_timing_reset(gf_ctx* ctx);
