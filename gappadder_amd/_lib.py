@@ -35,7 +35,7 @@ assert CONTIG.itemsize == 32 and EXT_PICK.itemsize == 40 and GAP.itemsize == 16 
 GF_OK, GF_E_INVAL, GF_E_NODEV, GF_E_NOMEM, GF_E_NOSPACE, GF_E_STATE, GF_E_UNSUPPORTED, GF_E_FORMAT = 0, -1, -2, -3, -4, -5, -6, -7
 KIND_CLIP, KIND_DISCORDANT, KIND_UNMAP, KIND_LOWMAPQ = 0, 1, 2, 3
 KIND_NAMES = {KIND_CLIP: "clip", KIND_DISCORDANT: "discordant", KIND_UNMAP: "unmap"}
-KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT, KERNEL_POLISH, KERNEL_PAIRS, KERNEL_ANCHORS, KERNEL_GAPSPAN, KERNEL_POLISH_GAPPED, KERNEL_PILEUP, KERNEL_JOIN = range(19)
+KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT, KERNEL_POLISH, KERNEL_PAIRS, KERNEL_ANCHORS, KERNEL_GAPSPAN, KERNEL_POLISH_GAPPED, KERNEL_PILEUP, KERNEL_JOIN, KERNEL_ALT = range(20)
 
 # words of the merge round's statistics (gf_merge_open_gaps_dev, u32[32])
 MG_N_PRE, MG_N_SETS, MG_SKIPPED, MG_N_PAIRS, MG_QC_FLAGS, MG_N_JOBS, MG_ERR, MG_N0, MG_N_EDGES, MG_SETS_WITH_JOBS = range(10)
@@ -138,6 +138,18 @@ assert FLANK_JOIN.itemsize == 32
 FJ_F_REVERSE, FJ_F_AMBIGUOUS, FJ_F_MULTI = 1, 2, 4
 FJ_OPEN, FJ_JOINED, FJ_USABLE, FJ_CANDIDATES, FJ_FAR, FJ_SHORT_FLANK, FJ_NO_CONTEXT, FJ_MISMATCH, FJ_NO_ANCHORS, FJ_WORDS = 0, 1, 2, 3, 4, 5, 6, 7, 8, 16
 FJ_MAX_OVERLAP, FJ_MAX_CONTEXT, FJ_MAX_MISMATCH, FJ_FLANK_LIMIT = 1024, 255, 15, 65536
+
+# the fill alternatives of the closed gaps (gf_fill_alts_dev): the record per gap (48 bytes, all zero: the gap is open), the record per
+# contig (8 bytes), the flags, the classes, the words of the statistics (u32[16]) and the limit of max_dist
+FILL_ALT = np.dtype([("contig", "<u4"), ("rival", "<u4"), ("fill_len", "<u4"), ("rival_len", "<u4"), ("lcp", "<u4"), ("lcs", "<u4"), ("len_min", "<u4"),
+                     ("len_max", "<u4"), ("n_candidates", "<u2"), ("n_lower", "<u2"), ("n_identical", "<u2"), ("n_near", "<u2"), ("n_far", "<u2"),
+                     ("dist", "<u2"), ("level", "u1"), ("flags", "u1"), ("reserved", "<u2")])
+FILL_ALT_CONTIG = np.dtype([("length", "<u4"), ("dist", "<u2"), ("cls", "u1"), ("strand", "u1")])
+assert FILL_ALT.itemsize == 48 and FILL_ALT_CONTIG.itemsize == 8
+FA_F_REVERSE, FA_F_RIVAL_REVERSE, FA_F_HAS_RIVAL, FA_F_LENGTH_VARIES, FA_F_OUTRANKED, FA_F_LOST = 1, 2, 4, 8, 16, 32
+FA_C_NONE, FA_C_WINNER, FA_C_IDENTICAL, FA_C_NEAR, FA_C_FAR, FA_C_LOWER = range(6)
+FA_CLOSED, FA_CONTESTED, FA_LENGTH_VARIES, FA_CANDIDATES, FA_LOWER, FA_IDENTICAL, FA_NEAR, FA_FAR, FA_OUTRANKED, FA_LOST, FA_WORDS = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 16
+FA_MAX_DIST, FA_DIST_FAR = 31, 0xFFFF
 
 # the gap-size measurement (gf_gap_span_dev): the record per (library, gap), its flag (n >= 1) and the words of its statistics (u32[16]):
 # u64 each: candidates, accepted, multi, clipped, lowq, low, high; then u32 gaps with n >= 1
@@ -300,6 +312,7 @@ def lib():
         "gf_pick_extended_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_pick_extended_aligned_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_pick_joins_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
+        "gf_fill_alts_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
         "gf_pick_extended_gapped_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_fill_support_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
         "gf_fill_polish_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),

@@ -88,4 +88,17 @@ __device__ __forceinline__ void anchor_scan(const char* s, uint32_t length, cons
     }
 }
 
+// The pick's pair of one level on one contig, from the scan's positions of that level (any / mn / mx of its four patterns), the level's
+// flags `fl` and its anchor length a: span + 1, or 0 for no pair, and the strand of the hits (pick.hip, fill_alt.hip).
+__device__ __forceinline__ uint32_t pick_span(const bool* any, const uint32_t* mn, const uint32_t* mx, uint32_t fl, uint32_t a, uint32_t* orient) {
+    // forward: leftmost left anchor, rightmost right anchor;  reverse: leftmost revcomp(right), rightmost revcomp(left) (the oriented
+    // contig is the reverse complement).  An unclipped flank's reverse hit is hidden by its forward hit.
+    const bool lf = any[ANC_LEFT], rf = any[ANC_RIGHT], lr = any[ANC_RC_LEFT] && !((fl & ANC_F_LEFT_WHOLE) && lf),
+               rr = any[ANC_RC_RIGHT] && !((fl & ANC_F_RIGHT_WHOLE) && rf);
+    *orient = 0;
+    if (lf && rf) return mx[ANC_RIGHT] >= mn[ANC_LEFT] + a ? mx[ANC_RIGHT] - (mn[ANC_LEFT] + a) + 1 : 0;
+    if (lr && rr) { *orient = 1; return mx[ANC_RC_LEFT] >= mn[ANC_RC_RIGHT] + a ? mx[ANC_RC_LEFT] - (mn[ANC_RC_RIGHT] + a) + 1 : 0; }
+    return 0;
+}
+
 }  // namespace gf

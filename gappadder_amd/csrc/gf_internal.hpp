@@ -14,7 +14,7 @@ namespace gf {
 
 constexpr uint32_t EMPTY32 = 0xFFFFFFFFu;
 constexpr int TILE_READS = 256;  // reads staged per workgroup pass of the screen filter
-constexpr int N_KERNEL_SLOTS = 19;
+constexpr int N_KERNEL_SLOTS = 20;
 
 // flank k-mer index for one k: three levels, all read-only on the device
 struct FlankIndex {
@@ -177,7 +177,7 @@ struct gf_ctx {
     size_t low_b1 = 0, low_b2 = 0;
 
     // scratch
-    gf::DevBuf cand, cand2, cand_keep, part_ws, tag_stage, verify_stage, bam_stream, bam_recs, asm_table, asm_surv, asm_nodes, asm_jump, asm_big, rowgap, pool_ws, xchg_ws, xchg_ws2, merge_ws, mx_ws, counters, stage_in, stage_out, stage_aux, table, r2_tmp, ext_ws, rs_tmp, pu_place, join_ws;
+    gf::DevBuf cand, cand2, cand_keep, part_ws, tag_stage, verify_stage, bam_stream, bam_recs, asm_table, asm_surv, asm_nodes, asm_jump, asm_big, rowgap, pool_ws, xchg_ws, xchg_ws2, merge_ws, mx_ws, counters, stage_in, stage_out, stage_aux, table, r2_tmp, ext_ws, rs_tmp, pu_place, join_ws, alt_ws;
     size_t bam_n_recs = 0;       // alignment records gf_bam_pack left in bam_recs (for gf_tag_*_bam)
     size_t bam_stream_len = 0;   // inflated BAM bytes gf_bgzf_inflate left in bam_stream
     // timing

@@ -37,17 +37,7 @@ struct PickParams {
     uint32_t* n_closed;
 };
 
-__device__ __forceinline__ uint32_t pick_span(const bool* any, const uint32_t* mn, const uint32_t* mx, uint32_t fl, uint32_t a, uint32_t* orient) {
-    // forward: leftmost left anchor, rightmost right anchor;  reverse: leftmost revcomp(right), rightmost revcomp(left) (the oriented
-    // contig is the reverse complement).  An unclipped flank's reverse hit is hidden by its forward hit.
-    const bool lf = any[ANC_LEFT], rf = any[ANC_RIGHT], lr = any[ANC_RC_LEFT] && !((fl & ANC_F_LEFT_WHOLE) && lf),
-               rr = any[ANC_RC_RIGHT] && !((fl & ANC_F_RIGHT_WHOLE) && rf);
-    *orient = 0;
-    if (lf && rf) return mx[ANC_RIGHT] >= mn[ANC_LEFT] + a ? mx[ANC_RIGHT] - (mn[ANC_LEFT] + a) + 1 : 0;
-    if (lr && rr) { *orient = 1; return mx[ANC_RC_LEFT] >= mn[ANC_RC_RIGHT] + a ? mx[ANC_RC_LEFT] - (mn[ANC_RC_RIGHT] + a) + 1 : 0; }
-    return 0;
-}
-
+// (pick_span, the span of one level from the scan's positions: anchor.hpp, shared with fill_alt.hip)
 __global__ __launch_bounds__(256) void pick_anchor_kernel(PickParams P) {
     const uint32_t n = contig_list_end(P.list);
     const uint32_t lane = threadIdx.x & 63;

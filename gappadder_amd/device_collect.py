@@ -255,6 +255,32 @@ def flank_joins_tsv(res, gaps, kmers):
     return "".join("\t".join(c) + "\n" for c in rows)
 
 
+ALT_FIELDS = B.FILL_ALT.names[:-1]             # (not the reserved word)
+
+
+def fill_alternatives_files(pipe, res, kmers):
+    """(fill_alternatives.tsv, alt_seqs.fa) of a step with the fill alternatives on.  The table: under a header line one row per closed
+    gap with more than one candidate, in gap order: the gap's key, the fields of its gf_fill_alt record (Results.alts), contested
+    (fill_alternatives.contested), the winner's name as picked_seqs.fa spells it and the rival's name spelled the same way (empty
+    without a rival).  The sequences: per contested gap, in gap order, the rival's gap sequence (Pipeline.alternative_sequences) in
+    lines of 60 under the picked name + "_alt"."""
+    from . import fill_alternatives as FA
+    from .assemble_gaps import velvet_kv
+    spelled = {}
+    for k, kv in kmers:
+        spelled.setdefault((int(k), velvet_kv(int(kv))), int(kv))
+    listed = [int(g) for g in np.nonzero(res.alts["n_candidates"] > 1)[0]]
+    rivals = [g for g in listed if FA.contested(res.alts[g])]
+    names = contig_names(res, {int(res.alts[g]["contig"]): g for g in listed}, spelled)
+    rival_names = contig_names(res, {int(res.alts[g]["rival"]): g for g in rivals}, spelled)
+    rows = [("gap",) + ALT_FIELDS + ("contested", "name", "rival_name")]
+    for g in listed:
+        rows.append([res.keys[g]] + [str(int(res.alts[g][f])) for f in ALT_FIELDS] + [str(int(FA.contested(res.alts[g]))), names.get(g, res.keys[g]), rival_names.get(g, "")])
+    seqs = pipe.alternative_sequences(res)
+    fa = [">" + names.get(g, res.keys[g]) + "_alt\n" + "".join(seqs[g][1][i:i + 60] + "\n" for i in range(0, len(seqs[g][1]), 60)) for g in rivals]
+    return "".join("\t".join(c) + "\n" for c in rows), "".join(fa)
+
+
 def round_keywords(cfg, L, rnd, prefix, names, check, switch):
     """The Pipeline keywords of an optional round of the CLI: <prefix>_<name> = cfg["fill_<rnd>_<name>"] for the names the configuration
     holds, validated against the read length by `check` (its ValueError ends the run), and <switch> = True."""
@@ -637,9 +663,17 @@ class DeviceCollector:
                 FJ.check_params(joins["join_max_overlap"], joins["join_min_context"], joins["join_max_mismatch"])
             except ValueError as e:
                 raise SystemExit("parameters.flank_joins_*: %s" % e)
+        alts = {}
+        if cfg.get("fill_alternatives") and kk:
+            from . import fill_alternatives as FA
+            alts = dict(alternatives=True, alt_max_dist=cfg.get("fill_alternatives_max_dist", FA.MAX_DIST))
+            try:
+                FA.check_params(alts["alt_max_dist"])
+            except ValueError as e:
+                raise SystemExit("parameters.fill_alternatives_max_dist: %s" % e)
         pipe = Pipeline(gf, len(gaps), L, kk, device=self.dev, anchor_mapq=self.anchor_mapq, clip_dist=self.clip_dist,
                         k_screen=k_screen or None, keep_read_ids=True, probe_column=False,
-                        read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"), **polish, **pileup, **pairs, **span, **joins)
+                        read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"), **polish, **pileup, **pairs, **span, **joins, **alts)
         # (no probe column on the file path: a file-born library is screened once, and until the packing kernels write the column while
         # they hold the bases, building it is a pass of its own — 38 B read + 4 np written per read — that costs more than pass A saves)
         pipe.assemble_in_step = False
@@ -684,6 +718,8 @@ class DeviceCollector:
             files["gap_span.tsv"] = gap_span_tsv(pipe, res, gaps, cfg["kmers"])
         if res.joins is not None:
             files["flank_joins.tsv"] = flank_joins_tsv(res, gaps, cfg["kmers"])
+        if res.alts is not None:
+            files["fill_alternatives.tsv"], files["alt_seqs.fa"] = fill_alternatives_files(pipe, res, cfg["kmers"])
         for name, text in files.items():
             with open(cfg["wf"] + name, "w") as f:
                 f.write(text)

@@ -115,6 +115,17 @@ def parse_configuration(path):
         if isinstance(v, bool) or not isinstance(v, int) or not lo <= v <= hi:
             raise SystemExit("parameters.%s must be an integer in %d..%d, not %r" % (key, lo, hi, p[key]))
         cfg[key] = v
+    # extension: fill alternatives (fill_alternatives.py): per gap the device step closes, the other contigs that carry both anchors as the
+    # winner does — identical fills, fills within fill_alternatives_max_dist edits, fills further away — and the best of the differing
+    # ones, the rival: {wf}fill_alternatives.tsv, one row per closed gap with more than one candidate, and {wf}alt_seqs.fa, the rival's
+    # gap sequence of every contested gap
+    cfg["fill_alternatives"] = bool(p.get("fill_alternatives", False))
+    v = p.get("fill_alternatives_max_dist")
+    if v is None:
+        v = 16
+    if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 31:
+        raise SystemExit("parameters.fill_alternatives_max_dist must be an integer in 1..31, not %r" % (p["fill_alternatives_max_dist"],))
+    cfg["fill_alternatives_max_dist"] = v
     for path_, what in [(cfg["draft"], "draft genome")] + [(a[0], "bam") for a in cfg["alignments"]] + \
                        [(x, "raw reads") for pair in cfg["raw_reads"] for x in pair] + [(cfg["wf"], "working folder")]:
         if not os.path.exists(path_):
@@ -237,6 +248,9 @@ def main_func(command, sf_config):
                              "no fill_pairs_anchored.tsv\n")
         if cfg["flank_joins"] and (first_round is None or first_round.joins is None):
             sys.stderr.write("flank_joins: only the first assembly round of the device-resident Collect (-c All) computes it: no flank_joins.tsv\n")
+        if cfg["fill_alternatives"] and (first_round is None or first_round.alts is None):
+            sys.stderr.write("fill_alternatives: only the first assembly round of the device-resident Collect (-c All) computes it: "
+                             "no fill_alternatives.tsv, no alt_seqs.fa\n")
         if cfg["gap_span"] and not done:
             sys.stderr.write("gap_span: only the device-resident Collect computes it: no gap_span.tsv\n")
         timings["stages_s"]["collect" + ("_and_first_assembly_round" if first_round is not None else "")] = time.perf_counter() - t0

@@ -22,6 +22,7 @@ What the reference does with files between processes —
     gf_rescue_hq_keys_dev + gf_rescue_bridges_dev              rescue round for the gaps still open after the merge pick (rescue_round.py):
       + gf_merge_rescue_dev + gf_pick_*_from_dev               high-quality reads clipped at two contigs join the own contigs, merge, pick at 15
     gf_pick_joins_dev                                          the open gaps whose flanks overlap on a contig that runs through the junction (flank_joins.py)
+    gf_fill_alts_dev                                           the closed gaps' other contigs with both anchors: identical, near or far rivals (fill_alternatives.py)
     gf_pick_extended[_aligned|_gapped]_dev                             partial fills of the gaps every pick left open (extended_fill.py)
     gf_fill_support_dev                                        how the pool of every closed gap backs the k-mers of its fill (read_support.py)
     gf_fill_polish_dev                                         the pool of every closed gap piled up on its fill: a vote per column (polish.py)
@@ -44,6 +45,7 @@ import torch
 
 from . import _lib as B
 from . import extended_fill as EXT
+from . import fill_alternatives as FA
 from . import flank_joins as FJ
 from . import fill_rounds as FR
 from . import gap_span as GSP
@@ -91,7 +93,7 @@ class Results:
     the merge round and of the optional rounds are None unless the round ran."""
     merge = rescue = rescue_first = round2 = round2_first = round2_reads = extended = ext = ext_bases = support = support_stats = None
     polish = polish_bases = polish_stats = pairs = pair_stats = lib_pool_off = lib_pool_rows = lib_pool_ids = None
-    pair_anchors = pair_anchor_stats = lib_taghits = gap_span = gap_span_stats = pileup = pileup_track = pileup_stats = joins = join_stats = None
+    pair_anchors = pair_anchor_stats = lib_taghits = gap_span = gap_span_stats = pileup = pileup_track = pileup_stats = joins = join_stats = alts = alt_contigs = alt_stats = None
 
 
 # anchor mode -> its pick, its pick over the contigs from an index on, its extended fill; do its picks leave a selection per contig
@@ -110,7 +112,8 @@ class Pipeline:
                  pair_span=False, pair_seed=16,
                  pair_max_mismatch=4, pair_min_overlap=48, pair_z=3, pair_anchors=False, pair_min_pairs=8, gap_span=False, span_z=3,
                  span_shift=1000, span_min_pairs=8, pileup=False, pileup_seed=16, pileup_max_mismatch=4, pileup_min_overlap=48, pileup_min_depth=3,
-                 pileup_min_agree=80, pileup_track=True, flank_joins=False, join_max_overlap=256, join_min_context=30, join_max_mismatch=2):
+                 pileup_min_agree=80, pileup_track=True, flank_joins=False, join_max_overlap=256, join_min_context=30, join_max_mismatch=2,
+                 alternatives=False, alt_max_dist=16):
         """gf: a GapFill whose gaps (and flanks, when a library is screened) are set.  k_pairs: [(k, k_velvet)] of
         assemble_gaps.py:87-122.  The screen runs at the SMALLEST k of the list: a read that shares a 51-mer with a flank shares
         its 31-mers too, so this is the superset every assembly k needs (the reference recruits once, then assembles at every k).
@@ -159,7 +162,13 @@ class Pipeline:
         round, before the extended fill), every gap still open is looked at for a contig that carries both anchors OUT of order — the
         flanks overlap, nothing is missing (Results.joins, gf_flank_join per gap; .join_stats; joined_gaps).  Exact anchors only; it reads
         the step's contigs and the flanks and no pool, so it goes with second_round, merge_in_step, rescue_round and extended_fill;
-        single rank."""
+        single rank.
+        alternatives with alt_max_dist (fill_alternatives.py): after the last pick, beside the joins, every CLOSED gap's contigs are
+        looked at again: those that carry both anchors as the winner does are classed by their fill — the winner's byte for byte,
+        within alt_max_dist edits of it, or further away — and the best of the differing ones is the gap's rival (Results.alts,
+        gf_fill_alt per gap; .alt_contigs, gf_fill_alt_contig per contig; .alt_stats; alternative_sequences).  Exact anchors only; it
+        reads the step's contigs, the flanks and the pick words, so it goes with second_round, merge_in_step, rescue_round,
+        extended_fill and flank_joins; single rank."""
         # what the options exclude, before anything touches gf or the library
         single_rank = int(world) == 1 and not force_exchange
         k_round2 = min([int(a) for a, _ in k_pairs if 16 <= int(a) <= 64], default=None)
@@ -181,6 +190,8 @@ class Pipeline:
                          (gap_span and not single_rank, "gap_span runs on a single rank: the sums are additive over ranks, and that reduction is left out"),
                          (flank_joins and anchor_mode in PICKS and anchor_mode != "exact", "flank_joins works with the exact anchors: not with anchor_mode %r" % (anchor_mode,)),
                          (flank_joins and not single_rank, "flank_joins runs on a single rank"),
+                         (alternatives and anchor_mode in PICKS and anchor_mode != "exact", "alternatives works with the exact anchors: not with anchor_mode %r" % (anchor_mode,)),
+                         (alternatives and not single_rank, "alternatives runs on a single rank"),
                          (extended_fill and not single_rank, "extended_fill runs on a single rank"),
                          (extended_fill and len(k_pairs) > B.EXT_MAX_PAIRS, "extended_fill: at most %d (k, kv) pairs" % B.EXT_MAX_PAIRS)):
             if bad:
@@ -191,6 +202,7 @@ class Pipeline:
         self.round2 = R2.SecondRound(self, k_round2) if second_round else None
         self.rescue = RS.RescueRound(self) if rescue_round else None
         self.joins = FJ.FlankJoins(self, join_max_overlap, join_min_context, join_max_mismatch) if flank_joins else None
+        self.alts = FA.FillAlternatives(self, alt_max_dist) if alternatives else None
         self.ext = EXT.ExtendedFill(self, int(ext_base_cap) if ext_base_cap is not None else None) if extended_fill else None
         self.support = SUP.ReadSupport(self, k_round2 if support_k is None else support_k) if read_support else None
         if polish and polish_indels:
@@ -605,6 +617,8 @@ class Pipeline:
             self.rescue.prepare()
         if self.joins is not None:
             self.joins.prepare()
+        if self.alts is not None:
+            self.alts.prepare()
         if self.ext is not None:        # (after the rounds: either may have grown the contig list its buffer is sized by)
             self.ext.prepare()
         for rnd in self.after_pick:     # (after the rounds: the polish's base buffer takes what the contig bases take)
@@ -735,6 +749,8 @@ class Pipeline:
             self.rescue.enqueue()
         if self.joins is not None:
             self.joins.enqueue()
+        if self.alts is not None:
+            self.alts.enqueue()
         if self.ext is not None:
             self.ext.enqueue()
         # (neither the rescue's nor the extension's launches change d_best after the rescue's pick; every round here reads the step's
@@ -823,6 +839,8 @@ class Pipeline:
             self.round2.fetch(r)
         if self.joins is not None and self.kk:
             self.joins.fetch(r)
+        if self.alts is not None and self.kk:
+            self.alts.fetch(r)
         if self.ext is not None and self.kk:
             self.ext.fetch(r)
         for rnd in self.after_pick if self.kk else ():
@@ -864,6 +882,20 @@ class Pipeline:
         if res.joins is None:
             raise ValueError("joined_gaps needs the Results of a Pipeline(flank_joins=True) step")
         return {int(g): int(res.joins[g]["overlap"]) for g in np.nonzero(res.joins["overlap"])[0] if FJ.usable(res.joins[g])}
+
+    def alternative_sequences(self, res):
+        """{gap: (rival contig index, the rival's gap sequence, reverse?)} of the contested gaps of the last step (fill_alternatives.contested):
+        the rival's sequence cut as picked_sequences cuts the winner's (_contig_cut)."""
+        from .pick_contigs import revcomp
+        if res.alts is None:
+            raise ValueError("alternative_sequences needs the Results of a Pipeline(alternatives=True) step")
+        out = {}
+        for g in np.nonzero(res.alts["flags"] & B.FA_F_HAS_RIVAL)[0]:
+            rec = res.alts[g]
+            ci, first, end, flip, rev = Pipeline._contig_cut(self, res, g, int(rec["rival"]), int(rec["level"]), bool(int(rec["flags"]) & B.FA_F_RIVAL_REVERSE))
+            body = contig_text(res, ci)[first:end]
+            out[int(g)] = (ci, revcomp(body) if flip else body, rev)
+        return out
 
     def merge_open_gaps(self, res, max_set=128):
         """The reference merges a gap's contigs BEFORE it picks (assemble_gaps.py:301-306, 335-339: run_contigs_merge, then
@@ -931,8 +963,12 @@ class Pipeline:
         contig as stored: contig[first:end], reverse-complemented for a reverse selection, is what ContigsSelection writes (pick_contigs.py:341-349).  "align" and "gapped": from
         the contig's selection in res.ctg_pick; "exact": the host picker's selection (pick_contigs.select_full over the exact anchors' hits)
         on the winning contig alone, at the word's anchor length, with the flanks given to gf_set_gaps."""
-        from .pick_contigs import select_full, stand_in_hits
         a_len, span1, ci, rev = decode_best(res.best[g])
+        return Pipeline._contig_cut(self, res, g, ci, a_len, rev)      # (by the class: a stand-in for `self` needs its .gf alone)
+
+    def _contig_cut(self, res, g, ci, a_len, rev):
+        """_pick_cut's rule for any contig ci of gap g with a selection at anchor length a_len on strand rev (the winner; a rival)."""
+        from .pick_contigs import select_full, stand_in_hits
         if res.ctg_pick is not None:
             p = res.ctg_pick[ci]
             lp, rp, lm, rm = int(p["lp"]), int(p["rp"]), int(p["lm"]), int(p["rm"])

@@ -827,6 +827,73 @@ int gf_pick_joins_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contig
                       int anchor_len_short, int max_overlap, int min_context, int max_mismatch, const void* d_first, const void* d_gap_best,
                       void* d_join, void* d_stats);
 
+/* ---- fill alternatives of the closed gaps (csrc/fill_alt.hip; definition and host twin: gappadder_amd/fill_alternatives.py).
+ * The pick keeps one contig per gap (level, then span, then the earlier contig) and drops every other contig that carries both anchors.
+ * For every gap with d_gap_best != 0 this round looks at them again.  A CANDIDATE is a contig of the gap in
+ * [*d_first, min(*d_n_contigs, contig_cap)) (d_first NULL: from 0) to which gf_pick_anchored2_dev's own rule gives a non-zero word: its
+ * level, span and strand.  The WINNER is the contig the gap's word names, re-located by its index (whatever *d_first is); when that
+ * contig is no contig of the gap, or no candidate of the word's level, strand and span, the gap is LOST: its record holds the level and
+ * GF_FA_F_LOST, its contigs are not looked at.  The oriented fill of a candidate is the span bytes between its anchors on the strand of
+ * its hits (the reverse strand: the reverse complement, A<->T, C<->G, every other byte as it is).  A candidate below the winner's level is
+ * LOWER (counted); one above it sets GF_FA_F_OUTRANKED and is counted as a candidate only; one of the winner's level is a PEER (and sets
+ * GF_FA_F_OUTRANKED when its word is greater than the gap's): IDENTICAL (the winner's fill byte for byte), NEAR (Levenshtein distance
+ * to the winner's fill <= max_dist, unit costs) or FAR.  The RIVAL is the NEAR or FAR peer with the largest word.  d_alt: n_gaps
+ * gf_fill_alt, written for every gap (all zero: the gap is open); d_alt_contig: NULL, or contig_cap gf_fill_alt_contig, written for
+ * every index in [0, min(*d_n_contigs, contig_cap)) (all zero: no candidate, or above the winner's level); d_stats: GF_FA_WORDS u32,
+ * zeroed by the call.  8 <= anchor_len_short < anchor_len <= 32 (or anchor_len_short 0), 1 <= max_dist <= GF_FA_MAX_DIST: GF_E_INVAL
+ * otherwise.  The contig list is read as every consumer reads it (contig_cap <= 2^31 - 1).  Writes nothing but d_alt, d_alt_contig,
+ * d_stats and scratch of the context (48 bytes per gap). */
+typedef struct {
+    uint32_t contig;                 /* the winner's index in the list */
+    uint32_t rival;                  /* the rival's index; 0 without GF_FA_F_HAS_RIVAL */
+    uint32_t fill_len, rival_len;    /* bytes of the winner's and the rival's oriented fill */
+    uint32_t lcp;                    /* longest common prefix of the two fills */
+    uint32_t lcs;                    /* longest common suffix of what follows the prefix: the fills differ in [lcp, len - lcs) */
+    uint32_t len_min, len_max;       /* fill lengths over the winner and its peers */
+    uint16_t n_candidates;           /* all candidates, the winner included (this and the next four saturate at 65 535) */
+    uint16_t n_lower, n_identical, n_near, n_far;
+    uint16_t dist;                   /* the rival's distance; GF_FA_DIST_FAR for a FAR rival */
+    uint8_t level;                   /* the winner's anchor length */
+    uint8_t flags;                   /* GF_FA_F_* */
+    uint16_t reserved;
+} gf_fill_alt;
+typedef struct {
+    uint32_t length;                 /* bytes of the candidate's fill */
+    uint16_t dist;                   /* the distance of a NEAR peer, else GF_FA_DIST_FAR */
+    uint8_t cls;                     /* GF_FA_C_* */
+    uint8_t strand;                  /* the strand of the candidate's hits */
+} gf_fill_alt_contig;
+#define GF_FA_F_REVERSE 1         /* the winner's hits are on the reverse strand */
+#define GF_FA_F_RIVAL_REVERSE 2
+#define GF_FA_F_HAS_RIVAL 4       /* the gap is contested */
+#define GF_FA_F_LENGTH_VARIES 8   /* len_min != len_max */
+#define GF_FA_F_OUTRANKED 16      /* a candidate's word is greater than the gap's */
+#define GF_FA_F_LOST 32           /* the gap's word does not lead back to a candidate */
+#define GF_FA_C_NONE 0
+#define GF_FA_C_WINNER 1
+#define GF_FA_C_IDENTICAL 2
+#define GF_FA_C_NEAR 3
+#define GF_FA_C_FAR 4
+#define GF_FA_C_LOWER 5
+/* words of d_stats: closed gaps seen, contested gaps, gaps with LENGTH_VARIES, candidates, and of them lower, identical, near, far;
+ * outranked gaps, lost gaps */
+#define GF_FA_CLOSED 0
+#define GF_FA_CONTESTED 1
+#define GF_FA_LENGTH_VARIES 2
+#define GF_FA_CANDIDATES 3
+#define GF_FA_LOWER 4
+#define GF_FA_IDENTICAL 5
+#define GF_FA_NEAR 6
+#define GF_FA_FAR 7
+#define GF_FA_OUTRANKED 8
+#define GF_FA_LOST 9
+#define GF_FA_WORDS 16
+#define GF_FA_MAX_DIST 31
+#define GF_FA_DIST_FAR 0xFFFF
+int gf_fill_alts_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq, int anchor_len,
+                     int anchor_len_short, int max_dist, const void* d_first, const void* d_gap_best, void* d_alt, void* d_alt_contig,
+                     void* d_stats);
+
 /* ---- read support of the closed gaps (csrc/fill_support.hip; definition and host twin: gappadder_amd/read_support.py).
  * For every gap with d_gap_best != 0 one record that says how the k-mers of the gap's fill are backed by the gap's own pool: the
  * evaluated windows are the k-windows of the winning contig (as stored) that hold at least one base strictly between the two flank hits
@@ -1287,6 +1354,7 @@ int gf_memset_dev(gf_ctx* ctx, void* d_ptr, int value, size_t bytes);
 #define GF_KERNEL_POLISH_GAPPED 16  /* indel-aware consensus polish of the closed gaps */
 #define GF_KERNEL_PILEUP 17  /* per-base pile-up of the closed gaps */
 #define GF_KERNEL_JOIN 18  /* flank-overlap joins of the open gaps */
+#define GF_KERNEL_ALT 19  /* fill alternatives of the closed gaps */
 int gf_timing_enable(gf_ctx* ctx, int on);
 int gf_timing_read(gf_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int gf_timing_reset(gf_ctx* ctx);
