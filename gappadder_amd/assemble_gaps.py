@@ -284,13 +284,15 @@ def bridging_reads_batch(items, seed_len=30, budget=2):
 
 class GapAssembler:
     def __init__(self, sf_fai, sf_pos, n_jobs, working_space, kmer_list=None, gf=None, bam_list=None, samtools_path=None, flank_anchor="exact",
-                 contig_merger="host"):
+                 contig_merger="host", recruit_rounds=1):
         """flank_anchor: how every ContigsSelection round anchors the flanks on the contigs, "exact", "align" or "gapped" (pick_contigs.py);
-        contig_merger: the engine of every contig-merge round, "host" or "device" (MergeContigs.merge_contigs)."""
+        contig_merger: the engine of every contig-merge round, "host" or "device" (MergeContigs.merge_contigs); recruit_rounds: how
+        often the second round's recruitment of both-unmapped pairs is repeated at the most (assemble_pipeline)."""
         global kmer_len_list, working_folder, _gf
         self.bam_list = list(bam_list or [])
         self.flank_anchor = flank_anchor
         self.contig_merger = contig_merger
+        self.recruit_rounds = int(recruit_rounds)
         self.samtools_path = samtools_path
         if kmer_list is not None:
             kmer_len_list = list(kmer_list)
@@ -374,7 +376,9 @@ class GapAssembler:
     def assemble_pipeline(self):
         """The reference's rounds (assemble_gaps.py:328-368): assemble + merge; pick the gaps whose contigs are anchored by both
         flanks (anchor length 30 = the reference's first bwa_min_score); for the gaps still open recruit the both-unmapped pairs that
-        share k-mers with their contigs and assemble again (:344-351), pick; merge those that are still open, pick (:353-356); bring
+        share k-mers with their contigs and assemble again (:344-351), pick — recruit_rounds times at the most, each further round with
+        the contigs the round before left, only the pairs a gap does not have yet, until a round appends nothing; merge those that are
+        still open, pick (:353-356); bring
         in the high-quality reads that bridge two contigs and merge once more (:358-361); pick at 15 (:364-366); what is still open
         gets the extended (partial, 'NN'-joined) fill (:367-368)."""
         from .pick_contigs import ContigsSelection
@@ -385,16 +389,26 @@ class GapAssembler:
         cs = ContigsSelection(working_folder, self.flank_anchor)
         closed = cs.pick_full_constructed_contigs(30, fa_list, sf_picked)
         remain = self.pick_already_constructed(cs, fa_list, sf_picked)
-        recruited = 0
+        recruited, rounds_run, burc, grown = 0, 0, None, {}
         if self.bam_list and self.samtools_path and remain:
             from .collect_both_unmapped_reads import BothUnmappedReadsCollector
             ks = [int(k) for k, _ in kmer_len_list if 16 <= int(k) <= 64]
             burc = BothUnmappedReadsCollector(working_folder, self.samtools_path, _ctx(), min(ks) if ks else 31)
-            burc.collect_both_unmapped_reads(self.bam_list, remain)
+            grown = burc.collect_both_unmapped_reads(self.bam_list, remain)
+            rounds_run = 1
             recruited = sum(1 for key in remain if os.path.exists("%sunmapped_reads/%s.fastq" % (working_folder, key)))
         self.assembly_given_list(remain)                                     # second-round assembly (:349-351)
         closed += cs.pick_full_constructed_contigs(30, remain, sf_picked)
         remain = self.pick_already_constructed(cs, remain, sf_picked)
+        while burc is not None and grown and rounds_run < self.recruit_rounds:          # further recruitment rounds on what is still open
+            rounds_run += 1
+            grown = burc.align_unmapped_to_contigs(remain)
+            if not grown:
+                break
+            again = [key for key in remain if key in grown]       # (a gap whose read file did not change keeps its contigs and its pick)
+            self.assembly_given_list(again)
+            closed += cs.pick_full_constructed_contigs(30, again, sf_picked)
+            remain = self.pick_already_constructed(cs, remain, sf_picked)
         merged += sum(1 for v in self.run_contigs_merge(remain).values() if v)             # second-round merging (:353-356)
         closed += cs.pick_full_constructed_contigs(30, remain, sf_picked)
         remain = self.pick_already_constructed(cs, remain, sf_picked)
@@ -403,5 +417,5 @@ class GapAssembler:
         closed += cs.pick_full_constructed_contigs(15, remain, sf_picked)    # (:364-366)
         remain = self.pick_already_constructed(cs, remain, sf_picked)
         extended = cs.pick_extended_contigs(15, remain, sf_picked)           # partial fills, left + 'NN' + right (:367-368)
-        return {"gaps": len(fa_list), "closed": closed, "extended": extended, "second_round_gaps": recruited,
+        return {"gaps": len(fa_list), "closed": closed, "extended": extended, "second_round_gaps": recruited, "recruit_rounds_run": rounds_run,
                 "gaps_with_merged_contigs": merged, "bridging_reads": bridges}

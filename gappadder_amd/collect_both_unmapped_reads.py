@@ -101,6 +101,7 @@ class BothUnmappedReadsCollector:
         self.samtools_path = samtools_path
         self.gf = gf
         self.k = int(k)
+        self.appended = {}      # gap key -> indices (into the record list) of the records its gap_reads file got, over the rounds
 
     def collect_both_unmapped_reads(self, bam_list, id_list):
         wf = self.wf
@@ -133,9 +134,12 @@ class BothUnmappedReadsCollector:
                         left, right = [], []
             f_left.write("".join(left))
             f_right.write("".join(right))
-        self.align_unmapped_to_contigs(id_list)
+        return self.align_unmapped_to_contigs(id_list)
 
     def align_unmapped_to_contigs(self, fa_list):
+        """One recruitment round over the records collect_both_unmapped_reads() read: -> {gap key: names of the records appended}.
+        Called again (a further round, on the contigs the gaps have by then) it appends only the records a gap did not get before and
+        rewrites the gap's unmapped_reads file with all of them, in record order."""
         wf = self.wf
         keys, contigs = [], []
         with open(wf + "gap_contigs_all.fa", "w") as fout:
@@ -156,14 +160,19 @@ class BothUnmappedReadsCollector:
         seqs = [self.reads[n].split("\n", 1)[0] for n in names]
         picked = kmer_recruit_unmapped(gf, contigs, names, seqs, self.k)
         os.makedirs(wf + "unmapped_reads", exist_ok=True)
+
+        def rec(ids):
+            return "".join("@" + names[i] + "\n" + self.reads[names[i]] for i in ids)
         out = {}
         for key, idx in zip(keys, picked):
-            if not idx:
+            have = self.appended.setdefault(key, set())
+            new = [i for i in idx if i not in have]
+            if not new:
                 continue
-            text = "".join("@" + names[i] + "\n" + self.reads[names[i]] for i in idx)
+            have.update(new)
             with open(wf + "gap_reads/%s.fastq" % key, "a") as f:                          # :113-117
-                f.write(text)
+                f.write(rec(new))
             with open(wf + "unmapped_reads/%s.fastq" % key, "w") as f:                     # :119-123
-                f.write(text)
-            out[key] = [names[i] for i in idx]
+                f.write(rec(sorted(have)))
+            out[key] = [names[i] for i in new]
         return out

@@ -126,6 +126,14 @@ def parse_configuration(path):
     if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 31:
         raise SystemExit("parameters.fill_alternatives_max_dist must be an integer in 1..31, not %r" % (p["fill_alternatives_max_dist"],))
     cfg["fill_alternatives_max_dist"] = v
+    # extension: recruitment rounds (assemble_gaps.assemble_pipeline): how often the second round — both-unmapped pairs recruited by the
+    # open gaps' contigs, assembly, pick — is repeated with the contigs the round before built; 1: the reference's single round
+    v = p.get("recruit_rounds")
+    if v is None:
+        v = 1
+    if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 16:
+        raise SystemExit("parameters.recruit_rounds must be an integer in 1..16, not %r" % (p["recruit_rounds"],))
+    cfg["recruit_rounds"] = v
     for path_, what in [(cfg["draft"], "draft genome")] + [(a[0], "bam") for a in cfg["alignments"]] + \
                        [(x, "raw reads") for pair in cfg["raw_reads"] for x in pair] + [(cfg["wf"], "working folder")]:
         if not os.path.exists(path_):
@@ -260,13 +268,13 @@ def main_func(command, sf_config):
             os.makedirs(wf + MERGE_FOLDER + s, exist_ok=True)
         ga = assemble_gaps.GapAssembler(sf_fai, sf_gap_pos, cfg["nthreads"], wf + MERGE_FOLDER, cfg["kmers"], gf,
                                         bam_list=[bam for bam, _, _ in cfg["alignments"]], samtools_path=cfg["samtools"],
-                                        flank_anchor=cfg["flank_anchor"], contig_merger=cfg["contig_merger"])
+                                        flank_anchor=cfg["flank_anchor"], contig_merger=cfg["contig_merger"], recruit_rounds=cfg["recruit_rounds"])
         if first_round is not None:
             assemble_gaps.set_first_round(first_round)
         res = ga.assemble_pipeline()
         print("assembled %d gaps, %d closed (picked_seqs.fa), %d with an extended (partial) fill, %d gaps got both-unmapped pairs in the "
-              "second round, contigs merged in %d gap rounds (%d bridging high-quality reads); contigs in %svelvet_temp/*/contigs.fa"
-              % (res["gaps"], res["closed"], res.get("extended", 0), res["second_round_gaps"], res["gaps_with_merged_contigs"],
+              "second round (%d recruitment rounds run), contigs merged in %d gap rounds (%d bridging high-quality reads); contigs in %svelvet_temp/*/contigs.fa"
+              % (res["gaps"], res["closed"], res.get("extended", 0), res["second_round_gaps"], res["recruit_rounds_run"], res["gaps_with_merged_contigs"],
                  res["bridging_reads"], wf + MERGE_FOLDER))
         timings["stages_s"]["assembly_rounds"] = time.perf_counter() - t0
         timings["assembly"] = res
