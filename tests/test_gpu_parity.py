@@ -244,7 +244,7 @@ def test_synthetic_generator_matches_oracle_bit_for_bit(gf):
 
 @pytest.mark.parametrize("n_big", [16385, 40000, 150001])
 def test_device_pools_keep_gaps_with_more_keys_than_the_lds_sort_holds(gf, n_big):
-    """A gap whose flank sits in a repeat recruits far more reads than the 16 384 keys one LDS sort holds (the reference has no
+    """A gap whose flank sits in a repeat recruits far more reads than the 4 096 keys one LDS sort holds (the reference has no
     bound: run_multi_threads_discordant.py:209-241 flushes any number of records).  Such a gap is sorted in place in global memory
     — same pools as numpy's sort + unique, no error flag, the neighbours untouched."""
     import torch

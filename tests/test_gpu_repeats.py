@@ -86,7 +86,7 @@ def test_screen_and_tagger_on_repeats_equal_the_oracle(gf, work):
 
 def test_deep_pools_are_built_and_assembled_without_loss(gf, work):
     """Device pipeline on the repeat workload: keys (screen hits + mates, tagger hits) -> pools -> assembly.  The class-0 gaps'
-    key lists exceed the 16 384 keys of one LDS sort and their pools the 2 000-row slices given to the assembly's main launch."""
+    key lists exceed the 4 096 keys of one LDS sort and their pools the 2 000-row slices given to the assembly's main launch."""
     import torch
     from gappadder_amd import _lib as B
     lib = B.lib()
