@@ -35,7 +35,7 @@ assert CONTIG.itemsize == 32 and EXT_PICK.itemsize == 40 and GAP.itemsize == 16 
 GF_OK, GF_E_INVAL, GF_E_NODEV, GF_E_NOMEM, GF_E_NOSPACE, GF_E_STATE, GF_E_UNSUPPORTED, GF_E_FORMAT = 0, -1, -2, -3, -4, -5, -6, -7
 KIND_CLIP, KIND_DISCORDANT, KIND_UNMAP, KIND_LOWMAPQ = 0, 1, 2, 3
 KIND_NAMES = {KIND_CLIP: "clip", KIND_DISCORDANT: "discordant", KIND_UNMAP: "unmap"}
-KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT, KERNEL_POLISH, KERNEL_PAIRS, KERNEL_ANCHORS, KERNEL_GAPSPAN, KERNEL_POLISH_GAPPED, KERNEL_PILEUP, KERNEL_JOIN, KERNEL_ALT = range(20)
+KERNEL_SCREEN, KERNEL_TAG, KERNEL_LOWMAPQ, KERNEL_ASSEMBLE, KERNEL_POOL, KERNEL_SYNTH, KERNEL_COUNT, KERNEL_VERIFY, KERNEL_INGEST, KERNEL_PICK, KERNEL_MERGE, KERNEL_SUPPORT, KERNEL_POLISH, KERNEL_PAIRS, KERNEL_ANCHORS, KERNEL_GAPSPAN, KERNEL_POLISH_GAPPED, KERNEL_PILEUP, KERNEL_JOIN, KERNEL_ALT, KERNEL_ADJ = range(21)
 
 # words of the merge round's statistics (gf_merge_open_gaps_dev, u32[32])
 MG_N_PRE, MG_N_SETS, MG_SKIPPED, MG_N_PAIRS, MG_QC_FLAGS, MG_N_JOBS, MG_ERR, MG_N0, MG_N_EDGES, MG_SETS_WITH_JOBS = range(10)
@@ -150,6 +150,18 @@ FA_F_REVERSE, FA_F_RIVAL_REVERSE, FA_F_HAS_RIVAL, FA_F_LENGTH_VARIES, FA_F_OUTRA
 FA_C_NONE, FA_C_WINNER, FA_C_IDENTICAL, FA_C_NEAR, FA_C_FAR, FA_C_LOWER = range(6)
 FA_CLOSED, FA_CONTESTED, FA_LENGTH_VARIES, FA_CANDIDATES, FA_LOWER, FA_IDENTICAL, FA_NEAR, FA_FAR, FA_OUTRANKED, FA_LOST, FA_WORDS = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 16
 FA_MAX_DIST, FA_DIST_FAR = 31, 0xFFFF
+
+# the read adjudication of the contested fills (gf_fill_adjudicate_dev): the record per gap (48 bytes, all zero: not contested), the
+# verdicts, the flags, the words of the statistics (u32[16]; VOTES_W, VOTES_R, TIES are u64) and the limits of context and ratio
+FILL_ADJ = np.dtype([("contig", "<u4"), ("rival", "<u4"), ("locus_w", "<u4"), ("locus_r", "<u4"), ("votes_w", "<u4"), ("votes_r", "<u4"),
+                     ("votes_w_s0", "<u4"), ("votes_r_s0", "<u4"), ("ties", "<u4"), ("unplaced", "<u4"), ("only", "<u4"), ("verdict", "u1"),
+                     ("flags", "u1"), ("reserved", "<u2")])
+assert FILL_ADJ.itemsize == 48
+AJ_KEEP, AJ_SWITCH, AJ_UNDECIDED = 1, 2, 3
+AJ_F_LONG, AJ_F_NON_ACGT, AJ_F_RIVAL_FAR, AJ_F_NO_ROWS = 1, 2, 4, 8
+(AJ_SEEN, AJ_ADJUDICATED, AJ_N_KEEP, AJ_N_SWITCH, AJ_N_UNDECIDED, AJ_SKIPPED_LONG, AJ_SKIPPED_NON_ACGT, AJ_MISMATCH, AJ_VOTES_W, AJ_VOTES_R, AJ_TIES,
+ AJ_WORDS) = 0, 1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 16
+AJ_MAX_CONTEXT, AJ_MAX_RATIO = 1000, 16
 
 # the gap-size measurement (gf_gap_span_dev): the record per (library, gap), its flag (n >= 1) and the words of its statistics (u32[16]):
 # u64 each: candidates, accepted, multi, clipped, lowq, low, high; then u32 gaps with n >= 1
@@ -313,6 +325,7 @@ def lib():
         "gf_pick_extended_aligned_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_pick_joins_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp]),
         "gf_fill_alts_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
+        "gf_fill_adjudicate_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp]),
         "gf_pick_extended_gapped_dev": (i32, [vp, vp, vp, sz, vp, i32, vp, vp, i32, vp, vp, vp, vp, sz, vp]),
         "gf_fill_support_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, vp, vp]),
         "gf_fill_polish_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),

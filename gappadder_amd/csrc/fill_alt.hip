@@ -14,11 +14,13 @@
 //   records  one wave per gap: the rival re-located from its key and scanned again, prefix and suffix once more, the record from lane 0
 // The rival key is the pick word of a peer without its level (all peers have the winner's) and with the distance in its place:
 // span field << 38 | (PICK_CONTIG_MAX - contig) << 7 | strand << 6 | min(dist, 63): the same order, and the records kernel reads the
-// distance from it whether the caller passed a per-contig buffer or not.
+// distance from it whether the caller passed a per-contig buffer or not.  What a candidate is and how its oriented fill is read:
+// fill_alt_dev.hpp (alt_candidate, AltFill), shared with fill_adj.hip.
 #include <cstring>
 
 #include "anchor.hpp"
 #include "contig_list.hpp"
+#include "fill_alt_dev.hpp"
 #include "gf_internal.hpp"
 #include "pick_word.hpp"
 
@@ -53,40 +55,6 @@ GF_HD unsigned long long alt_key_pack(uint32_t span, uint32_t contig, uint32_t s
     const unsigned long long span1 = (uint64_t)span + 1 < PICK_SPAN_SAT ? (uint64_t)span + 1 : PICK_SPAN_SAT;
     return (span1 << 38) | ((unsigned long long)(PICK_CONTIG_MAX - contig) << 7) | ((unsigned long long)strand << 6) | (dist < ALT_KEY_FAR ? dist : ALT_KEY_FAR);
 }
-
-// a candidate: the contig's own word as pick_anchor_kernel forms it (level, span, strand) and where its fill starts on the contig as stored
-struct AltCand { uint32_t level, span, strand, start; };
-
-// the whole wave scans contig c; false: pick_anchor_kernel publishes no word for it.  Every lane returns the same.
-__device__ __forceinline__ bool alt_candidate(const AltParams& P, const gf_contig& c, uint32_t lane, AltCand* o) {
-    const uint32_t a = P.a_s, al = P.a_l;
-    if (c.gap >= P.n_gaps || c.length < 2 * a) return false;
-    const uint8_t* as = anchor_rows(P.anc_s, c.gap);
-    if (!anchor_rows_set(as)) return false;
-    const uint8_t* alp = P.anc_l ? anchor_rows(P.anc_l, c.gap) : nullptr;
-    const bool has_long = alp && anchor_rows_set(alp) && c.length >= 2 * al;
-    const bool want[2] = {true, true};
-    uint32_t mn[8], mx[8];
-    bool any[8];
-    anchor_scan<true>(P.list.seq + c.seq_off, c.length, as, has_long ? alp : nullptr, a, al, want, lane, mn, mx, any);
-    uint32_t orient = 0, best = 0;
-    if (has_long) best = pick_span(any + 4, mn + 4, mx + 4, anchor_flags(alp), al, &orient);
-    if (best) {
-        *o = {al, best - 1, orient, (orient ? mn[4 + ANC_RC_RIGHT] : mn[4 + ANC_LEFT]) + al};
-        return true;
-    }
-    best = pick_span(any, mn, mx, anchor_flags(as), a, &orient);
-    if (!best) return false;
-    *o = {a, best - 1, orient, (orient ? mn[ANC_RC_RIGHT] : mn[ANC_LEFT]) + a};
-    return true;
-}
-
-// an oriented fill: byte x of it, read forward or complemented from the far end
-struct AltFill {
-    const char* s;                   // the contig
-    uint32_t start, len, strand;
-    __device__ __forceinline__ uint8_t at(uint32_t x) const { return (uint8_t)(strand ? base_comp(s[start + len - 1 - x]) : s[start + x]); }
-};
 
 // longest common prefix of W and P, at most `limit` <= min(W.len, P.len)
 __device__ __forceinline__ uint32_t alt_lcp(const AltFill& W, const AltFill& Pf, uint32_t limit, uint32_t lane) {

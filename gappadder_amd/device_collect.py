@@ -281,6 +281,26 @@ def fill_alternatives_files(pipe, res, kmers):
     return "".join("\t".join(c) + "\n" for c in rows), "".join(fa)
 
 
+ADJ_FIELDS = B.FILL_ADJ.names[:-1]             # (not the reserved word)
+
+
+def fill_adjudication_files(pipe, res, kmers):
+    """(fill_adjudication.tsv, adjudicated_seqs.fa) of a step with the read adjudication on.  The table: under a header line one row per
+    contested gap (fill_alternatives.contested) in gap order: the gap's name as picked_seqs.fa spells it, the fields of its gf_fill_adj
+    record (Results.adjudication), and the verdict as a word.  The sequences: picked_seqs.fa's records — every closed gap in gap order
+    under its picked name, lines of 60 — with the rival's sequence where the verdict is switch (Pipeline.adjudicated_sequences)."""
+    from . import fill_adjudication as ADJ
+    from . import fill_alternatives as FA
+    names, seqs = picked_names(res, kmers), pipe.adjudicated_sequences(res)
+    rows = [("name",) + ADJ_FIELDS + ("verdict_word",)]
+    for g in range(len(res.alts)):
+        if FA.contested(res.alts[g]):
+            rec = res.adjudication[g]
+            rows.append([names.get(g, res.keys[g])] + [str(int(rec[f])) for f in ADJ_FIELDS] + [ADJ.VERDICTS[int(rec["verdict"])]])
+    fa = [">" + names[g] + "\n" + "".join(seqs[g][0][i:i + 60] + "\n" for i in range(0, len(seqs[g][0]), 60)) for g in sorted(names)]
+    return "".join("\t".join(c) + "\n" for c in rows), "".join(fa)
+
+
 def round_keywords(cfg, L, rnd, prefix, names, check, switch):
     """The Pipeline keywords of an optional round of the CLI: <prefix>_<name> = cfg["fill_<rnd>_<name>"] for the names the configuration
     holds, validated against the read length by `check` (its ValueError ends the run), and <switch> = True."""
@@ -671,6 +691,10 @@ class DeviceCollector:
                 FA.check_params(alts["alt_max_dist"])
             except ValueError as e:
                 raise SystemExit("parameters.fill_alternatives_max_dist: %s" % e)
+            if cfg.get("fill_adjudication"):
+                from . import fill_adjudication as ADJ
+                alts.update(round_keywords(cfg, L, "adjudication", "adj", ("seed", "max_mismatch", "min_overlap", "context", "min_votes", "ratio"),
+                                           ADJ.check_params, "adjudicate"))
         pipe = Pipeline(gf, len(gaps), L, kk, device=self.dev, anchor_mapq=self.anchor_mapq, clip_dist=self.clip_dist,
                         k_screen=k_screen or None, keep_read_ids=True, probe_column=False,
                         read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"), **polish, **pileup, **pairs, **span, **joins, **alts)
@@ -720,6 +744,8 @@ class DeviceCollector:
             files["flank_joins.tsv"] = flank_joins_tsv(res, gaps, cfg["kmers"])
         if res.alts is not None:
             files["fill_alternatives.tsv"], files["alt_seqs.fa"] = fill_alternatives_files(pipe, res, cfg["kmers"])
+        if res.adjudication is not None:
+            files["fill_adjudication.tsv"], files["adjudicated_seqs.fa"] = fill_adjudication_files(pipe, res, cfg["kmers"])
         for name, text in files.items():
             with open(cfg["wf"] + name, "w") as f:
                 f.write(text)

@@ -1,5 +1,5 @@
 """What the rounds that look at the closed fills after the last pick of the step share on the host (read_support.py, polish.py,
-polish_gapped.py, pileup.py, pair_span.py, pair_anchors.py; the device side: csrc/fill_round.hpp, fill_body.hpp, fill_place.hpp, fill_place_split.hpp): the twins' walk over a step's
+polish_gapped.py, pileup.py, pair_span.py, pair_anchors.py, fill_adjudication.py; the device side: csrc/fill_round.hpp, fill_body.hpp, fill_place.hpp, fill_place_split.hpp): the twins' walk over a step's
 Results (closed_fills, pool_reads), the placing rounds' skip classification and parameter check (skip_flag, check_placement), and the
 base of the round objects the Pipeline holds (FillRound).  A rule about closed fills exists once here and once on the device."""
 import numpy as np
@@ -15,7 +15,8 @@ for _i, _c in enumerate(b"ACGT"):
 NOT_WITH_SECOND_ROUND = {"read_support": "the support is defined on the step's pool", "polish": "the polish is defined on the step's pool",
                          "pileup": "the pile-up is defined on the step's pool",
                          "pair_span": "the pairs are looked up in the step's pools",
-                         "pair_anchors": "the anchored pairs are looked up in the step's pools"}
+                         "pair_anchors": "the anchored pairs are looked up in the step's pools",
+                         "adjudicate": "the adjudication is defined on the step's pool"}
 
 
 def refusals(name, on, single_rank, second_round):

@@ -80,13 +80,16 @@ def parse_configuration(path):
         raise SystemExit("parameters.fill_pairs_anchored needs fill_pairs: it reads the pair span's placements")
     # (name, default, lo, hi) of fill_<round>_<name>
     for rnd, own in (("polish", (("min_votes", 2, 1, None), ("max_indel", 8, 1, 16))), ("pairs", (("z", 3, 1, None), ("min_pairs", 8, 1, None))),
-                     ("pileup", (("min_depth", 3, 1, None), ("min_agree", 80, 1, 100)))):
+                     ("pileup", (("min_depth", 3, 1, None), ("min_agree", 80, 1, 100))),
+                     ("adjudication", (("min_votes", 3, 1, None), ("ratio", 2, 2, 16), ("context", None, 12, 1000)))):
         for name, default, lo, hi in (("seed", 16, 12, 32), ("max_mismatch", 4, 0, 15), ("min_overlap", 48, 12, None)) + own:
             key = "fill_%s_%s" % (rnd, name)
             try:
                 v = int(p[key]) if p.get(key) is not None else default
             except (TypeError, ValueError):
                 raise SystemExit("parameters.%s must be an integer, not %r" % (key, p[key]))
+            if v is None:                        # (fill_adjudication_context: the read length unless given)
+                continue
             if v < lo or (hi is not None and v > hi):
                 raise SystemExit("parameters.%s must be %s, not %r" % (key, "in %d..%d" % (lo, hi) if hi is not None else "at least %d" % lo, v))
             cfg[key] = v
@@ -126,6 +129,13 @@ def parse_configuration(path):
     if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= 31:
         raise SystemExit("parameters.fill_alternatives_max_dist must be an integer in 1..31, not %r" % (p["fill_alternatives_max_dist"],))
     cfg["fill_alternatives_max_dist"] = v
+    # extension: with fill_alternatives, the read adjudication of the contested gaps (fill_adjudication.py): the gap's own reads placed on
+    # the winner's and on the rival's fill, a vote per read: {wf}fill_adjudication.tsv, one row per contested gap with the votes and the
+    # verdict keep / switch / undecided, and {wf}adjudicated_seqs.fa, picked_seqs.fa's records with the rival's sequence where the verdict
+    # is switch.  Advice: picked_seqs.fa and the scaffold write-back do not change
+    cfg["fill_adjudication"] = bool(p.get("fill_adjudication", False))
+    if cfg["fill_adjudication"] and not cfg["fill_alternatives"]:
+        raise SystemExit("parameters.fill_adjudication needs fill_alternatives: it reads the alternatives round's records")
     # extension: recruitment rounds (assemble_gaps.assemble_pipeline): how often the second round — both-unmapped pairs recruited by the
     # open gaps' contigs, assembly, pick — is repeated with the contigs the round before built; 1: the reference's single round
     v = p.get("recruit_rounds")
@@ -259,6 +269,9 @@ def main_func(command, sf_config):
         if cfg["fill_alternatives"] and (first_round is None or first_round.alts is None):
             sys.stderr.write("fill_alternatives: only the first assembly round of the device-resident Collect (-c All) computes it: "
                              "no fill_alternatives.tsv, no alt_seqs.fa\n")
+        if cfg["fill_adjudication"] and (first_round is None or first_round.adjudication is None):
+            sys.stderr.write("fill_adjudication: only the first assembly round of the device-resident Collect (-c All) computes it: "
+                             "no fill_adjudication.tsv, no adjudicated_seqs.fa\n")
         if cfg["gap_span"] and not done:
             sys.stderr.write("gap_span: only the device-resident Collect computes it: no gap_span.tsv\n")
         timings["stages_s"]["collect" + ("_and_first_assembly_round" if first_round is not None else "")] = time.perf_counter() - t0

@@ -29,6 +29,7 @@ What the reference does with files between processes —
     gf_fill_polish_gapped_dev                                  ... with rows placed with one indel and votes on indel events (polish_gapped.py)
     gf_fill_pileup_dev                                         the same pool piled up on the whole winning contig: eight counters per column, a record per gap (pileup.py)
     gf_fill_pairs_dev                                          per library: the read pairs of every closed gap placed on its fill (pair_span.py)
+    gf_fill_adjudicate_dev                                     the pool of every contested gap placed on the winner's and the rival's fill: votes and a verdict (fill_adjudication.py)
     gf_gap_span_dev                                            per library, behind its tagger: the size of every gap from the pairs that span it (gap_span.py)
 
 `Pipeline` owns the sizing pass (capacities follow what the libraries actually recruit), every buffer of the core step, the stream
@@ -45,6 +46,7 @@ import torch
 
 from . import _lib as B
 from . import extended_fill as EXT
+from . import fill_adjudication as FADJ
 from . import fill_alternatives as FA
 from . import flank_joins as FJ
 from . import fill_rounds as FR
@@ -93,7 +95,7 @@ class Results:
     the merge round and of the optional rounds are None unless the round ran."""
     merge = rescue = rescue_first = round2 = round2_first = round2_reads = extended = ext = ext_bases = support = support_stats = None
     polish = polish_bases = polish_stats = pairs = pair_stats = lib_pool_off = lib_pool_rows = lib_pool_ids = None
-    pair_anchors = pair_anchor_stats = lib_taghits = gap_span = gap_span_stats = pileup = pileup_track = pileup_stats = joins = join_stats = alts = alt_contigs = alt_stats = None
+    pair_anchors = pair_anchor_stats = lib_taghits = gap_span = gap_span_stats = pileup = pileup_track = pileup_stats = joins = join_stats = alts = alt_contigs = alt_stats = adjudication = adj_stats = None
 
 
 # anchor mode -> its pick, its pick over the contigs from an index on, its extended fill; do its picks leave a selection per contig
@@ -113,7 +115,8 @@ class Pipeline:
                  pair_max_mismatch=4, pair_min_overlap=48, pair_z=3, pair_anchors=False, pair_min_pairs=8, gap_span=False, span_z=3,
                  span_shift=1000, span_min_pairs=8, pileup=False, pileup_seed=16, pileup_max_mismatch=4, pileup_min_overlap=48, pileup_min_depth=3,
                  pileup_min_agree=80, pileup_track=True, flank_joins=False, join_max_overlap=256, join_min_context=30, join_max_mismatch=2,
-                 alternatives=False, alt_max_dist=16):
+                 alternatives=False, alt_max_dist=16, adjudicate=False, adj_seed=16, adj_max_mismatch=4, adj_min_overlap=48, adj_context=None,
+                 adj_min_votes=3, adj_ratio=2):
         """gf: a GapFill whose gaps (and flanks, when a library is screened) are set.  k_pairs: [(k, k_velvet)] of
         assemble_gaps.py:87-122.  The screen runs at the SMALLEST k of the list: a read that shares a 51-mer with a flank shares
         its 31-mers too, so this is the superset every assembly k needs (the reference recruits once, then assembles at every k).
@@ -168,7 +171,12 @@ class Pipeline:
         within alt_max_dist edits of it, or further away — and the best of the differing ones is the gap's rival (Results.alts,
         gf_fill_alt per gap; .alt_contigs, gf_fill_alt_contig per contig; .alt_stats; alternative_sequences).  Exact anchors only; it
         reads the step's contigs, the flanks and the pick words, so it goes with second_round, merge_in_step, rescue_round,
-        extended_fill and flank_joins; single rank."""
+        extended_fill and flank_joins; single rank.
+        adjudicate with adj_seed, adj_max_mismatch, adj_min_overlap, adj_context, adj_min_votes, adj_ratio (fill_adjudication.py; only
+        with alternatives): last of the after-pick rounds, the pool of every CONTESTED gap is placed on the winner's and on the rival's
+        fill, each between adj_context bases of the flanks (default: the read length), and every row votes for the one it fits strictly
+        better: KEEP, SWITCH or UNDECIDED per gap (Results.adjudication, gf_fill_adj per gap; .adj_stats; adjudicated_sequences).
+        Advice only: the picks, the contigs and picked_sequences stay as they are."""
         # what the options exclude, before anything touches gf or the library
         single_rank = int(world) == 1 and not force_exchange
         k_round2 = min([int(a) for a, _ in k_pairs if 16 <= int(a) <= 64], default=None)
@@ -192,6 +200,8 @@ class Pipeline:
                          (flank_joins and not single_rank, "flank_joins runs on a single rank"),
                          (alternatives and anchor_mode in PICKS and anchor_mode != "exact", "alternatives works with the exact anchors: not with anchor_mode %r" % (anchor_mode,)),
                          (alternatives and not single_rank, "alternatives runs on a single rank"),
+                         (adjudicate and not alternatives, "adjudicate needs alternatives: it reads the alternatives round's records"),
+                         *FR.refusals("adjudicate", adjudicate, single_rank, second_round),
                          (extended_fill and not single_rank, "extended_fill runs on a single rank"),
                          (extended_fill and len(k_pairs) > B.EXT_MAX_PAIRS, "extended_fill: at most %d (k, kv) pairs" % B.EXT_MAX_PAIRS)):
             if bad:
@@ -216,7 +226,9 @@ class Pipeline:
                                      read_len) if pileup else None)
         self.pairs = PSP.PairSpan(self, pair_seed, pair_max_mismatch, pair_min_overlap, pair_z, read_len) if pair_span else None
         self.anchored = PAN.PairAnchors(self, pair_min_pairs, read_len) if pair_anchors else None        # (launched by self.pairs, per library)
-        self.after_pick = [r for r in (self.support, self.polish, self.pileup, self.pairs, self.anchored) if r is not None]      # (the order they run in)
+        self.adj = (FADJ.FillAdjudication(self, adj_seed, adj_max_mismatch, adj_min_overlap, adj_context, adj_min_votes, adj_ratio, read_len)
+                    if adjudicate else None)          # (reads the records self.alts wrote before the after-pick rounds)
+        self.after_pick = [r for r in (self.support, self.polish, self.pileup, self.pairs, self.anchored, self.adj) if r is not None]      # (the order they run in)
         self.gap_span = GSP.GapSpan(self, span_z, span_shift, span_min_pairs) if gap_span else None      # (launched behind every tagger pass, per library)
         self.gf, self.lib, self.h = gf, B.lib(), gf.handle
         self.n_gaps, self.L, self.kk = int(n_gaps), int(read_len), [(int(a), int(b)) for a, b in k_pairs]
@@ -895,6 +907,17 @@ class Pipeline:
             ci, first, end, flip, rev = Pipeline._contig_cut(self, res, g, int(rec["rival"]), int(rec["level"]), bool(int(rec["flags"]) & B.FA_F_RIVAL_REVERSE))
             body = contig_text(res, ci)[first:end]
             out[int(g)] = (ci, revcomp(body) if flip else body, rev)
+        return out
+
+    def adjudicated_sequences(self, res):
+        """{gap: (gap sequence, "picked" | "rival")} of every closed gap of the last step: picked_sequences' text, and
+        alternative_sequences' text where the adjudication's verdict is SWITCH."""
+        if res.adjudication is None:
+            raise ValueError("adjudicated_sequences needs the Results of a Pipeline(alternatives=True, adjudicate=True) step")
+        rivals = self.alternative_sequences(res)
+        out = {g: (text, "picked") for g, (_, text, _) in self.picked_sequences(res).items()}
+        for g in np.nonzero(res.adjudication["verdict"] == B.AJ_SWITCH)[0]:
+            out[int(g)] = (rivals[int(g)][1], "rival")
         return out
 
     def merge_open_gaps(self, res, max_set=128):

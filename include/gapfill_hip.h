@@ -1330,6 +1330,63 @@ int gf_merge_rescue_dev(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_t 
                         const void* d_gap_best, size_t n_gaps, const gf_ovl_params* params, int kmer_len_quick, int max_set, const int* k_list,
                         const int* kv_list, int n_k, const void* d_merge_stats, const void* d_rescue_first, const void* d_gap_bridges, void* d_stats);
 
+/* ---- read adjudication of the contested fills (csrc/fill_adj.hip; definition and host twin: gappadder_amd/fill_adjudication.py,
+ * DESIGN.md §26).  A gap is CONTESTED when its gf_fill_alt (d_alt, read only: what gf_fill_alts_dev wrote over the same list and pick
+ * words) has GF_FA_F_HAS_RIVAL and not GF_FA_F_LOST.  For such a gap the oriented fills F_w of `contig` and F_r of `rival` are located
+ * again by gf_fill_alts_dev's candidate rule; a contig that is no contig of the gap, that the gap's pick word does not name (the winner),
+ * that is no candidate, or whose fill has another strand or length than the record states is a MISMATCH: zero record, counted.  The
+ * LOCUS of a fill F is LC + F + RC, LC the last min(context, |LF|) bytes of the gap's left flank, RC the first min(context, |RF|) of
+ * its right flank: d_flank_text holds n_gaps * 2 * context bytes (LC then RC, each from the start of its `context` bytes),
+ * d_flank_len n_gaps * 2 u16 (their lengths).  Every row of the gap's pool (the pool arguments of gf_fill_polish_dev) is placed on
+ * both loci by gf_fill_polish_dev's placement rule (seed, max_mismatch, min_overlap); its key on a locus is the smallest mismatches << 12
+ * | (4095 - overlap) over its accepted (strand, diagonal) pairs whatever their number, its strand there 0 when a pair with that key
+ * lies on strand 0.  The row votes for the locus with the smaller key (no pair: larger than every key), ties when both keys are equal,
+ * is unplaced without a pair on either.  verdict: KEEP when votes_w >= min_votes and votes_w >= ratio * votes_r, SWITCH the same way
+ * round, else UNDECIDED.  A locus of more than GF_PL_MAX_CONTIG bases (either one), or with a byte other than A, C, G, T, is flagged
+ * and counted: the lengths set, votes and verdict zero.  d_place_scratch: u32 per pool row, overwritten.  d_adj: n_gaps gf_fill_adj,
+ * written for every gap (all zero: not contested, or a mismatch); d_stats: GF_AJ_WORDS u32, zeroed by the call.  The placement rule
+ * out of gf_fill_polish_dev's range: GF_E_UNSUPPORTED; context outside min_overlap..1000, min_votes < 1, ratio outside 2..GF_AJ_MAX_RATIO,
+ * a missing argument or anchor lengths outside 8 <= short < long <= 32 (or short 0): GF_E_INVAL.  No host synchronisation. */
+typedef struct {
+    uint32_t contig, rival;          /* the winner's and the rival's index in the list */
+    uint32_t locus_w, locus_r;       /* bases of the two loci */
+    uint32_t votes_w, votes_r;       /* rows that fit the winner's / the rival's locus strictly better */
+    uint32_t votes_w_s0, votes_r_s0; /* of them: rows placed as stored (strand 0) on the locus they vote for */
+    uint32_t ties, unplaced;         /* rows with equal keys on both loci; rows with no accepted pair on either */
+    uint32_t only;                   /* votes of rows with no accepted pair on the other locus */
+    uint8_t verdict;                 /* GF_AJ_KEEP, GF_AJ_SWITCH, GF_AJ_UNDECIDED; 0: not adjudicated */
+    uint8_t flags;                   /* GF_AJ_F_* */
+    uint16_t reserved;
+} gf_fill_adj;
+#define GF_AJ_KEEP 1
+#define GF_AJ_SWITCH 2
+#define GF_AJ_UNDECIDED 3
+#define GF_AJ_F_LONG 1            /* skipped: a locus of more than GF_PL_MAX_CONTIG bases */
+#define GF_AJ_F_NON_ACGT 2        /* skipped: a locus byte other than A, C, G, T */
+#define GF_AJ_F_RIVAL_FAR 4       /* the rival's dist is GF_FA_DIST_FAR */
+#define GF_AJ_F_NO_ROWS 8         /* the gap's pool is empty */
+/* words of d_stats: contested gaps seen, adjudicated, and of them keep, switch, undecided; skipped long, skipped non-ACGT, mismatches;
+ * u64 each (two words, low first): votes_w, votes_r, ties over the adjudicated gaps */
+#define GF_AJ_SEEN 0
+#define GF_AJ_ADJUDICATED 1
+#define GF_AJ_N_KEEP 2
+#define GF_AJ_N_SWITCH 3
+#define GF_AJ_N_UNDECIDED 4
+#define GF_AJ_SKIPPED_LONG 5
+#define GF_AJ_SKIPPED_NON_ACGT 6
+#define GF_AJ_MISMATCH 7
+#define GF_AJ_VOTES_W 8
+#define GF_AJ_VOTES_R 10
+#define GF_AJ_TIES 12
+#define GF_AJ_WORDS 16
+#define GF_AJ_MAX_CONTEXT 1000
+#define GF_AJ_MAX_RATIO 16
+int gf_fill_adjudicate_dev(gf_ctx* ctx, const void* d_pool_packed, const void* d_nmask_or_null, const void* d_pool_off, size_t pool_rows,
+                           int read_len, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
+                           const void* d_gap_best, int anchor_long, int anchor_short, const void* d_alt, const void* d_flank_text,
+                           const void* d_flank_len, void* d_place_scratch, int seed, int max_mismatch, int min_overlap, int context,
+                           int min_votes, int ratio, void* d_adj, void* d_stats);
+
 /* ---- device memory + timing helpers (so a ctypes host needs no other HIP binding) ---------------------- */
 int gf_dev_alloc(gf_ctx* ctx, size_t bytes, void** d_ptr);
 int gf_dev_free(gf_ctx* ctx, void* d_ptr);
@@ -1357,6 +1414,7 @@ int gf_memset_dev(gf_ctx* ctx, void* d_ptr, int value, size_t bytes);
 #define GF_KERNEL_PILEUP 17  /* per-base pile-up of the closed gaps */
 #define GF_KERNEL_JOIN 18  /* flank-overlap joins of the open gaps */
 #define GF_KERNEL_ALT 19  /* fill alternatives of the closed gaps */
+#define GF_KERNEL_ADJ 20  /* read adjudication of the contested fills */
 int gf_timing_enable(gf_ctx* ctx, int on);
 int gf_timing_read(gf_ctx* ctx, int which, double* total_ms, uint64_t* launches);
 int gf_timing_reset(gf_ctx* ctx);
