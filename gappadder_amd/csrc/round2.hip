@@ -17,38 +17,11 @@
 #include <rocprim/device/device_scan.hpp>
 
 #include "gf_internal.hpp"
+#include "round2_dev.hpp"
 
 namespace gf {
 
 namespace {
-
-enum : uint32_t {
-    R2_KMERS = 0,        // contig k-mer positions of the open gaps (the table's sizing count)
-    R2_TAB_FULL = 1,     // (k-mer, gap) entries the table had no room for
-    R2_HITS = 2,         // keys emitted by the recruitment (beyond the key capacity: not stored)
-    R2_UNIQUE = 3,       // distinct (gap, library, pair)
-    R2_TRIED = 4,        // gaps open after the first pick
-    R2_WITH = 5,         // gaps with at least one recruited pair
-    R2_ROWS = 6,         // u64 (words 6-7): rows of the round-2 pools
-    R2_FIRST = 8,        // index of the first round-2 contig in the step's list
-    R2_APPEND_ERR = 9,   // the round-2 contigs did not fit the step's list (nothing appended)
-    R2_N2 = 10,          // round-2 contigs appended
-    R2_POOL_OVF = 11,    // the round-2 pools did not fit their capacity (every round-2 pool left empty)
-};
-
-constexpr unsigned long long R2_EMPTY_KEY = ~0ull;
-
-struct R2Slot {
-    uint64_t hi, lo;
-    uint32_t gap, state;
-};
-static_assert(sizeof(R2Slot) == 24, "slot layout");
-
-struct LibRows {
-    const uint8_t* reads[GF_R2_MAX_LIBS];
-};
-
-__device__ __forceinline__ bool r2_acgt(char c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
 
 __global__ __launch_bounds__(256) void r2_candidates_kernel(const uint32_t* recs, uint64_t n_recs, uint64_t n_reads, uint32_t* bits,
                                                             uint32_t* out, uint64_t cap, uint32_t* n_out) {
@@ -62,34 +35,6 @@ __global__ __launch_bounds__(256) void r2_candidates_kernel(const uint32_t* recs
         const uint32_t j = atomicAdd(n_out, 1u);
         if (j < cap) out[j] = pair;
     }
-}
-
-__device__ void r2_insert(R2Slot* tab, uint32_t log2, K128 v, uint32_t gap, uint32_t* full) {
-    const uint32_t mask = (uint32_t)((1ull << log2) - 1);
-    uint32_t pos = hash_kmer(v, (int)log2);
-    uint64_t probes = 0;
-    while (probes <= mask) {
-        R2Slot* s = tab + pos;
-        const uint32_t st = __hip_atomic_load(&s->state, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        if (st == 0u) {
-            if (atomicCAS(&s->state, 0u, 1u) == 0u) {
-                __hip_atomic_store(&s->hi, v.hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&s->lo, v.lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&s->gap, gap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&s->state, 2u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-                return;
-            }
-            continue;            // lost the claim: read the same slot again
-        }
-        if (st == 1u) continue;  // being written: read it again in the next turn
-        if (__hip_atomic_load(&s->hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == v.hi &&
-            __hip_atomic_load(&s->lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == v.lo &&
-            __hip_atomic_load(&s->gap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gap)
-            return;              // (k-mer, gap) is in the table already
-        pos = (pos + 1) & mask;
-        ++probes;
-    }
-    atomicAdd(full, 1u);
 }
 
 __global__ __launch_bounds__(256) void r2_table_kernel(const gf_contig* ctg, const uint32_t* d_n, uint64_t ctg_cap, const char* seq,
@@ -178,8 +123,6 @@ __global__ __launch_bounds__(256) void r2_recruit_kernel(const uint8_t* reads, c
         }
     }
 }
-
-__device__ __forceinline__ uint32_t key_gap(unsigned long long x) { return (uint32_t)(x >> 40); }
 
 __global__ __launch_bounds__(256) void r2_mark_kernel(const unsigned long long* s, uint64_t n, uint64_t n_gaps, uint32_t* flag, uint32_t* cnt) {
     for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
@@ -279,10 +222,6 @@ __global__ void r2_append_counts_kernel(uint32_t* d_n1, uint64_t dst_cap, uint64
     *d_n1 = (uint32_t)(n1 + n2);
     *d_s1 = s1 + s2;
     stats[R2_N2] = (uint32_t)n2;
-}
-
-unsigned r2_grid(gf_ctx* ctx, uint64_t work) {
-    return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((uint64_t)ctx->n_cu * 16, (work + 255) / 256));
 }
 
 }  // namespace

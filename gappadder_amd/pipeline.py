@@ -93,7 +93,7 @@ class DeviceLibrary:
 class Results:
     """What one step left on the device, fetched once (contigs, their bases, the pick words, the pools when asked for).  The fields of
     the merge round and of the optional rounds are None unless the round ran."""
-    merge = rescue = rescue_first = round2 = round2_first = round2_reads = extended = ext = ext_bases = support = support_stats = None
+    merge = rescue = rescue_first = round2 = round2_first = round2_reads = recruit_rounds = recruit_rounds_run = recruit_reads = extended = ext = ext_bases = support = support_stats = None
     polish = polish_bases = polish_stats = pairs = pair_stats = lib_pool_off = lib_pool_rows = lib_pool_ids = None
     pair_anchors = pair_anchor_stats = lib_taghits = gap_span = gap_span_stats = pileup = pileup_track = pileup_stats = joins = join_stats = alts = alt_contigs = alt_stats = adjudication = adj_stats = None
 
@@ -109,7 +109,7 @@ class Pipeline:
     def __init__(self, gf, n_gaps, read_len, k_pairs, device=None, world=1, rank=0, backend="nccl", force_exchange=False,
                  min_count=2, min_contig=40, anchors=(30, 15), clip_dist=250, anchor_mapq=30, k_screen=None, keep_read_ids=False,
                  key_column=True, linear_keys=True, probe_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False,
-                 extended_fill=False, ext_base_cap=None, rescue_round=False, read_support=False, support_k=None, polish=False,
+                 recruit_rounds=1, extended_fill=False, ext_base_cap=None, rescue_round=False, read_support=False, support_k=None, polish=False,
                  polish_seed=16, polish_max_mismatch=4, polish_min_overlap=48, polish_min_votes=2, polish_indels=False, polish_max_indel=8,
                  pair_span=False, pair_seed=16,
                  pair_max_mismatch=4, pair_min_overlap=48, pair_z=3, pair_anchors=False, pair_min_pairs=8, gap_span=False, span_z=3,
@@ -139,7 +139,8 @@ class Pipeline:
         Results carry `ctg_pick` (gf_ctg_pick per contig) and `align_dropped` / `align_seed_overflow` (the pick's d_stats).
         second_round (second_round.py), rescue_round (rescue_round.py), extended_fill with ext_base_cap (extended_fill.py): the
         reference's later stages inside the step, each described in its module; in the step they run in this order after the merge
-        round's pick.  read_support with support_k (read_support.py; default: the smallest k of k_pairs in 16..64): after all of them,
+        round's pick.  recruit_rounds (1..16, with second_round): the second round repeated with the contigs of the round before until a
+        round grows no gap (Results.recruit_rounds, .recruit_rounds_run, .recruit_reads).  read_support with support_k (read_support.py; default: the smallest k of k_pairs in 16..64): after all of them,
         a record per closed gap of how its pool backs the k-mers of its fill (Results.support).  polish with polish_seed,
         polish_max_mismatch, polish_min_overlap, polish_min_votes (polish.py): last of all, the pool of every closed gap is piled up on
         its winning contig and every column of the fill takes a vote (Results.polish, .polish_bases, .polish_stats;
@@ -187,6 +188,9 @@ class Pipeline:
                          (second_round and not single_rank, "second_round runs on a single rank"),
                          (second_round and merge_in_step, "second_round with merge_in_step: the order of the merge and the second round is not settled"),
                          (second_round and k_round2 is None, "second_round needs a k in 16..64 among k_pairs"),
+                         (isinstance(recruit_rounds, bool) or not isinstance(recruit_rounds, int) or not 1 <= recruit_rounds <= 16,
+                          "recruit_rounds %r: an integer 1..16" % (recruit_rounds,)),
+                         (not second_round and recruit_rounds != 1, "recruit_rounds repeats the second round: it needs second_round"),
                          *FR.refusals("read_support", read_support, single_rank, second_round),
                          (read_support and support_k is None and k_round2 is None, "read_support needs support_k, or a k in 16..64 among k_pairs"),
                          *FR.refusals("polish", polish, single_rank, second_round),
@@ -209,7 +213,7 @@ class Pipeline:
         self.anchor_mode = anchor_mode
         self.per_contig = PICKS[anchor_mode][3]      # the mode's picks leave a selection per contig and two statistics words
         # the optional rounds, in the order the step runs them; None: off
-        self.round2 = R2.SecondRound(self, k_round2) if second_round else None
+        self.round2 = R2.SecondRound(self, k_round2, recruit_rounds) if second_round else None
         self.rescue = RS.RescueRound(self) if rescue_round else None
         self.joins = FJ.FlankJoins(self, join_max_overlap, join_min_context, join_max_mismatch) if flank_joins else None
         self.alts = FA.FillAlternatives(self, alt_max_dist) if alternatives else None
@@ -654,10 +658,10 @@ class Pipeline:
         if self.per_contig:
             self.d_ctg_pick = self._u8(self.contig_cap * B.CTG_PICK.itemsize)
 
-    def _size_round(self, name, grow):
+    def _size_round(self, name, grow, tries=8):
         """Sizing of an optional round: the step with the round runs on the hits prepare() left until grow() — which reads the round's
         counters and enlarges what they outgrew — reports that everything fitted."""
-        for _ in range(8):
+        for _ in range(tries):
             torch.cuda.synchronize()
             self._on_stream(lambda: self._step(recruited=True))
             self.sync()

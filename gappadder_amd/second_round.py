@@ -3,7 +3,11 @@ pick leaves open.  The pairs with both mates unmapped (FLAG & 12 == 12) that sha
 16..64) with a gap's round-1 contigs are appended to its pool, the gap is assembled again at every (k, kv) and picked over the round-2
 contigs only (appended after round 1's; Results.round2 / round2_first / round2_reads).  Single rank, without merge_in_step.
 The candidate pairs are listed from the libraries' alignment records once, in prepare(): like the key column, they assume the records
-do not change after prepare() (a caller that rewrites d_recs prepares a new Pipeline)."""
+do not change after prepare() (a caller that rewrites d_recs prepares a new Pipeline).
+recruit_rounds=R (1..16) repeats the round: round r >= 2 builds its table from the contigs round r - 1 appended, carries the keys recruited
+so far, recruits behind them, gives a pool (round-1 rows, then every pair recruited so far) to the open gaps whose recruits grew, assembles
+them, appends and picks over its own contigs; a round after one that grew no gap is gated on the device and does nothing
+(Results.recruit_rounds / recruit_rounds_run / recruit_reads).  rounds_host() is the same in plain Python."""
 import ctypes as C
 
 import numpy as np
@@ -14,8 +18,8 @@ from . import pipeline as P
 
 
 class SecondRound:
-    def __init__(self, pipe, k):
-        self.p, self.k = pipe, int(k)
+    def __init__(self, pipe, k, rounds=1):
+        self.p, self.k, self.R = pipe, int(k), int(rounds)
 
     def _alloc(self):
         p = self.p
@@ -26,6 +30,8 @@ class SecondRound:
         self.d_pool = p._u8(self.pool_cap * p.rb + 64)
         self.d_ctg = p._u8(self.ctg_cap * 32)
         self.d_seq = p._u8(self.seq_cap)
+        if self.R > 1 and p.keep_read_ids:      # round j's distinct keys, j < R: written by round j + 1's carry
+            self.d_snap = torch.empty((self.R - 1) * self.key_cap, dtype=torch.int64, device=p.dev)
 
     # ---- sizing (untimed) ------------------------------------------------------------------------------------------------------
     def prepare(self):
@@ -53,42 +59,54 @@ class SecondRound:
                 cap, d_pairs = n, torch.empty(n + 1, dtype=torch.int32, device=dev)
             self.cand.append((d_pairs, d_n, cap))
         self.lib_ptrs = (C.c_void_p * len(p.libs))(*[lb.d_reads.data_ptr() for lb in p.libs])
-        self.d_st = torch.zeros(B.R2_WORDS, dtype=torch.int32, device=dev)
-        self.d_acnt = torch.zeros(8, dtype=torch.int32, device=dev)
-        self.d_gap_err = torch.zeros(max(1, n_gaps), dtype=torch.int32, device=dev)
+        # one block per recruitment round of each of: statistics, assembly counters, gap errors, pool rows + offsets
+        R = self.R
+        self.d_st = torch.zeros(R * B.R2_WORDS, dtype=torch.int32, device=dev)
+        self.d_acnt = torch.zeros(R * 8, dtype=torch.int32, device=dev)
+        self.d_gap_err = torch.zeros(R * max(1, n_gaps), dtype=torch.int32, device=dev)
         # round-2 rows per gap, then their offsets (the pool_off of the round-2 assembly)
-        self.d_rows_all = torch.zeros(2 * (n_gaps + 1), dtype=torch.int64, device=dev)
-        self.d_rows, self.d_off = self.d_rows_all[:n_gaps + 1], self.d_rows_all[n_gaps + 1:]
+        self.d_rows_all = torch.zeros(R * 2 * (n_gaps + 1), dtype=torch.int64, device=dev)
+        self.d_rows, self.d_off = self.d_rows_all[:n_gaps + 1], self.d_rows_all[n_gaps + 1:2 * (n_gaps + 1)]
+        if R > 1:       # the carry's per-gap counts; the candidate counts in one array, and the copy a gated round zeroes
+            self.d_prev = torch.zeros(max(1, n_gaps), dtype=torch.int32, device=dev)
+            self.d_np = torch.cat([d_n[:1] for _, d_n, _ in self.cand]).contiguous()
+            self.d_np_live = torch.zeros(len(p.libs), dtype=torch.int32, device=dev)
+            torch.cuda.synchronize()
         self.log2, self.key_cap, self.pool_cap = 12, 4096, 4096
         self.ctg_cap, self.seq_cap = p.contig_caps(0)
         self._alloc()
         self.deepest = int(p.max_pool_rows)
-        p._size_round("second round", self._grow)
+        p._size_round("second round", self._grow, tries=8 + 4 * (self.R - 1))    # (a later round shows its counts once the earlier ones fit)
 
     def _grow(self):
-        p = self.p
-        st = self.d_st.cpu().numpy().view(np.uint32)
-        a1, a2 = p.d_acnt.cpu().numpy(), self.d_acnt.cpu().numpy()
-        n2, s2 = int(a2[0]), P.counter_u64(a2)
-        rows = P.counter_u64(st, B.R2_ROWS)
+        """Every capacity from the maximum over the rounds' blocks."""
+        p, R = self.p, self.R
+        st = self.d_st.cpu().numpy().view(np.uint32).reshape(R, B.R2_WORDS)
+        a1, a2 = p.d_acnt.cpu().numpy(), self.d_acnt.cpu().numpy().reshape(R, 8)
+        n2s, s2s = [int(a[0]) for a in a2], [P.counter_u64(a) for a in a2]
+        n2, s2 = max(n2s), max(s2s)
+        rows = max(P.counter_u64(b, B.R2_ROWS) for b in st)
+        kmers, hits = int(st[:, B.R2_KMERS].max()), int(st[:, B.R2_HITS].max())
         grown = False
-        need_log2 = max(12, int(2 * int(st[B.R2_KMERS]) + 16).bit_length())
-        if need_log2 > self.log2 or int(st[B.R2_TAB_FULL]):
+        need_log2 = max(12, int(2 * kmers + 16).bit_length())
+        if need_log2 > self.log2 or int(st[:, B.R2_TAB_FULL].max()):
             self.log2, grown = max(need_log2, self.log2 + 1), True
-        if int(st[B.R2_HITS]) > self.key_cap:
-            self.key_cap, grown = int(1.25 * int(st[B.R2_HITS])) + 4096, True
+        if hits > self.key_cap:
+            self.key_cap, grown = int(1.25 * hits) + 4096, True
         if rows > self.pool_cap:
             self.pool_cap, grown = int(1.25 * rows) + 4096, True
         if n2 > self.ctg_cap or s2 > self.seq_cap:
             c2, q2 = p.contig_caps(rows)
             self.ctg_cap, self.seq_cap, grown = max(c2, int(1.25 * n2)), max(q2, int(1.25 * s2)), True
-        # the step's list holds both rounds' contigs
-        n1, q1 = int(st[B.R2_FIRST]), P.counter_u64(a1) - (0 if int(st[B.R2_APPEND_ERR]) else s2)
-        if n1 + n2 > p.contig_cap or q1 + s2 > p.seq_cap:
-            p._alloc_contig_list(max(p.contig_cap, int(1.25 * (n1 + n2)) + 4096), max(p.seq_cap, int(1.25 * (q1 + s2)) + (1 << 20)))
+        # the step's list holds every round's contigs: what it holds now plus what the refused appends would have added
+        failed = [r for r in range(R) if int(st[r, B.R2_APPEND_ERR])]
+        n_all, q_all = int(a1[0]) + sum(n2s[r] for r in failed), P.counter_u64(a1) + sum(s2s[r] for r in failed)
+        if n_all > p.contig_cap or q_all > p.seq_cap:
+            p._alloc_contig_list(max(p.contig_cap, int(1.25 * n_all) + 4096), max(p.seq_cap, int(1.25 * q_all) + (1 << 20)))
             grown = True
-        # the assembly's workspace bounds cover the round-2 pools too (a pool beyond asm_big_pool_reads would set its gap error)
-        sizes = self.d_rows[:p.n_gaps].cpu().numpy()
+        # the assembly's workspace bounds cover the rounds' pools too (a pool beyond asm_big_pool_reads would set its gap error)
+        sizes = self.d_rows_all.cpu().numpy().reshape(R, 2, p.n_gaps + 1)[:, 0, :p.n_gaps]
+        sizes = sizes[int(np.argmax(sizes.max(axis=1)))] if sizes.size else sizes.reshape(-1)      # the round with the deepest pool
         deep = int(sizes.max()) if len(sizes) else 0
         if deep > self.deepest:
             self.deepest = deep
@@ -110,7 +128,9 @@ class SecondRound:
         p = self.p
         lib, h, n_gaps, k = p.lib, p.h, p.n_gaps, self.k
         st = self.d_st.data_ptr()
-        p._chk(lib.gf_memset_dev(h, st, 0, 4 * B.R2_WORDS) or lib.gf_memset_dev(h, self.d_keys.data_ptr(), 0xFF, 8 * self.key_cap), "gf_memset_dev")
+        p._chk(lib.gf_memset_dev(h, st, 0, 4 * B.R2_WORDS * self.R) or lib.gf_memset_dev(h, self.d_keys.data_ptr(), 0xFF, 8 * self.key_cap), "gf_memset_dev")
+        if self.R > 1:      # the later rounds' rows and offsets: a gated round leaves them alone, and its assembly must see empty pools
+            p._chk(lib.gf_memset_dev(h, self.d_rows_all.data_ptr() + 16 * (n_gaps + 1), 0, 16 * (n_gaps + 1) * (self.R - 1)), "gf_memset_dev")
         p._chk(lib.gf_contig_kmer_table_dev(h, p.d_ctg.data_ptr(), p.ap, p.contig_cap, p.d_seq.data_ptr(), p.d_best.data_ptr(), n_gaps, k,
                                             self.d_tab.data_ptr(), self.log2, st), "gf_contig_kmer_table_dev")
         for l, (lb, (d_pairs, d_n, cap)) in enumerate(zip(p.libs, self.cand)):
@@ -127,32 +147,160 @@ class SecondRound:
         p._chk(lib.gf_contigs_append_dev(h, p.d_ctg.data_ptr(), p.ap, p.contig_cap, p.d_seq.data_ptr(), p.ap + 8, p.seq_cap, self.d_ctg.data_ptr(), ap2,
                                          self.ctg_cap, self.d_seq.data_ptr(), ap2 + 8, self.seq_cap, st), "gf_contigs_append_dev")
         p._pick(*p.anchor_pair, first=self.first_ptr())
+        for r in range(1, self.R):
+            self._enqueue_later(r)
+
+    def _enqueue_later(self, r):
+        """Round r + 1 (r >= 1 counts from 0): carry, table of the contigs round r appended, recruitment behind the carried keys, pools of
+        the gaps that grew, assembly, append, pick over the round's own contigs — every new launch gated by round r's GROWN word."""
+        p = self.p
+        lib, h, n_gaps, k = p.lib, p.h, p.n_gaps, self.k
+        prev = self.d_st.data_ptr() + 4 * B.R2_WORDS * (r - 1)
+        st = prev + 4 * B.R2_WORDS
+        live = prev + 4 * (B.R2_GROWN if r > 1 else B.R2_WITH)
+        snap = self.d_snap.data_ptr() + 8 * self.key_cap * (r - 1) if p.keep_read_ids else None
+        p._chk(lib.gf_round_carry_dev(h, self.d_keys.data_ptr(), self.d_sorted.data_ptr(), self.key_cap, n_gaps, self.d_work.data_ptr(),
+                                      self.d_prev.data_ptr(), prev, st, p.ap, self.d_np.data_ptr(), self.d_np_live.data_ptr(), len(p.libs), snap,
+                                      live), "gf_round_carry_dev")
+        p._chk(lib.gf_contig_kmer_table_from_dev(h, p.d_ctg.data_ptr(), p.ap, p.contig_cap, p.d_seq.data_ptr(), p.d_best.data_ptr(), n_gaps, k,
+                                                 prev + 4 * B.R2_FIRST, self.d_tab.data_ptr(), self.log2, st, live), "gf_contig_kmer_table_from_dev")
+        for l, (lb, (d_pairs, _, cap)) in enumerate(zip(p.libs, self.cand)):     # (round 1's entry: a gated round has no candidates)
+            p._chk(lib.gf_recruit_by_contigs_dev(h, lb.d_reads.data_ptr(), lb.d_nmask.data_ptr() if lb.d_nmask is not None else None, lb.n_reads, p.L,
+                                                 d_pairs.data_ptr(), self.d_np_live.data_ptr() + 4 * l, cap, l, k, self.d_tab.data_ptr(), self.log2,
+                                                 self.d_keys.data_ptr(), self.key_cap, st), "gf_recruit_by_contigs_dev")
+        rows = self.d_rows_all.data_ptr() + 16 * (n_gaps + 1) * r
+        p._chk(lib.gf_round_pools_dev(h, self.d_keys.data_ptr(), self.d_sorted.data_ptr(), self.key_cap, self.lib_ptrs, len(p.libs), p.L, p.asm_ptr,
+                                      p.asm_off, p.d_best.data_ptr(), n_gaps, self.d_prev.data_ptr(), self.d_work.data_ptr(), rows,
+                                      self.d_pool.data_ptr(), self.pool_cap, st, live), "gf_round_pools_dev")
+        ap2 = self.d_acnt.data_ptr() + 32 * r
+        p._chk(lib.gf_assemble_multi_dev(h, self.d_pool.data_ptr(), None, rows + 8 * (n_gaps + 1), n_gaps, self.pool_cap, p.L, p.k_arr, p.kv_arr,
+                                         len(p.kk), p.min_count, p.min_contig, self.d_ctg.data_ptr(), self.ctg_cap, ap2, self.d_seq.data_ptr(),
+                                         self.seq_cap, ap2 + 8, self.d_gap_err.data_ptr() + 4 * max(1, n_gaps) * r),
+               "gf_assemble_multi_dev (round %d)" % (r + 1))
+        p._chk(lib.gf_contigs_append_dev(h, p.d_ctg.data_ptr(), p.ap, p.contig_cap, p.d_seq.data_ptr(), p.ap + 8, p.seq_cap, self.d_ctg.data_ptr(), ap2,
+                                         self.ctg_cap, self.d_seq.data_ptr(), ap2 + 8, self.seq_cap, st), "gf_contigs_append_dev")
+        p._pick(*p.anchor_pair, first=st + 4 * B.R2_FIRST)
 
     # ---- results ---------------------------------------------------------------------------------------------------------------
     def fetch(self, r):
-        st = self.d_st.cpu().numpy().view(np.uint32)
-        a2 = self.d_acnt.cpu().numpy()
-        n2, s2 = int(a2[0]), P.counter_u64(a2)
+        R = self.R
+        st_all = self.d_st.cpu().numpy().view(np.uint32).reshape(R, B.R2_WORDS)
+        a2_all = self.d_acnt.cpu().numpy().reshape(R, 8)
         n_err = int(self.d_gap_err.sum())
-        if n_err or int(st[B.R2_APPEND_ERR]) or n2 > self.ctg_cap or s2 > self.seq_cap:
-            raise RuntimeError("second round overflow: %d gap errors, append flag %d, %d contigs (cap %d), %d contig bases (cap %d)"
-                               % (n_err, int(st[B.R2_APPEND_ERR]), n2, self.ctg_cap, s2, self.seq_cap))
-        first = int(st[B.R2_FIRST])
-        n_keys = min(int(st[B.R2_HITS]), self.key_cap)
+        for st, a2 in zip(st_all, a2_all):
+            n2, s2 = int(a2[0]), P.counter_u64(a2)
+            if n_err or int(st[B.R2_APPEND_ERR]) or n2 > self.ctg_cap or s2 > self.seq_cap:
+                raise RuntimeError("second round overflow: %d gap errors, append flag %d, %d contigs (cap %d), %d contig bases (cap %d)"
+                                   % (n_err, int(st[B.R2_APPEND_ERR]), n2, self.ctg_cap, s2, self.seq_cap))
         cand = [int(d_n[0]) for _, d_n, _ in self.cand]
-        # recruits the round could not take: table entries without room, keys beyond their buffer, candidates beyond theirs, pools beyond theirs
-        dropped = (int(st[B.R2_TAB_FULL]) + max(0, int(st[B.R2_HITS]) - self.key_cap) + sum(max(0, c - cap) for c, (_, _, cap) in zip(cand, self.cand))
-                   + (2 * int(st[B.R2_UNIQUE]) if int(st[B.R2_POOL_OVF]) else 0))
-        r.round2_first = first
-        r.round2 = {"gaps_tried": int(st[B.R2_TRIED]), "gaps_with_recruits": int(st[B.R2_WITH]), "reads_recruited": 2 * int(st[B.R2_UNIQUE]),
-                    "contigs": int(st[B.R2_N2]), "gaps_closed": int(((r.best != 0) & (P.pick_index(r.best) >= first)).sum()), "dropped": int(dropped),
-                    "candidates": 2 * sum(cand)}
-        if self.p.keep_read_ids:      # per gap with recruits: [(library, read id)] in round-2 pool order
+        firsts = [int(st[B.R2_FIRST]) for st in st_all]
+        idx = P.pick_index(r.best)
+        rounds = []
+        for j, st in enumerate(st_all):
+            # recruits the round could not take: table entries without room, keys beyond their buffer, candidates beyond theirs, pools beyond theirs
+            dropped = (int(st[B.R2_TAB_FULL]) + max(0, int(st[B.R2_HITS]) - self.key_cap)
+                       + (sum(max(0, c - cap) for c, (_, _, cap) in zip(cand, self.cand)) if j == 0 else 0)
+                       + (2 * int(st[B.R2_UNIQUE]) if int(st[B.R2_POOL_OVF]) else 0))
+            closed = (r.best != 0) & (idx >= firsts[j])
+            if j + 1 < R:
+                closed &= idx < firsts[j + 1]
+            rounds.append({"gaps_tried": int(st[B.R2_TRIED]), "gaps_with_recruits": int(st[B.R2_WITH]), "reads_recruited": 2 * int(st[B.R2_UNIQUE]),
+                           "contigs": int(st[B.R2_N2]), "gaps_closed": int(closed.sum()), "dropped": int(dropped), "candidates": 2 * sum(cand),
+                           "new_pairs": int(st[B.R2_NEW] if j else st[B.R2_UNIQUE]), "gaps_grown": int(st[B.R2_GROWN] if j else st[B.R2_WITH]),
+                           "first": firsts[j], "gated": bool(st[B.R2_GATED])})
+        r.round2_first = firsts[0]
+        r.round2 = {key: rounds[0][key] for key in ("gaps_tried", "gaps_with_recruits", "reads_recruited", "contigs", "gaps_closed", "dropped",
+                                                    "candidates")}
+        r.round2["dropped"] = sum(d["dropped"] for d in rounds)
+        r.recruit_rounds = rounds
+        # the rounds that ran: up to and with the first that grew no gap (the rounds behind it are gated)
+        r.recruit_rounds_run = next((j + 1 for j, d in enumerate(rounds) if not d["gaps_grown"]), R)
+        if self.p.keep_read_ids:      # per gap with recruits: [(library, read id)] in round-2 pool order, after the last round that ran
+            live = [j for j, d in enumerate(rounds) if not d["gated"]]
+            last = live[-1]
+            n_keys = min(int(st_all[last][B.R2_HITS]), self.key_cap)
             keys = np.unique(self.d_sorted[:n_keys].cpu().numpy().view(np.uint64))
             keys = keys[keys != np.uint64(0xFFFFFFFFFFFFFFFF)]
-            gap, libi, pair = (keys >> np.uint64(40)).astype(np.int64), ((keys >> np.uint64(36)) & np.uint64(15)).astype(np.int64), \
-                (keys & np.uint64((1 << 36) - 1)).astype(np.int64)
-            out = {}
-            for g, l, q in zip(gap.tolist(), libi.tolist(), pair.tolist()):
-                out.setdefault(g, []).extend([(l, 2 * q), (l, 2 * q + 1)])
-            r.round2_reads = out
+            r.round2_reads = _reads_of_keys(keys)
+            # the pairs new in each round: its distinct keys (round j < last: the snapshot round j + 1's carry took) without the round before's
+            per, before = [], np.zeros(0, dtype=np.uint64)
+            for j in range(R):
+                if j > last:
+                    per.append({})
+                    continue
+                if j < last:
+                    n = min(int(st_all[j][B.R2_UNIQUE]), self.key_cap)
+                    now = self.d_snap[j * self.key_cap:j * self.key_cap + n].cpu().numpy().view(np.uint64)
+                else:
+                    now = keys[(keys >> np.uint64(40)) < np.uint64(self.p.n_gaps)]
+                per.append(_reads_of_keys(np.setdiff1d(now, before)))
+                before = now
+            r.recruit_reads = per
+
+
+def _reads_of_keys(keys):
+    """{gap: [(library, read id)]} of sorted keys gap << 40 | library << 36 | pair: both reads of every pair."""
+    gap, libi, pair = (keys >> np.uint64(40)).astype(np.int64), ((keys >> np.uint64(36)) & np.uint64(15)).astype(np.int64), \
+        (keys & np.uint64((1 << 36) - 1)).astype(np.int64)
+    out = {}
+    for g, l, q in zip(gap.tolist(), libi.tolist(), pair.tolist()):
+        out.setdefault(g, []).extend([(l, 2 * q), (l, 2 * q + 1)])
+    return out
+
+
+_RC = str.maketrans("ACGT", "TGCA")
+
+
+def _canonical_kmers(text, k):
+    out = set()
+    for i in range(len(text) - k + 1):
+        w = text[i:i + k]
+        if w.count("A") + w.count("C") + w.count("G") + w.count("T") == k:
+            out.add(min(w, w[::-1].translate(_RC)))
+    return out
+
+
+def rounds_host(pools, candidates, contigs, open_gaps, k, assemble, pick, max_rounds):
+    """The recruitment rounds in plain Python, from the state the first pick leaves.
+    pools: {gap: [read text]} as the assembly saw them; candidates: {(library, pair): (text of read 2 * pair, of read 2 * pair + 1)}, an N
+    where a base is masked; contigs: [(gap, text)], the step's list after the first pick (a tombstone: empty text); open_gaps: the gaps with
+    pick word 0; assemble(gap, [read text]) -> [contig text] over every (k, kv); pick(gap, [contig text]) -> closed?.
+    -> (rounds, rounds_run): per round {"hits": {gap: set of (library, pair)} (H), "new": {gap: set} (S_r - S_(r-1)), "grown": [gap],
+    "reads": {gap: [(library, pair)]} (S_r of the grown gaps in pool order), "contigs": [(gap, text)] (appended), "closed": [gap],
+    "gated": bool}; rounds_run counts the first round that grew no gap."""
+    open_now = set(open_gaps)
+    cand_kmers = {key: _canonical_kmers(a, k) | _canonical_kmers(b, k) for key, (a, b) in candidates.items()}
+    seen = {}                               # S: per gap, every pair recruited so far
+    last, rounds, rounds_run = list(contigs), [], None
+    for r in range(1, max_rounds + 1):
+        if rounds_run is not None:
+            rounds.append({"hits": {}, "new": {}, "grown": [], "reads": {}, "contigs": [], "closed": [], "gated": True})
+            continue
+        table = {}
+        for g, text in last:
+            if g in open_now and len(text) >= k:
+                for w in _canonical_kmers(text, k):
+                    table.setdefault(w, set()).add(g)
+        hits = {}
+        for key, ws in cand_kmers.items():
+            for w in ws & table.keys():
+                for g in table[w]:
+                    hits.setdefault(g, set()).add(key)
+        new = {g: h - seen.get(g, set()) for g, h in hits.items()}
+        new = {g: v for g, v in new.items() if v}
+        for g, v in new.items():
+            seen.setdefault(g, set()).update(v)
+        grown = sorted(g for g in new if g in open_now)
+        reads, last, closed = {}, [], []
+        for g in grown:
+            reads[g] = sorted(seen[g])
+            rows = list(pools.get(g, ())) + [t for key in reads[g] for t in candidates[key]]
+            mine = list(assemble(g, rows))
+            last += [(g, t) for t in mine]
+            if pick(g, mine):
+                closed.append(g)
+        open_now -= set(closed)
+        rounds.append({"hits": hits, "new": new, "grown": grown, "reads": reads, "contigs": last, "closed": closed, "gated": False})
+        if not grown:
+            rounds_run = r
+    return rounds, (max_rounds if rounds_run is None else rounds_run)

@@ -1268,6 +1268,32 @@ int gf_contigs_append_dev(gf_ctx* ctx, void* d_contigs, void* d_n_contigs, size_
                           const void* d_src_contigs, const void* d_src_n, size_t src_cap, const void* d_src_seq, const void* d_src_seq_len,
                           size_t src_seq_cap, void* d_stats);
 
+/* ---- recruitment rounds 2 and later (csrc/round_n.hip; DESIGN.md §10 "Repeated rounds"): the round above run again with the contigs the round
+ * before appended, until a round grows no gap.  Every round has a statistics block u32[16] of its own (zeroed by the caller before the step):
+ * words 0-11 as above, [12] pairs new in this round (summed over the gaps open at its start), [13] gaps open at its start whose recruits grew,
+ * [14] 1 when the round was gated.  THE GATE: every call here takes d_live, a device u32 — the round before's word [13], for round 2 round 1's
+ * word [5].  Where *d_live == 0 every kernel of the call returns at once and no caller's buffer is written (gf_round_carry_dev alone then sets
+ * [8] = *d_n_contigs and [14] = 1 and zeroes d_n_pairs_live).  d_live_or_null == NULL: not gated. */
+/* gf_contig_kmer_table_dev over the contigs [*d_first, min(*d_n_contigs, contig_cap)) (d_first: device u32; at or beyond the end: an empty
+ * table).  Same slots, same d_stats words [0] and [1]; the table is cleared by the call (unless gated). */
+int gf_contig_kmer_table_from_dev(gf_ctx* ctx, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
+                                  const void* d_gap_best, size_t n_gaps, int k, const void* d_first, void* d_table, int log2_slots, void* d_stats,
+                                  const void* d_live_or_null);
+/* before a round recruits: the distinct valid keys of the round before (d_keys_sorted and d_work as its pools call left them; d_prev_stats:
+ * its block) go to the front of d_keys in sorted order, the rest of d_keys is filled with 0xFF, their per-gap counts go to d_prev_cnt
+ * (u32[n_gaps]) and their number becomes d_stats[2], so that gf_recruit_by_contigs_dev appends behind them.  d_n_pairs -> d_n_pairs_live:
+ * u32[n_lib] candidate counts, copied (gated: zeroed) — the recruitment of the round reads d_n_pairs_live + l as its d_n_pairs.
+ * d_snapshot_or_null: u64[key_cap], receives the same keys (the round before's recruits, for a caller that keeps read ids). */
+int gf_round_carry_dev(gf_ctx* ctx, void* d_keys, const void* d_keys_sorted, size_t key_cap, size_t n_gaps, const void* d_work, void* d_prev_cnt,
+                       const void* d_prev_stats, void* d_stats, const void* d_n_contigs, const void* d_n_pairs, void* d_n_pairs_live, int n_lib,
+                       void* d_snapshot_or_null, const void* d_live);
+/* gf_round2_pools_dev with d_prev_cnt (d_work: gf_round2_work_words): a gap gets a pool — its round-1 rows, then ALL its recruited pairs so
+ * far in (library, pair) order — only when d_gap_best == 0 and its count exceeds d_prev_cnt; every other gap gets an empty pool, whatever
+ * keys it has.  d_stats [3] [4] [5] [6-7] [11] as above (counts over all gaps, closed ones included), [12], [13]. */
+int gf_round_pools_dev(gf_ctx* ctx, void* d_keys, void* d_keys_sorted, size_t key_cap, const void* const* d_lib_reads, int n_lib, int read_len,
+                       const void* d_asm_pool, const void* d_asm_off, const void* d_gap_best, size_t n_gaps, const void* d_prev_cnt, void* d_work,
+                       void* d_rows, void* d_pool, size_t pool_cap, void* d_stats, const void* d_live_or_null);
+
 /* ---- the reference's rescue round (assemble_gaps.py:166-217 run_collect_high_quality_unmap_to_contig_reads: `bwa mem` of a gap's high-quality
  * reads against its merged contigs, reads that align CLIPPED to at least two contigs are bridges), for ALL gaps of a round in one host call (no GPU
  * work; ctx may be NULL).  Contigs of gap g = texts [ctg_set_off[g], ctg_set_off[g+1]) of ctg_text (text c at ctg_off[c] .. ctg_off[c+1]), reads
