@@ -57,6 +57,8 @@ MX_NEW_RECORDS, MX_EDGE_RECORDS, MX_WORDS = 14, 15, 16
 R2_KMERS, R2_TAB_FULL, R2_HITS, R2_UNIQUE, R2_TRIED, R2_WITH, R2_ROWS, R2_FIRST, R2_APPEND_ERR, R2_N2, R2_POOL_OVF = 0, 1, 2, 3, 4, 5, 6, 8, 9, 10, 11
 R2_NEW, R2_GROWN, R2_GATED = 12, 13, 14          # rounds 2 and later (round_n.hip): one block of R2_WORDS per round
 R2_WORDS, R2_MAX_LIBS = 16, 16
+# the closing pools (closing_pools.hip, u32[CP_WORDS] statistics): rows needed (u64), gaps with a pool, recruited rows copied, overflow
+CP_ROWS, CP_GAPS, CP_RECRUITED, CP_OVF, CP_WORDS, CP_NO_ID = 0, 2, 3, 4, 8, 0xFFFFFFFF
 
 # the rescue round (rescue.hip, u32[16] statistics): marker of the bridge records (k = kv = RESCUE_MARK), the words of the statistics
 RESCUE_MARK = 0xFFFF
@@ -333,12 +335,15 @@ def lib():
         "gf_fill_pileup_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
         "gf_fill_polish_gapped_dev": (i32, [vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, sz, vp]),
         "gf_fill_pairs_dev": (i32, [vp, vp, vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
+        "gf_fill_pairs_split_dev": (i32, [vp, vp, vp, vp, vp, sz, vp, i32, vp, vp, sz, vp, vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp]),
         "gf_fill_pairs_anchored_dev": (i32, [vp, vp, vp, sz, i32, vp, vp, sz, vp, vp, vp, i32, i32, vp, vp, sz, vp, vp, sz, i32, i32, i32, i32, vp, vp, vp]),
         "gf_gap_span_dev": (i32, [vp, vp, vp, sz, i32, i32, i32, i32, i32, i32, vp, vp]),
         "gf_contigs_append_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp, vp, sz, vp]),
         "gf_contig_kmer_table_from_dev": (i32, [vp, vp, vp, sz, vp, vp, sz, i32, vp, vp, i32, vp, vp]),
         "gf_round_carry_dev": (i32, [vp, vp, vp, sz, sz, vp, vp, vp, vp, vp, vp, vp, i32, vp, vp]),
         "gf_round_pools_dev": (i32, [vp, vp, vp, sz, vp, i32, i32, vp, vp, vp, sz, vp, vp, vp, vp, sz, vp, vp]),
+        "gf_closing_pools_work_words": (sz, [sz]),
+        "gf_closing_pools_dev": (i32, [vp, vp, vp, sz, vp, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, sz, vp, vp, vp, sz, vp, vp, vp, vp]),
         "gf_rescue_work_bytes": (sz, [sz, sz, sz, i32]),
         "gf_rescue_reset_dev": (i32, [vp, vp, sz, sz, sz, i32, vp]),
         "gf_rescue_hq_keys_dev": (i32, [vp, vp, vp, sz, vp, sz, i32, sz, vp, sz, sz, i32, vp]),

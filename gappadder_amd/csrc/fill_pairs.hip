@@ -35,10 +35,23 @@ struct PsParams {
     PlPlaceArgs place;
     FillRoundArgs round;         // (pool_off, pool_rows: the library's pool)
     const uint32_t* ids;
+    const uint64_t* head_off;    // NULL, or offsets whose differences are the rows at the head of every slice that are ordered by (mate side, pair)
     int64_t lo, hi;              // is_mean -/+ z * is_sd
     uint32_t* scratch;
     gf_fill_pairs* out;
 };
+
+// the row of read `id` in ids[a, b) — ordered by (mate side, pair), or by_id: by read id — or b
+__device__ __forceinline__ uint64_t ps_find(const uint32_t* ids, uint64_t a, uint64_t b, uint32_t id, bool by_id) {
+    const uint64_t end = b;
+    const uint32_t want = by_id ? id : ps_order(id);
+    while (a < b) {
+        const uint64_t m = a + ((b - a) >> 1);
+        if ((by_id ? ids[m] : ps_order(ids[m])) < want) a = m + 1;
+        else b = m;
+    }
+    return a < end && ids[a] == id ? a : end;
+}
 
 __global__ __launch_bounds__(PL_THREADS) void fill_pairs_kernel(PsParams P) {
     __shared__ uint32_t s_idx[PS_IDX_WORDS];
@@ -112,17 +125,15 @@ __global__ __launch_bounds__(PL_THREADS) void fill_pairs_kernel(PsParams P) {
         {
             uint32_t c_complete = 0, c_placed = 0, c_proper = 0, c_mis = 0, c_in = 0, c_short = 0, c_long = 0, c_span = 0;
             long long sum = 0;
+            // [r0, rh): ordered by (mate side, pair); [rh, r1): pairs appended behind them, ordered by read id (a closing pool's recruits)
+            const uint64_t rh = P.head_off ? min(r1, r0 + (P.head_off[g + 1] - P.head_off[g])) : r1;
             for (uint64_t i = r0 + t; i < r1; i += PL_THREADS) {
                 const uint32_t id = P.ids[i];
                 if (id & 1u) continue;
-                const uint32_t want = ps_order(id ^ 1u);
-                uint64_t a = r0, b = r1;         // the first row of the slice whose order is not below `want`
-                while (a < b) {
-                    const uint64_t m = a + ((b - a) >> 1);
-                    if (ps_order(P.ids[m]) < want) a = m + 1;
-                    else b = m;
-                }
-                if (a >= r1 || P.ids[a] != (id ^ 1u)) continue;
+                if (i >= rh && ps_find(P.ids, r0, rh, id, false) < rh) continue;       // a read met twice counts at its first row
+                uint64_t a = ps_find(P.ids, r0, rh, id ^ 1u, false);
+                if (a >= rh) a = ps_find(P.ids, rh, r1, id ^ 1u, true);                // (the mate's first row as well)
+                if (a >= r1) continue;
                 ++c_complete;
                 const uint32_t w0 = P.scratch[i], w1 = P.scratch[a];
                 if (!(w0 & w1 & PS_PLACED)) continue;
@@ -226,6 +237,15 @@ extern "C" int gf_fill_pairs_dev(gf_ctx* ctx, const void* d_pool_packed, const v
                                  size_t pool_cap_rows, int read_len, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
                                  const void* d_gap_best, const void* d_ctg_pick_or_null, int anchor_long, int anchor_short, int seed, int max_mismatch,
                                  int min_overlap, int is_mean, int is_sd, int z, void* d_place_scratch, void* d_rec, void* d_stats) {
+    return gf_fill_pairs_split_dev(ctx, d_pool_packed, d_nmask_or_null, d_pool_off, d_pool_read_ids, pool_cap_rows, nullptr, read_len, d_contigs,
+                                   d_n_contigs, contig_cap, d_seq, d_gap_best, d_ctg_pick_or_null, anchor_long, anchor_short, seed, max_mismatch,
+                                   min_overlap, is_mean, is_sd, z, d_place_scratch, d_rec, d_stats);
+}
+
+extern "C" int gf_fill_pairs_split_dev(gf_ctx* ctx, const void* d_pool_packed, const void* d_nmask_or_null, const void* d_pool_off, const void* d_pool_read_ids,
+                                 size_t pool_cap_rows, const void* d_head_off_or_null, int read_len, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
+                                 const void* d_gap_best, const void* d_ctg_pick_or_null, int anchor_long, int anchor_short, int seed, int max_mismatch,
+                                 int min_overlap, int is_mean, int is_sd, int z, void* d_place_scratch, void* d_rec, void* d_stats) {
     if (pool_cap_rows && (!d_pool_read_ids || !d_place_scratch)) return GF_E_INVAL;
     PsParams P;
     memset(&P, 0, sizeof(P));
@@ -237,6 +257,7 @@ extern "C" int gf_fill_pairs_dev(gf_ctx* ctx, const void* d_pool_packed, const v
     const int rc = fill_round_setup(ctx, in, own, GF_PS_WORDS, 3, &P.round, &blocks);   // 3: workgroups the static LDS lets a CU hold
     if (rc || !blocks) return rc;
     P.ids = (const uint32_t*)d_pool_read_ids;
+    P.head_off = (const uint64_t*)d_head_off_or_null;
     P.lo = (int64_t)is_mean - (int64_t)z * is_sd;
     P.hi = (int64_t)is_mean + (int64_t)z * is_sd;
     P.scratch = (uint32_t*)d_place_scratch;

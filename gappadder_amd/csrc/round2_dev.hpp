@@ -38,7 +38,7 @@ struct LibRows {
 
 __device__ __forceinline__ bool r2_acgt(char c) { return c == 'A' || c == 'C' || c == 'G' || c == 'T'; }
 
-static __device__ void r2_insert(R2Slot* tab, uint32_t log2, K128 v, uint32_t gap, uint32_t* full) {
+[[maybe_unused]] static __device__ void r2_insert(R2Slot* tab, uint32_t log2, K128 v, uint32_t gap, uint32_t* full) {
     const uint32_t mask = (uint32_t)((1ull << log2) - 1);
     uint32_t pos = hash_kmer(v, (int)log2);
     uint64_t probes = 0;

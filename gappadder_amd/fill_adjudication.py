@@ -199,7 +199,7 @@ def adjudicate_gaps(alts, contigs, flanks, best, reads_of, L, anchors=(30, 15), 
 
 def adjudication_of_results(pipe, res, nmask=None):
     """The twin on a step's Results (fetch(pools=True)): what Results.adjudication and .adj_stats must equal."""
-    reads_of = lambda g: FR.pool_reads(res.pool_off, res.pool_rows, g, pipe.L, nmask)[2]
+    reads_of = lambda g: FR.fill_reads(res, g, pipe.L, nmask)
     return adjudicate_gaps(res.alts, FA.contigs_of_results(res), pipe.gf.flanks, res.best, reads_of, pipe.L, pipe.anchors, *pipe.adj.params)
 
 
@@ -240,16 +240,16 @@ class FillAdjudication(FR.FillRound):
         text, lens = flank_context(p.gf.flanks, self.params[3])
         self.d_text = torch.from_numpy(text.reshape(-1)).to(p.dev)
         self.d_lens = torch.from_numpy(lens.reshape(-1).view(np.int16)).to(p.dev)
-        self.d_scratch = torch.zeros(max(1, p.merged_cap if p.need_merge else p.lib_cap), dtype=torch.int32, device=p.dev)
+        self.d_scratch = torch.zeros(max(1, self.pool_cap()), dtype=torch.int32, device=p.dev)
         self.d_rec = p._u8(max(1, p.n_gaps) * B.FILL_ADJ.itemsize)
         self.d_stats = torch.zeros(B.AJ_WORDS, dtype=torch.int32, device=p.dev)
 
     def _launch(self, d_nmask):
         """On the pool the step assembled, behind the alternatives round (whose records it reads) and the other after-pick rounds."""
         p = self.p
-        if p.alts.d_rec is None or p.asm_rows > self.d_scratch.numel():
+        if p.alts.d_rec is None or self.pool_cap() > self.d_scratch.numel():
             raise RuntimeError("adjudicate: the alternatives round has no records, or the pool outgrew the scratch")
-        p._chk(p.lib.gf_fill_adjudicate_dev(p.h, p.asm_ptr, d_nmask, p.asm_off, p.asm_rows, p.L, p.d_ctg.data_ptr(), p.ap, p.contig_cap,
+        p._chk(p.lib.gf_fill_adjudicate_dev(p.h, *self.pool_args(d_nmask), p.L, p.d_ctg.data_ptr(), p.ap, p.contig_cap,
                                             p.d_seq.data_ptr(), p.d_best.data_ptr(), *p.anchor_pair, p.alts.d_rec.data_ptr(), self.d_text.data_ptr(),
                                             self.d_lens.data_ptr(), self.d_scratch.data_ptr(), *self.params, self.d_rec.data_ptr(),
                                             self.d_stats.data_ptr()), "gf_fill_adjudicate_dev")

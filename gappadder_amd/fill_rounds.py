@@ -11,7 +11,7 @@ _LUT = np.full(256, 4, dtype=np.uint8)          # A, C, G, T -> 0..3; any other 
 for _i, _c in enumerate(b"ACGT"):
     _LUT[_c] = _i
 
-# why a round that reads the step's pools does not run with second_round (Pipeline's refusals)
+# why a round that reads the step's pools does not run with second_round (Pipeline's refusals) unless the step rebuilds the closing pools
 NOT_WITH_SECOND_ROUND = {"read_support": "the support is defined on the step's pool", "polish": "the polish is defined on the step's pool",
                          "pileup": "the pile-up is defined on the step's pool",
                          "pair_span": "the pairs are looked up in the step's pools",
@@ -44,6 +44,28 @@ def pool_reads(off, rows, g, L, nmask=None):
     from .read_support import codes_of_rows
     r0, r1 = int(off[g]), int(off[g + 1])
     return r0, r1, codes_of_rows(rows[r0:r1], L, None if nmask is None else nmask[r0:r1])
+
+
+def fill_pool(res, nmask=None):
+    """(offsets, rows, N-mask rows or None) of the pool the after-pick rounds of a step read: the closing pool when the Results carry one
+    (Pipeline(closing_pools=True), with its own masks), else the step's pool with the caller's masks."""
+    if getattr(res, "closing_pool_off", None) is not None:
+        return res.closing_pool_off, res.closing_pool_rows, res.closing_pool_nmask
+    return res.pool_off, res.pool_rows, nmask
+
+
+def fill_lib_pool(res, l, nmask=None):
+    """fill_pool for library l's own pool: (offsets, rows, read ids, N-mask rows or None)."""
+    if getattr(res, "closing_lib_pool_off", None) is not None:
+        return res.closing_lib_pool_off[l], res.closing_lib_pool_rows[l], res.closing_lib_pool_ids[l], \
+            None if res.closing_lib_pool_nmask is None else res.closing_lib_pool_nmask[l]
+    return res.lib_pool_off[l], res.lib_pool_rows[l], res.lib_pool_ids[l], nmask
+
+
+def fill_reads(res, g, L, nmask=None):
+    """(codes, valid) of gap g's rows of fill_pool(res, nmask)."""
+    off, rows, nm = fill_pool(res, nmask)
+    return pool_reads(off, rows, g, L, nm)[2]
 
 
 def skip_flag(contig, f_long, f_non_acgt):
@@ -85,6 +107,17 @@ class FillRound:
         p = self.p
         return (p.d_ctg.data_ptr(), p.ap, p.contig_cap, p.d_seq.data_ptr(), p.d_best.data_ptr(),
                 p.d_ctg_pick.data_ptr() if p.per_contig else None) + (p.anchor_pair if not p.per_contig else (0, 0))
+
+    def pool_args(self, d_nmask):
+        """(pool, N masks or None, offsets, capacity in rows): the four ABI arguments of the pool a round reads — the closing pool where
+        the step builds one (second_round.ClosingPools), else the pool the step assembled with the masks assemble() was given."""
+        p = self.p
+        return p.closing.pool_args() if p.closing is not None else (p.asm_ptr, d_nmask, p.asm_off, p.asm_rows)
+
+    def pool_cap(self):
+        """Rows of the array pool_args() names: what a round sizes its scratch per row by."""
+        p = self.p
+        return p.closing.cap if p.closing is not None else p.merged_cap if p.need_merge else p.lib_cap
 
     def enqueue(self, d_nmask=None):
         """After the last pick of the step, in the order support, polish, pile-up, pairs.  d_nmask: the N masks assemble() was given."""

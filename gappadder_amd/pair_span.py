@@ -3,7 +3,7 @@ placed, without gaps in the alignment, on the gap's winning contig, the two mate
 per (library, gap) says how the pairs' inserts and their physical coverage of the fill fit the library's insert size (gf_fill_pairs,
 _lib.FILL_PAIRS; gf_fill_pairs_dev, csrc/fill_pairs.hip) at the end of the step.  The reference collects reads by this very statistic
 (collect_reads_for_gaps.py:5-6: mean -/+ 3 sd) and never applies it to its result.  Results.pairs ([n_lib, n_gaps]) and .pair_stats (a
-dictionary per library); single rank; not with second_round, whose pool is not the step's.  Nothing else of the step changes.
+dictionary per library); single rank; with second_round only on the closing pools (closing_pools: each library's closing pool).  Nothing else of the step changes.
 
 The definition is the host twin below (pair_span_host).  For a closed gap, one library, the winning contig c of n bases
 (stored orientation; always the UNPOLISHED one):
@@ -11,7 +11,7 @@ The definition is the host twin below (pair_span_host).  For a c
               word's pick is the same MISMATCH: zero record, counted, fetch() raises;
   placement   of a row: the polish's rule word for word (polish.placements: seed, max_mismatch, min_overlap, L // seed > max_mismatch):
               PLACED at (strand, diagonal d), AMBIGUOUS or unplaced;
-  pairs       over the rows of the LIBRARY's pool for the gap (read id = 2 * pair + mate, every read at most once): ids r and r ^ 1
+  pairs       over the rows of the LIBRARY's pool for the gap (read id = 2 * pair + mate; a read with two rows — a closing pool may hold one among the step's rows and among the recruits — counts at its first): ids r and r ^ 1
               both present: a complete pair; both rows PLACED: a placed pair; the mates on opposite strands and the strand-0 mate's
               diagonal d_f <= the strand-1 mate's d_r: proper (FR), insert = d_r + L - d_f; every other placed pair: misoriented;
   classes     lo = is_mean - z * is_sd, hi = is_mean + z * is_sd: in range iff lo < insert < hi (strict, collect_reads_for_gaps.py:243),
@@ -53,8 +53,10 @@ def pair_span_host(reads, ids, contig, b0, b1, is_mean, is_sd, seed=SEED, max_mi
     L = codes.shape[1] if len(codes) else None
     s, mm_max, mo, zz = check_params(L if L is not None else 1 << 20, seed, max_mismatch, min_overlap, z, is_sd)
     ids = [int(r) for r in ids]
-    row_of = {r: i for i, r in enumerate(ids)}
-    assert len(ids) == len(codes) and len(row_of) == len(ids), "one id per row, every read at most once"
+    row_of = {}
+    for i, r in enumerate(ids):         # (a library's closing pool may hold a read twice, among the step's rows and among the recruits: its first row)
+        row_of.setdefault(r, i)
+    assert len(ids) == len(codes), "one id per row"
     b0, b1 = int(b0), max(int(b0), int(b1))
     n = len(contig)
     rec = np.zeros((), dtype=B.FILL_PAIRS)
@@ -119,8 +121,7 @@ def pair_span_of_results(res, flanks, L, libs, seed=SEED, max_mismatch=MAX_MISMA
     stats = [dict.fromkeys(STAT_KEYS, 0) for _ in libs]
     for l, (is_mean, is_sd) in enumerate(libs):
         check_params(L, seed, max_mismatch, min_overlap, z, is_sd)
-        off, rows, ids = res.lib_pool_off[l], res.lib_pool_rows[l], res.lib_pool_ids[l]
-        nm = None if nmasks is None else nmasks[l]
+        off, rows, ids, nm = FR.fill_lib_pool(res, l, None if nmasks is None else nmasks[l])
         for g, contig, body in FR.closed_fills(res, flanks):
             if body is None:
                 stats[l]["mismatches"] += 1
@@ -162,7 +163,7 @@ class PairSpan(FR.FillRound):
         self.plane = max(1, p.n_gaps) * B.FILL_PAIRS.itemsize
         self.d_rec = p._u8(len(p.libs) * self.plane)
         self.d_stats = torch.zeros(len(p.libs) * B.PS_WORDS, dtype=torch.int32, device=p.dev)
-        self.d_scratch = torch.zeros(p.lib_cap, dtype=torch.int32, device=p.dev)
+        self.d_scratch = torch.zeros(self.lib_pool_cap(), dtype=torch.int32, device=p.dev)
         self.d_nm = torch.zeros(p.lib_cap * self.nmw, dtype=torch.int32, device=p.dev) if any(lb.d_nmask is not None for lb in p.libs) else None
 
     def masks_of(self, l):
@@ -175,14 +176,27 @@ class PairSpan(FR.FillRound):
                                         lb.d_pool_off.data_ptr() + 8 * p.n_gaps, p.lib_cap, self.d_nm.data_ptr()), "gf_gather_rows_dev")
         return self.d_nm.data_ptr()
 
+    def lib_pool_args(self, l):
+        """(pool, N masks or None, offsets, read ids, capacity in rows, head offsets or None) of library l's pool as gf_fill_pairs_split_dev
+        takes them: the library's closing pool where the step builds one (second_round.ClosingPools; its head: the library's own pool), else
+        the library's own pool of the step, ordered by (mate side, pair) throughout."""
+        p, lb = self.p, self.p.libs[l]
+        if p.closing is not None:
+            return p.closing.lib_pool_args(l)
+        return (p.pool_ptr[l], self.masks_of(l), lb.d_pool_off.data_ptr(), lb.d_ids.data_ptr(), p.lib_cap, None)
+
+    def lib_pool_cap(self):
+        p = self.p
+        return p.closing.lib_cap if p.closing is not None else p.lib_cap
+
     def _launch(self, d_nmask):
         """One launch per library (after the read-support and polish rounds), on that library's pool, read ids and — gathered by the
         ids, so d_nmask, the masks of the step's merged pool, is not used — N masks."""
         p = self.p
         for l, lb in enumerate(p.libs):
-            p._chk(p.lib.gf_fill_pairs_dev(p.h, p.pool_ptr[l], self.masks_of(l), lb.d_pool_off.data_ptr(), lb.d_ids.data_ptr(), p.lib_cap, p.L,
+            p._chk(p.lib.gf_fill_pairs_split_dev(p.h, *self.lib_pool_args(l), p.L,
                                            *self.shared_args(), *self.params[:3], lb.is_mean, lb.is_sd, self.params[3], self.d_scratch.data_ptr(),
-                                           self.d_rec.data_ptr() + l * self.plane, self.d_stats.data_ptr() + 4 * l * B.PS_WORDS), "gf_fill_pairs_dev")
+                                           self.d_rec.data_ptr() + l * self.plane, self.d_stats.data_ptr() + 4 * l * B.PS_WORDS), "gf_fill_pairs_split_dev")
             if p.anchored is not None:        # (pair_anchors.py: it reads this library's placement words before the next library's replace them)
                 p.anchored.launch_library(l)
 

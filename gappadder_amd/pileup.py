@@ -208,7 +208,7 @@ def pileup_of_results(res, flanks, L, seed=SEED, max_mismatch=MAX_MISMATCH, min_
         if body is None:
             stats["mismatches"] += 1
             continue
-        reads = FR.pool_reads(res.pool_off, res.pool_rows, g, L, nmask)[2]
+        reads = FR.fill_reads(res, g, L, nmask)
         entries, out[g] = pileup_host(reads, contig, body[0], body[1], seed, max_mismatch, min_overlap, min_depth, min_agree, track=track)
         if entries is not None:
             tracks[int(g)] = entries
@@ -246,7 +246,7 @@ class FillPileup(FR.FillRound):
     def _launch(self, d_nmask):
         """On the pool the step assembled (after the polish)."""
         p = self.p
-        p._chk(p.lib.gf_fill_pileup_dev(p.h, p.asm_ptr, d_nmask, p.asm_off, p.asm_rows, p.L, *self.shared_args(), *self.params,
+        p._chk(p.lib.gf_fill_pileup_dev(p.h, *self.pool_args(d_nmask), p.L, *self.shared_args(), *self.params,
                                         self.d_rec.data_ptr(), self.d_track.data_ptr() if self.track else None, self.track_cap,
                                         self.d_stats.data_ptr()), "gf_fill_pileup_dev")
 

@@ -19,6 +19,7 @@ What the reference does with files between processes —
     gf_contig_kmer_table_dev + gf_recruit_by_contigs_dev       second assembly round for the gaps still open (second_round.py):
       + gf_round2_pools_dev + gf_assemble_multi_dev            both-unmapped pairs recruited by the round-1 contigs' k-mers, pools
       + gf_contigs_append_dev + gf_pick_*_from_dev             = round-1 rows + recruits, assembled and picked again
+    gf_closing_pools_dev                                       behind the last of those rounds: the pool every closed gap was closed from, for the rounds that read the fills' pools (closing_pools)
     gf_rescue_hq_keys_dev + gf_rescue_bridges_dev              rescue round for the gaps still open after the merge pick (rescue_round.py):
       + gf_merge_rescue_dev + gf_pick_*_from_dev               high-quality reads clipped at two contigs join the own contigs, merge, pick at 15
     gf_pick_joins_dev                                          the open gaps whose flanks overlap on a contig that runs through the junction (flank_joins.py)
@@ -95,6 +96,8 @@ class Results:
     the merge round and of the optional rounds are None unless the round ran."""
     merge = rescue = rescue_first = round2 = round2_first = round2_reads = recruit_rounds = recruit_rounds_run = recruit_reads = extended = ext = ext_bases = support = support_stats = None
     polish = polish_bases = polish_stats = pairs = pair_stats = lib_pool_off = lib_pool_rows = lib_pool_ids = None
+    closing_pools = closing_pool_off = closing_pool_rows = closing_pool_nmask = closing_pool_ids = closing_pool_lib = None
+    closing_lib_pool_off = closing_lib_pool_rows = closing_lib_pool_ids = closing_lib_pool_nmask = None
     pair_anchors = pair_anchor_stats = lib_taghits = gap_span = gap_span_stats = pileup = pileup_track = pileup_stats = joins = join_stats = alts = alt_contigs = alt_stats = adjudication = adj_stats = None
 
 
@@ -116,7 +119,7 @@ class Pipeline:
                  span_shift=1000, span_min_pairs=8, pileup=False, pileup_seed=16, pileup_max_mismatch=4, pileup_min_overlap=48, pileup_min_depth=3,
                  pileup_min_agree=80, pileup_track=True, flank_joins=False, join_max_overlap=256, join_min_context=30, join_max_mismatch=2,
                  alternatives=False, alt_max_dist=16, adjudicate=False, adj_seed=16, adj_max_mismatch=4, adj_min_overlap=48, adj_context=None,
-                 adj_min_votes=3, adj_ratio=2):
+                 adj_min_votes=3, adj_ratio=2, closing_pools=False):
         """gf: a GapFill whose gaps (and flanks, when a library is screened) are set.  k_pairs: [(k, k_velvet)] of
         assemble_gaps.py:87-122.  The screen runs at the SMALLEST k of the list: a read that shares a 51-mer with a flank shares
         its 31-mers too, so this is the superset every assembly k needs (the reference recruits once, then assembles at every k).
@@ -177,10 +180,15 @@ class Pipeline:
         with alternatives): last of the after-pick rounds, the pool of every CONTESTED gap is placed on the winner's and on the rival's
         fill, each between adj_context bases of the flanks (default: the read length), and every row votes for the one it fits strictly
         better: KEEP, SWITCH or UNDECIDED per gap (Results.adjudication, gf_fill_adj per gap; .adj_stats; adjudicated_sequences).
-        Advice only: the picks, the contigs and picked_sequences stay as they are."""
+        Advice only: the picks, the contigs and picked_sequences stay as they are.
+        closing_pools (second_round.ClosingPools; only with second_round): behind the last recruitment round's pick the closing pool of
+        every closed gap is built — the rows the step's first assembly saw, then every pair recruited for the gap — and read_support,
+        polish, pileup, pair_span (one pool per library, with read ids) and adjudicate, refused beside second_round without it, run on
+        that pool (Results.closing_pools; with fetch(pools=True) .closing_pool_off, _rows, _nmask, _ids, _lib and .closing_lib_pool_*)."""
         # what the options exclude, before anything touches gf or the library
         single_rank = int(world) == 1 and not force_exchange
         k_round2 = min([int(a) for a, _ in k_pairs if 16 <= int(a) <= 64], default=None)
+        own_pools = second_round and not closing_pools      # the second round's pools are not rebuilt for the rounds that read the fills' pools
         for bad, why in ((anchor_mode not in PICKS, "anchor_mode %r: 'exact', 'align' or 'gapped'" % (anchor_mode,)),
                          (rescue_round and not merge_in_step, "rescue_round needs merge_in_step: the reads are aligned to the merged contigs"),
                          (rescue_round and not single_rank, "rescue_round runs on a single rank"),
@@ -191,12 +199,13 @@ class Pipeline:
                          (isinstance(recruit_rounds, bool) or not isinstance(recruit_rounds, int) or not 1 <= recruit_rounds <= 16,
                           "recruit_rounds %r: an integer 1..16" % (recruit_rounds,)),
                          (not second_round and recruit_rounds != 1, "recruit_rounds repeats the second round: it needs second_round"),
-                         *FR.refusals("read_support", read_support, single_rank, second_round),
+                         (closing_pools and not second_round, "closing_pools needs second_round: it rebuilds the pools the recruitment rounds closed gaps from"),
+                         *FR.refusals("read_support", read_support, single_rank, own_pools),
                          (read_support and support_k is None and k_round2 is None, "read_support needs support_k, or a k in 16..64 among k_pairs"),
-                         *FR.refusals("polish", polish, single_rank, second_round),
+                         *FR.refusals("polish", polish, single_rank, own_pools),
                          (polish_indels and not polish, "polish_indels needs polish: it is a mode of the polish round"),
-                         *FR.refusals("pileup", pileup, single_rank, second_round),
-                         *FR.refusals("pair_span", pair_span, single_rank, second_round),
+                         *FR.refusals("pileup", pileup, single_rank, own_pools),
+                         *FR.refusals("pair_span", pair_span, single_rank, own_pools),
                          (pair_anchors and not pair_span, "pair_anchors needs pair_span: it reads the pair span's placements"),
                          *FR.refusals("pair_anchors", pair_anchors, single_rank, second_round),
                          (gap_span and not single_rank, "gap_span runs on a single rank: the sums are additive over ranks, and that reduction is left out"),
@@ -205,7 +214,7 @@ class Pipeline:
                          (alternatives and anchor_mode in PICKS and anchor_mode != "exact", "alternatives works with the exact anchors: not with anchor_mode %r" % (anchor_mode,)),
                          (alternatives and not single_rank, "alternatives runs on a single rank"),
                          (adjudicate and not alternatives, "adjudicate needs alternatives: it reads the alternatives round's records"),
-                         *FR.refusals("adjudicate", adjudicate, single_rank, second_round),
+                         *FR.refusals("adjudicate", adjudicate, single_rank, own_pools),
                          (extended_fill and not single_rank, "extended_fill runs on a single rank"),
                          (extended_fill and len(k_pairs) > B.EXT_MAX_PAIRS, "extended_fill: at most %d (k, kv) pairs" % B.EXT_MAX_PAIRS)):
             if bad:
@@ -214,6 +223,7 @@ class Pipeline:
         self.per_contig = PICKS[anchor_mode][3]      # the mode's picks leave a selection per contig and two statistics words
         # the optional rounds, in the order the step runs them; None: off
         self.round2 = R2.SecondRound(self, k_round2, recruit_rounds) if second_round else None
+        self.closing = R2.ClosingPools(self, per_library=pair_span) if closing_pools else None
         self.rescue = RS.RescueRound(self) if rescue_round else None
         self.joins = FJ.FlankJoins(self, join_max_overlap, join_min_context, join_max_mismatch) if flank_joins else None
         self.alts = FA.FillAlternatives(self, alt_max_dist) if alternatives else None
@@ -629,6 +639,8 @@ class Pipeline:
         torch.cuda.synchronize()
         if self.round2 is not None:
             self.round2.prepare()
+        if self.closing is not None:
+            self.closing.prepare()
         if self.rescue is not None:
             self.rescue.prepare()
         if self.joins is not None:
@@ -771,6 +783,8 @@ class Pipeline:
             self.ext.enqueue()
         # (neither the rescue's nor the extension's launches change d_best after the rescue's pick; every round here reads the step's
         # contigs and picks and writes buffers of its own; the pair span runs per library, on the libraries' own pools, ids and masks)
+        if self.closing is not None:    # (the pool of every closed gap as its closing round assembled it: what the rounds below read)
+            self.closing.enqueue(d_nmask)
         for rnd in self.after_pick:
             rnd.enqueue(d_nmask)
 
@@ -853,6 +867,8 @@ class Pipeline:
             r.merge["gaps_closed_by_merging"] = int(((r.best != 0) & (idx >= r.merge["contigs_before"]) & (idx < end)).sum())
         if self.round2 is not None:
             self.round2.fetch(r)
+        if self.closing is not None and self.kk:
+            self.closing.fetch(r, pools)
         if self.joins is not None and self.kk:
             self.joins.fetch(r)
         if self.alts is not None and self.kk:

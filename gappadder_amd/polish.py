@@ -132,7 +132,7 @@ def polish_of_results(res, flanks, L, seed=SEED, max_mismatch=MAX_MISMATCH, min_
         if body is None:
             stats["mismatches"] += 1
             continue
-        reads = FR.pool_reads(res.pool_off, res.pool_rows, g, L, nmask)[2]
+        reads = FR.fill_reads(res, g, L, nmask)
         texts[int(g)], out[g] = polish_host(reads, contig, body[0], body[1], seed, max_mismatch, min_overlap, min_votes)
         f = int(out[g]["flags"])
         stats["skipped_long"] += bool(f & B.PL_F_LONG)
@@ -173,7 +173,7 @@ class FillPolish(FR.FillRound):
     def _launch(self, d_nmask):
         """On the pool the step assembled (after the read-support round)."""
         p = self.p
-        p._chk(p.lib.gf_fill_polish_dev(p.h, p.asm_ptr, d_nmask, p.asm_off, p.asm_rows, p.L, *self.shared_args(), *self.params,
+        p._chk(p.lib.gf_fill_polish_dev(p.h, *self.pool_args(d_nmask), p.L, *self.shared_args(), *self.params,
                                         self.d_rec.data_ptr(), self.d_bases.data_ptr(), self.base_cap, self.d_stats.data_ptr()), "gf_fill_polish_dev")
 
     def fetch(self, r):

@@ -281,7 +281,7 @@ def polish_gapped_of_results(res, flanks, L, seed=SEED, max_mismatch=MAX_MISMATC
         if body is None:
             stats["mismatches"] += 1
             continue
-        reads = FR.pool_reads(res.pool_off, res.pool_rows, g, L, nmask)[2]
+        reads = FR.fill_reads(res, g, L, nmask)
         texts[int(g)], out[g] = polish_gapped_host(reads, contig, body[0], body[1], seed, max_mismatch, min_overlap, min_votes, max_indel)
         add_stats(stats, out[g], len(texts[int(g)]))
     return out, texts, stats
@@ -313,7 +313,7 @@ class FillPolishGapped(POL.FillPolish):
 
     def _launch(self, d_nmask):
         p = self.p
-        p._chk(p.lib.gf_fill_polish_gapped_dev(p.h, p.asm_ptr, d_nmask, p.asm_off, p.asm_rows, p.L, *self.shared_args(), *self.params,
+        p._chk(p.lib.gf_fill_polish_gapped_dev(p.h, *self.pool_args(d_nmask), p.L, *self.shared_args(), *self.params,
                                                self.d_rec.data_ptr(), self.d_bases.data_ptr(), self.base_cap, self.d_stats.data_ptr()),
                "gf_fill_polish_gapped_dev")
 

@@ -177,7 +177,7 @@ def support_of_results(res, flanks, L, k, min_count=2, nmask=None):
         if body is None:
             stats["mismatches"] += 1
             continue
-        reads = FR.pool_reads(res.pool_off, res.pool_rows, g, L, nmask)[2]
+        reads = FR.fill_reads(res, g, L, nmask)
         out[g] = support_host(reads, contig, body[0], body[1], k, min_count)
         stats["gaps"] += 1
         stats["windows"] += int(out[g]["n_windows"])
@@ -199,7 +199,7 @@ class ReadSupport(FR.FillRound):
     def _launch(self, d_nmask):
         """On the pool the step assembled."""
         p = self.p
-        p._chk(p.lib.gf_fill_support_dev(p.h, p.asm_ptr, d_nmask, p.asm_off, p.asm_rows, p.L, *self.shared_args(), self.k, p.min_count,
+        p._chk(p.lib.gf_fill_support_dev(p.h, *self.pool_args(d_nmask), p.L, *self.shared_args(), self.k, p.min_count,
                                          self.d_rec.data_ptr(), self.d_stats.data_ptr()), "gf_fill_support_dev")
 
     def fetch(self, r):

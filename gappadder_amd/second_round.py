@@ -238,6 +238,142 @@ class SecondRound:
             r.recruit_reads = per
 
 
+class ClosingPools:
+    """Pipeline(closing_pools=True): after the last recruitment round's pick, the closing pool of every closed gap (DESIGN.md §27;
+    closing_pools_host is the definition) — the pool of the step's first assembly, then every pair recruited for the gap — built by
+    gf_closing_pools_dev from the keys the last pools call left in the second round's buffers, and handed to the after-pick rounds in
+    place of the step's pool (fill_rounds.FillRound.pool_args).  per_library: one more pool per library, from the library's own pool and
+    keys, with read ids (pair_span.PairSpan.lib_pool_args)."""
+
+    def __init__(self, pipe, per_library=False):
+        self.p, self.per_library = pipe, bool(per_library)
+        self.d_pool = None
+
+    def _alloc(self):
+        p = self.p
+        i32 = lambda n: torch.zeros(max(1, n), dtype=torch.int32, device=p.dev)
+        self.d_pool = p._u8(self.cap * p.rb + 64)
+        self.d_nm = i32(self.cap * self.nmw) if self.masks else None
+        self.d_ids = i32(self.cap) if p.keep_read_ids else None
+        self.d_lib = p._u8(self.cap) if p.keep_read_ids else None
+        if self.per_library:
+            n = len(p.libs)
+            self.d_lib_pool = [p._u8(self.lib_cap * p.rb + 64) for _ in range(n)]
+            self.d_lib_ids = [i32(self.lib_cap) for _ in range(n)]
+            self.d_lib_nm = [i32(self.lib_cap * self.nmw) if self.masks else None for _ in range(n)]
+
+    def prepare(self):
+        """Behind the second round's own sizing: the step runs until the merged pool and the largest library's fit their capacities."""
+        p = self.p
+        n_lib, n_gaps = len(p.libs), p.n_gaps
+        self.nmw = (p.L + 31) // 32
+        self.masks = any(lb.d_nmask is not None for lb in p.libs)
+        self.lib_nm_ptrs = (C.c_void_p * n_lib)(*[lb.d_nmask.data_ptr() if lb.d_nmask is not None else None for lb in p.libs]) if self.masks else None
+        self.d_work = torch.zeros(int(p.lib.gf_closing_pools_work_words(n_gaps)), dtype=torch.int32, device=p.dev)
+        self.n_blocks = 1 + (n_lib if self.per_library else 0)         # statistics: the merged pool's block, then one per library
+        self.d_stats = torch.zeros(self.n_blocks * B.CP_WORDS, dtype=torch.int32, device=p.dev)
+        self.d_off = torch.zeros(self.n_blocks * (n_gaps + 1), dtype=torch.int64, device=p.dev)
+        # a library's masks in the order of its own pool's rows (gathered by the pool's read ids before the library's call)
+        self.d_src_nm = torch.zeros(p.lib_cap * self.nmw, dtype=torch.int32, device=p.dev) if self.masks and self.per_library else None
+        self.cap = self.lib_cap = 4096
+        self._alloc()
+        p._size_round("closing pools", self._grow)
+
+    def _rows(self):
+        st = self.d_stats.cpu().numpy().view(np.uint32).reshape(self.n_blocks, B.CP_WORDS)
+        return st, [P.counter_u64(b, B.CP_ROWS) for b in st]
+
+    def _grow(self):
+        _, rows = self._rows()
+        grown = False
+        if rows[0] > self.cap:
+            self.cap, grown = int(1.25 * rows[0]) + 1024, True
+        if max(rows[1:], default=0) > self.lib_cap:
+            self.lib_cap, grown = int(1.25 * max(rows[1:])) + 1024, True
+        if grown:
+            self._alloc()
+        return grown
+
+    def off_ptr(self, block):
+        return self.d_off.data_ptr() + 8 * block * (self.p.n_gaps + 1)
+
+    def pool_args(self):
+        """FillRound.pool_args' four arguments for the merged closing pool."""
+        return (self.d_pool.data_ptr(), self.d_nm.data_ptr() if self.d_nm is not None else None, self.off_ptr(0), self.cap)
+
+    def lib_pool_args(self, l):
+        """PairSpan.lib_pool_args' six arguments for library l's closing pool (its head: the library's own pool of the step)."""
+        nm = self.d_lib_nm[l]
+        return (self.d_lib_pool[l].data_ptr(), nm.data_ptr() if nm is not None else None, self.off_ptr(1 + l), self.d_lib_ids[l].data_ptr(), self.lib_cap,
+                self.p.libs[l].d_pool_off.data_ptr())
+
+    def _call(self, block, filt, src, src_off, src_nm, src_ids, src_lib, pool, cap, nm, ids, libs):
+        p, r2 = self.p, self.p.round2
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        p._chk(p.lib.gf_closing_pools_dev(p.h, r2.d_sorted.data_ptr(), r2.d_work.data_ptr(), r2.key_cap, r2.lib_ptrs, self.lib_nm_ptrs, len(p.libs),
+                                          filt, p.L, src, src_off, src_nm, ptr(src_ids), src_lib, p.d_best.data_ptr(), p.n_gaps,
+                                          self.d_work.data_ptr(), self.off_ptr(block), pool.data_ptr(), cap, ptr(nm), ptr(ids), ptr(libs),
+                                          self.d_stats.data_ptr() + 4 * B.CP_WORDS * block), "gf_closing_pools_dev")
+
+    def enqueue(self, d_nmask=None):
+        """Behind the last pick of the step, before the after-pick rounds.  d_nmask: the N masks assemble() was given."""
+        p = self.p
+        if self.d_pool is None:       # the second round's own sizing runs: nobody reads a closing pool yet
+            return
+        if d_nmask is not None and not self.masks:
+            raise RuntimeError("closing_pools: masks of the step's pool without a library that has masks")
+        one = not p.need_merge        # the step's pool is library 0's own: its rows have read ids
+        self._call(0, -1, p.asm_ptr, p.asm_off, d_nmask, p.libs[0].d_ids if one else None, 0 if one else -1, self.d_pool, self.cap, self.d_nm,
+                   self.d_ids, self.d_lib)
+        for l, lb in enumerate(p.libs if self.per_library else ()):
+            src_nm = None
+            if lb.d_nmask is not None:
+                p._chk(p.lib.gf_gather_rows_dev(p.h, lb.d_nmask.data_ptr(), lb.n_reads, 4 * self.nmw, lb.d_ids.data_ptr(),
+                                                lb.d_pool_off.data_ptr() + 8 * p.n_gaps, p.lib_cap, self.d_src_nm.data_ptr()), "gf_gather_rows_dev")
+                src_nm = self.d_src_nm.data_ptr()
+            self._call(1 + l, l, p.pool_ptr[l], lb.d_pool_off.data_ptr(), src_nm, lb.d_ids, l, self.d_lib_pool[l], self.lib_cap, self.d_lib_nm[l],
+                       self.d_lib_ids[l], None)
+
+    def fetch(self, r, pools):
+        p = self.p
+        st, rows = self._rows()
+        caps = [self.cap] + [self.lib_cap] * (self.n_blocks - 1)
+        for b, (need, cap) in enumerate(zip(rows, caps)):
+            if int(st[b][B.CP_OVF]) or need > cap:
+                raise RuntimeError("closing pools: %d rows of %s exceed the capacity %d"
+                                   % (need, "the merged pool" if b == 0 else "library %s" % p.libs[b - 1].name, cap))
+        blocks = [{"rows": rows[b], "gaps": int(st[b][B.CP_GAPS]), "recruited_rows": int(st[b][B.CP_RECRUITED]), "capacity": caps[b]}
+                  for b in range(self.n_blocks)]
+        r.closing_pools = dict(blocks[0], per_library=blocks[1:])
+        if not pools:
+            return
+        off = self.d_off.cpu().numpy().astype(np.int64).reshape(self.n_blocks, p.n_gaps + 1)
+        rows_of = lambda t, n: t[:n * p.rb].cpu().numpy().reshape(-1, p.rb)
+        nm_of = lambda t, n: None if t is None else t[:n * self.nmw].cpu().numpy().view(np.uint32).reshape(-1, self.nmw)
+        n = rows[0]
+        r.closing_pool_off, r.closing_pool_rows, r.closing_pool_nmask = off[0], rows_of(self.d_pool, n), nm_of(self.d_nm, n)
+        if self.d_ids is not None:
+            r.closing_pool_ids, r.closing_pool_lib = self.d_ids[:n].cpu().numpy().view(np.uint32), self.d_lib[:n].cpu().numpy()
+        if self.per_library:
+            r.closing_lib_pool_off = [off[1 + l] for l in range(len(p.libs))]
+            r.closing_lib_pool_rows = [rows_of(self.d_lib_pool[l], rows[1 + l]) for l in range(len(p.libs))]
+            r.closing_lib_pool_ids = [self.d_lib_ids[l][:rows[1 + l]].cpu().numpy().view(np.uint32) for l in range(len(p.libs))]
+            r.closing_lib_pool_nmask = [nm_of(self.d_lib_nm[l], rows[1 + l]) for l in range(len(p.libs))] if self.masks else None
+
+
+def closing_pools_host(n_src, best, keys, library=None):
+    """The closing pools' definition in plain Python.  n_src[g]: rows of the source pool of gap g (the pool the step's first assembly saw;
+    library l's own pool with library=l); best[g]: the pick word, 0 for an open gap; keys: (gap, library, pair) of the final recruit sets,
+    in any order, repeats allowed.  -> per gap the rows in pool order: (-1, j) for row j of the gap's source rows, (library, read id) for a
+    recruit — reads 2p, 2p + 1 of every pair in (library, pair) order, each pair once; [] for an open gap, whatever keys it holds."""
+    S = {}
+    for g, l, q in keys:
+        if 0 <= g < len(best) and (library is None or l == library):
+            S.setdefault(g, set()).add((l, q))
+    return [([(-1, j) for j in range(n_src[g])] + [(l, 2 * q + m) for l, q in sorted(S.get(g, ())) for m in (0, 1)]) if best[g] else []
+            for g in range(len(best))]
+
+
 def _reads_of_keys(keys):
     """{gap: [(library, read id)]} of sorted keys gap << 40 | library << 36 | pair: both reads of every pair."""
     gap, libi, pair = (keys >> np.uint64(40)).astype(np.int64), ((keys >> np.uint64(36)) & np.uint64(15)).astype(np.int64), \

@@ -1123,6 +1123,14 @@ int gf_fill_pairs_dev(gf_ctx* ctx, const void* d_pool_packed, const void* d_nmas
                       size_t pool_cap_rows, int read_len, const void* d_contigs, const void* d_n_contigs, size_t contig_cap, const void* d_seq,
                       const void* d_gap_best, const void* d_ctg_pick_or_null, int anchor_long, int anchor_short, int seed, int max_mismatch,
                       int min_overlap, int is_mean, int is_sd, int z, void* d_place_scratch, void* d_rec, void* d_stats);
+/* gf_fill_pairs_dev on slices only whose head is ordered by (mate side, pair): d_head_off (u64[n_gaps + 1]) gives the head's rows of gap g as
+ * d_head_off[g + 1] - d_head_off[g]; the rows behind it are whole pairs ordered by read id (a library's closing pool: gf_closing_pools_dev).
+ * A read with a row in both parts counts at its first row, and so does its mate.  d_head_off_or_null == NULL: gf_fill_pairs_dev. */
+int gf_fill_pairs_split_dev(gf_ctx* ctx, const void* d_pool_packed, const void* d_nmask_or_null, const void* d_pool_off, const void* d_pool_read_ids,
+                            size_t pool_cap_rows, const void* d_head_off_or_null, int read_len, const void* d_contigs, const void* d_n_contigs,
+                            size_t contig_cap, const void* d_seq, const void* d_gap_best, const void* d_ctg_pick_or_null, int anchor_long,
+                            int anchor_short, int seed, int max_mismatch, int min_overlap, int is_mean, int is_sd, int z, void* d_place_scratch,
+                            void* d_rec, void* d_stats);
 
 /* ---- anchored pair span (csrc/fill_anchor.hip; definition and host twin: gappadder_amd/pair_anchors.py).  Called behind
  * gf_fill_pairs_dev of the SAME library in the same step, with that call's pool offsets, read ids, shared arguments and d_place_scratch
@@ -1293,6 +1301,25 @@ int gf_round_carry_dev(gf_ctx* ctx, void* d_keys, const void* d_keys_sorted, siz
 int gf_round_pools_dev(gf_ctx* ctx, void* d_keys, void* d_keys_sorted, size_t key_cap, const void* const* d_lib_reads, int n_lib, int read_len,
                        const void* d_asm_pool, const void* d_asm_off, const void* d_gap_best, size_t n_gaps, const void* d_prev_cnt, void* d_work,
                        void* d_rows, void* d_pool, size_t pool_cap, void* d_stats, const void* d_live_or_null);
+
+/* ---- the closing pools (closing_pools.hip): after the last recruitment round, per gap with d_gap_best != 0 the rows of a
+ * source pool (d_src_pool / d_src_off, u64[n_gaps + 1]: the pool the step's first assembly saw, or one library's own pool) followed by reads
+ * 2p, 2p + 1 of every distinct key (gap, library, p) of the gap in (library, pair) order; a gap with d_gap_best == 0 gets an empty pool,
+ * whatever keys it has.  d_keys_sorted, d_round_work, key_cap: what the last gf_round2_pools_dev / gf_round_pools_dev call left (a gated call
+ * leaves them as the call before did).  lib_filter: -1, or the one library whose keys count.  d_lib_reads / d_lib_nmask_or_null: n_lib device
+ * pointers each (host arrays; a mask entry may be NULL).  d_work: gf_closing_pools_work_words(n_gaps) u32 words.
+ * Out: d_off u64[n_gaps + 1]; d_pool, rows of gf_packed_read_bytes(read_len) bytes; optional d_nmask (ceil(read_len / 32) u32 words per row:
+ * the source's, the library's, zero where there is none), d_ids (u32 per row: d_src_ids', 0xFFFFFFFF without them; 2p, 2p + 1) and d_lib
+ * (u8 per row: src_lib; the key's library).  d_stats: u32[GF_CP_WORDS], set by the call: [0-1] u64 rows needed, [2] gaps with a non-empty
+ * pool, [3] recruited rows copied, [4] 1 when the rows exceed pool_cap — every pool is then left empty ([2] = [3] = 0) and no row is written.
+ * Enqueued on the context's stream; no host synchronisation. */
+#define GF_CP_WORDS 8
+size_t gf_closing_pools_work_words(size_t n_gaps);
+int gf_closing_pools_dev(gf_ctx* ctx, const void* d_keys_sorted, const void* d_round_work, size_t key_cap, const void* const* d_lib_reads,
+                         const void* const* d_lib_nmask_or_null, int n_lib, int lib_filter, int read_len, const void* d_src_pool,
+                         const void* d_src_off, const void* d_src_nmask_or_null, const void* d_src_ids_or_null, int src_lib, const void* d_gap_best,
+                         size_t n_gaps, void* d_work, void* d_off, void* d_pool, size_t pool_cap, void* d_nmask_or_null, void* d_ids_or_null,
+                         void* d_lib_or_null, void* d_stats);
 
 /* ---- the reference's rescue round (assemble_gaps.py:166-217 run_collect_high_quality_unmap_to_contig_reads: `bwa mem` of a gap's high-quality
  * reads against its merged contigs, reads that align CLIPPED to at least two contigs are bridges), for ALL gaps of a round in one host call (no GPU
