@@ -188,6 +188,15 @@ class ProbeColumnGeom(C.Structure):
         return (self.n_reads, self.read_len, self.k, self.first, self.stride, self.np, self.ext)
 
 
+class ScreenPartsGeom(C.Structure):
+    """gf_screen_parts_geom: what a library's resident parts (pass A's output) were built for (include/gapfill_hip.h)."""
+    _fields_ = [("probe", ProbeColumnGeom)] + [(n, C.c_uint32) for n in ("n_writers", "cap", "gs", "n_groups", "n_grp", "tiles_wg", "use", "reserved")]
+
+    def key(self):
+        """What the parts depend on (not `use`, which is advice, nor the reserved word)."""
+        return self.probe.key() + (self.n_writers, self.cap, self.gs, self.n_groups, self.n_grp, self.tiles_wg)
+
+
 class TagLayout(C.Structure):
     """gf_tag_layout: the linear layout a library's 4-byte key column was built for (include/gapfill_hip.h)."""
     _fields_ = [("n_recs", C.c_uint64), ("span", C.c_uint64), ("checksum", C.c_uint64), ("n_scaffolds", C.c_uint32),
@@ -276,6 +285,10 @@ def lib():
         "gf_probe_column_bytes": (sz, [C.POINTER(ProbeColumnGeom)]),
         "gf_read_probes_dev": (i32, [vp, vp, sz, i32, i32, vp, C.POINTER(ProbeColumnGeom)]),
         "gf_screen_reads_probes_dev": (i32, [vp, vp, vp, vp, C.POINTER(ProbeColumnGeom), sz, i32, i32, i32, vp, sz, vp]),
+        "gf_screen_parts_geometry": (i32, [vp, sz, i32, i32, C.POINTER(ScreenPartsGeom)]),
+        "gf_screen_parts_bytes": (sz, [C.POINTER(ScreenPartsGeom)]),
+        "gf_screen_parts_build_dev": (i32, [vp, vp, vp, C.POINTER(ProbeColumnGeom), sz, i32, i32, vp, C.POINTER(ScreenPartsGeom)]),
+        "gf_screen_reads_parts_dev": (i32, [vp, vp, vp, vp, C.POINTER(ProbeColumnGeom), vp, C.POINTER(ScreenPartsGeom), sz, i32, i32, i32, vp, sz, vp]),
         "gf_tag_alignments": (i32, [vp, vp, sz, i32, i32, i32, i32, vp, sz, szp]),
         "gf_tag_alignments_dev": (i32, [vp, vp, sz, i32, i32, i32, i32, vp, sz, vp]),
         "gf_tag_low_mapq": (i32, [vp, vp, sz, vp, sz, vp, sz, szp]),

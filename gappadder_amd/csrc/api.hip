@@ -8,6 +8,7 @@
 
 #include "fill_round.hpp"
 #include "gf_internal.hpp"
+#include "screen_dev.hpp"   // the resident parts' geometry and layout (fill_parts_geom, parts_layout)
 
 namespace gf {
 
@@ -398,6 +399,42 @@ int gf_screen_reads_probes_dev(gf_ctx* ctx, const void* d_reads, const void* d_n
     int rc = build_flank_index(ctx, k, &ix);
     if (rc) return rc;
     return launch_screen(ctx, *ix, d_reads, d_nmask, n_reads, read_len, min_hits, d_out, cap, d_n_out, d_probes, built_for);
+}
+
+int gf_screen_parts_geometry(gf_ctx* ctx, size_t n_reads, int read_len, int k, gf_screen_parts_geom* out) {
+    if (!out || read_len < k || read_len > 1000 || k < 16 || k > 64) return GF_E_INVAL;
+    FlankIndex* ix = nullptr;
+    const int rc = probe_index(ctx, k, &ix);
+    if (rc) return rc;
+    (void)fill_parts_geom(ctx, ix, n_reads, read_len, k, out);
+    return GF_OK;
+}
+
+size_t gf_screen_parts_bytes(const gf_screen_parts_geom* g) {
+    return g && g->n_writers ? parts_layout(g->n_writers, g->cap, g->gs).bytes : 0;
+}
+
+int gf_screen_parts_build_dev(gf_ctx* ctx, const void* d_reads, const void* d_probes, const gf_probe_geom* probe_geom, size_t n_reads, int read_len,
+                              int k, void* d_parts, gf_screen_parts_geom* built_for) {
+    if (!ctx || !d_parts || !built_for || (n_reads && !d_reads) || (d_probes && !probe_geom) || read_len < k || read_len > 1000 || k < 16 || k > 64)
+        return GF_E_INVAL;
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    FlankIndex* ix = nullptr;
+    const int rc = probe_index(ctx, k, &ix);
+    if (rc) return rc;
+    return launch_parts_build(ctx, ix, d_reads, d_probes, probe_geom, n_reads, read_len, k, d_parts, built_for);
+}
+
+int gf_screen_reads_parts_dev(gf_ctx* ctx, const void* d_reads, const void* d_nmask, const void* d_probes, const gf_probe_geom* probe_geom,
+                              const void* d_parts, const gf_screen_parts_geom* parts_for, size_t n_reads, int read_len, int k, int min_hits,
+                              void* d_out, size_t cap, void* d_n_out) {
+    if (!ctx || !d_n_out || (n_reads && !d_reads) || (cap && !d_out) || (d_probes && !probe_geom) || (d_parts && !parts_for)) return GF_E_INVAL;
+    if (ctx->gaps.empty() && ctx->n_scaffolds == 0) return GF_E_STATE;
+    GF_HIP(ctx, hipSetDevice(ctx->device));
+    FlankIndex* ix = nullptr;
+    int rc = build_flank_index(ctx, k, &ix);
+    if (rc) return rc;
+    return launch_screen(ctx, *ix, d_reads, d_nmask, n_reads, read_len, min_hits, d_out, cap, d_n_out, d_probes, probe_geom, d_parts, parts_for);
 }
 
 int gf_screen_debug_view(gf_ctx* ctx, gf_screen_view* out) {

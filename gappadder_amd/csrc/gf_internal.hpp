@@ -253,7 +253,11 @@ int launch_read_probes(gf_ctx* ctx, const FlankIndex* ix_or_null, const void* d_
 // d_probes + built_for: the library's probe column and the geometry it was built for (or null): used only where it is valid for this screen
 int launch_screen(gf_ctx* ctx, const FlankIndex& ix, const void* d_reads, const void* d_nmask, size_t n_reads,
                   int read_len, int min_hits, void* d_out, size_t cap, void* d_n_out, const void* d_probes = nullptr,
-                  const gf_probe_geom* built_for = nullptr);
+                  const gf_probe_geom* built_for = nullptr, const void* d_parts = nullptr, const gf_screen_parts_geom* parts_for = nullptr);
+// d_parts + parts_for, likewise: the library's resident parts (pass A's output, gf_screen_parts_geom) — where they fit, pass A is not launched.
+// launch_parts_build fills them (ix as fill_probe_geom's; geometry and plan: fill_parts_geom, screen_dev.hpp).
+int launch_parts_build(gf_ctx* ctx, const FlankIndex* ix_or_null, const void* d_reads, const void* d_probes, const gf_probe_geom* probes_for,
+                       size_t n_reads, int read_len, int k, void* d_parts, gf_screen_parts_geom* built_for);
 // tagger.hip (the plan of its launch: tag_dev.hpp)
 int launch_tag(gf_ctx* ctx, const void* d_recs, size_t n, int insert_size, int sd, int clip_dist, int anchor_mapq,
                void* d_out, size_t cap, void* d_n_out, void* d_low, size_t low_cap, void* d_n_low, const void* d_keys = nullptr,

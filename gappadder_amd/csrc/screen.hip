@@ -415,6 +415,7 @@ static const PipeKernel* pipe_kernel(uint32_t nch, uint32_t npt, bool exact) {
 // What launch_screen will do for n_reads reads of read_len bases against index ix under the context's options (screen_variant: 0 =
 // automatic; 9 / 13 force the plain / pipelined form, 16 / 17 the partitioned form with whole-line / unaligned stores, 18 = 16 without
 // a probe column — the parity tests run every one of them on the same inputs).
+static void plan_pf4(const gf_ctx* ctx_or_null, ScreenPlan& S, size_t n_reads);
 ScreenPlan plan_screen(const gf_ctx* ctx, const FlankIndex& ix, size_t n_reads, int read_len) {
     ScreenPlan S = {};
     const int variant = ctx->screen_variant;
@@ -427,7 +428,6 @@ ScreenPlan plan_screen(const gf_ctx* ctx, const FlankIndex& ix, size_t n_reads, 
                         ix.bm_log2 <= 28 && rb <= 64 && ix.d_sgrp && pf4_scatter_lds_bytes(pf4_slice_words(rb)) <= 156 * 1024;
     S.pg = probe_geometry(read_len, ix.k, pf4_ok && ctx->screen_ext);
     const uint32_t np = S.pg.np;
-    S.bytes = ((2 * S.pg.first) & 7u) == 0 && ((2 * S.pg.stride) & 7u) == 0;
 
     // the LDS pre-filter pays while the coarse bitmap is sparse enough to stop most probes before L2 and a handful of waves
     // fit next to it (long reads leave too few); the pipelined form covers up to 10 probes and 64 packed bytes per read
@@ -455,12 +455,24 @@ ScreenPlan plan_screen(const gf_ctx* ctx, const FlankIndex& ix, size_t n_reads, 
         S.form = ScreenForm::plain;
         return S;
     }
-    // partitioned filter, 256 buckets, 4-byte pairs (see Part4Params)
+    plan_pf4(ctx, S, n_reads);
+    return S;
+}
+
+// The partitioned filter (256 buckets, 4-byte pairs, see Part4Params) for S.rb and S.pg: the form of pass A, its parts and the workspace.
+// Nothing here reads the index — what pass A leaves depends on the reads and these numbers alone, which is why a library may keep it
+// (fill_parts_geom).  ctx null: the default options on a device of 256 CUs.
+static void plan_pf4(const gf_ctx* ctx, ScreenPlan& S, size_t n_reads) {
+    const int variant = ctx ? ctx->screen_variant : 0, n_cu = ctx ? ctx->n_cu : 256, writers = ctx ? ctx->screen_pf4_writers : 0,
+              cap8_opt = ctx ? ctx->screen_pf4_cap8 : 0;
+    const uint32_t rb = S.rb, np = S.pg.np;
+    const size_t tiles64 = (n_reads + 63) / 64;
+    S.bytes = ((2 * S.pg.first) & 7u) == 0 && ((2 * S.pg.stride) & 7u) == 0;
     S.slice_words = pf4_slice_words(rb);
     const size_t tiles_wg = (size_t)PF2_WAVES * PF2_TILES;      // tiles per workgroup and iteration
     // (the pair list carries the writer in 8 bits; an empty read set plans like one tile — nothing is launched for it)
-    S.n_writers = (uint32_t)std::max<size_t>(std::min<size_t>(std::min<size_t>((tiles64 + tiles_wg - 1) / tiles_wg, (size_t)ctx->n_cu), 256), 1);
-    if (ctx->screen_pf4_writers > 0) S.n_writers = std::min(S.n_writers, (uint32_t)ctx->screen_pf4_writers);   // tests: long parts on small inputs (several trips of pass B)
+    S.n_writers = (uint32_t)std::max<size_t>(std::min<size_t>(std::min<size_t>((tiles64 + tiles_wg - 1) / tiles_wg, (size_t)n_cu), 256), 1);
+    if (writers > 0) S.n_writers = std::min(S.n_writers, (uint32_t)writers);   // tests: long parts on small inputs (several trips of pass B)
     S.tiles_wg = (uint32_t)tiles_wg;
     const size_t n_iter = (tiles64 + (size_t)S.n_writers * tiles_wg - 1) / ((size_t)S.n_writers * tiles_wg);
     const double pairs_w = (double)n_iter * tiles_wg * 64.0 * np;
@@ -480,21 +492,21 @@ ScreenPlan plan_screen(const gf_ctx* ctx, const FlankIndex& ix, size_t n_reads, 
     S.n_groups = (uint32_t)(n_iter * S.n_grp);
     S.gs = (S.n_groups + 1 + 15) & ~15u;
     S.cap8 = (uint32_t)(std::min<size_t>(std::max<size_t>((size_t)1 << 22, n_reads / 2), 0x7FFFFFFFu) / PF4_CHUNK * PF4_CHUNK);
-    if (ctx->screen_pf4_cap8 > 0) S.cap8 = (uint32_t)std::max(1, ctx->screen_pf4_cap8 / (int)PF4_CHUNK) * PF4_CHUNK;   // tests: a short pair list (the serial path)
+    if (cap8_opt > 0) S.cap8 = (uint32_t)std::max(1, cap8_opt / (int)PF4_CHUNK) * PF4_CHUNK;   // tests: a short pair list (the serial path)
     S.plane = ((uint64_t)n_reads + 63) & ~(uint64_t)63;
     const size_t b_pairs = (size_t)PF2_NB * S.n_writers * S.cap * 4, b_cnt = ((size_t)PF2_NB * S.n_writers * 4 + 255 + 256) & ~(size_t)255,
                  b_seen = (((size_t)n_reads + 31) / 32 * 4 + 255) & ~(size_t)255, b_fill = (size_t)PF2_NB * S.n_writers * S.gs * 4,
                  b_c8 = ((size_t)S.cap8 * 12 + S.cap8 / PF4_CHUNK + 1 + 255) & ~(size_t)255;
     S.o_n_cand8 = b_cnt - 256;
     S.o_seen = b_cnt;
-    S.o_fills = b_cnt + b_seen;
-    S.o_cand8 = S.o_fills + b_fill;
+    S.o_cand8 = b_cnt + b_seen;
     S.o_cand8x = S.o_cand8 + (size_t)S.cap8 * 8;
     S.o_chunk_b = S.o_cand8 + (size_t)S.cap8 * 12;
-    S.o_pairs = S.o_cand8 + b_c8;
+    S.o_fills = S.o_cand8 + b_c8;
+    S.o_pairs = S.o_fills + b_fill;
     S.ws_bytes = S.o_pairs + b_pairs + 1024;
+    S.ws_bytes_resident = S.o_fills;
     S.zero_bytes = 256 + b_seen;
-    return S;
 }
 
 // ix: the flank index of k when the context has gaps (the column is then wanted only where the screen would stream it), or null
@@ -515,11 +527,42 @@ void fill_probe_geom(gf_ctx* ctx, const FlankIndex* ix, size_t n_reads, int read
     g->ext = pg.ext;
 }
 
+// What a library's resident parts depend on and whether they are kept (`use`): the probe geometry, and of the plan the numbers that
+// shape pass A's output.  With an index the plan is the one the screen itself will make; without (no gaps yet, or no context) the one
+// the partitioned filter would have.  Returns that plan: the build launches its pass A.
+ScreenPlan fill_parts_geom(gf_ctx* ctx, const FlankIndex* ix, size_t n_reads, int read_len, int k, gf_screen_parts_geom* g) {
+    fill_probe_geom(ctx, ix, n_reads, read_len, k, &g->probe);
+    ScreenPlan S = {};
+    if (n_reads < 0xFFFFFFFFull) {
+        if (ctx && ix) S = plan_screen(ctx, *ix, n_reads, read_len);
+        else {
+            S.rb = (uint32_t)((read_len + 3) / 4);
+            S.pg = probe_geometry(read_len, k, !ctx || ctx->screen_ext != 0);
+            if (S.rb <= 64 && pf4_scatter_lds_bytes(pf4_slice_words(S.rb)) <= 156 * 1024) plan_pf4(ctx, S, n_reads);
+        }
+    }
+    g->use = g->probe.use && S.col_ok && S.cap < (1u << 24);
+    g->n_writers = S.n_writers;
+    g->cap = S.cap;
+    g->gs = S.gs;
+    g->n_groups = S.n_groups;
+    g->n_grp = S.n_grp;
+    g->tiles_wg = S.tiles_wg;
+    g->reserved = 0;
+    return S;
+}
+
 // is the handed column one that pass A may stream for this plan: built for exactly this call's reads and geometry?
-static bool column_fits(const ScreenPlan& S, const FlankIndex& ix, size_t n_reads, int read_len, const void* d_probes, const gf_probe_geom* built_for) {
+static bool column_fits(const ScreenPlan& S, int k, size_t n_reads, int read_len, const void* d_probes, const gf_probe_geom* built_for) {
     return S.col_ok && d_probes && built_for && built_for->use && built_for->n_reads == n_reads && built_for->read_len == (uint32_t)read_len &&
-           built_for->k == (uint32_t)ix.k && built_for->first == S.pg.first && built_for->stride == S.pg.stride && built_for->np == S.pg.np &&
+           built_for->k == (uint32_t)k && built_for->first == S.pg.first && built_for->stride == S.pg.stride && built_for->np == S.pg.np &&
            built_for->ext == S.pg.ext;
+}
+
+// are the handed parts what pass A of this plan would leave: built for exactly this call's reads, geometry and parts?
+static bool parts_fit(const ScreenPlan& S, int k, size_t n_reads, int read_len, const void* d_parts, const gf_screen_parts_geom* b) {
+    return d_parts && b && b->use && column_fits(S, k, n_reads, read_len, d_parts, &b->probe) && b->n_writers == S.n_writers && b->cap == S.cap &&
+           b->gs == S.gs && b->n_groups == S.n_groups && b->n_grp == S.n_grp && b->tiles_wg == S.tiles_wg;
 }
 
 static FilterParams filter_params(const gf_ctx* ctx, const FlankIndex& ix, const ScreenPlan& S, const void* d_reads, size_t n_reads) {
@@ -574,7 +617,8 @@ static int wait_after_filter(gf_ctx* ctx, gf_ctx* waiter) {
 }
 
 int launch_screen(gf_ctx* ctx, const FlankIndex& ix, const void* d_reads, const void* d_nmask, size_t n_reads,
-                  int read_len, int min_hits, void* d_out, size_t cap, void* d_n_out, const void* d_probes, const gf_probe_geom* built_for) {
+                  int read_len, int min_hits, void* d_out, size_t cap, void* d_n_out, const void* d_probes, const gf_probe_geom* built_for,
+                  const void* d_parts, const gf_screen_parts_geom* parts_for) {
     // one-shot (gf_stream_wait_after_filter): taken here, so that no exit below leaves it armed for a later, unrelated pass
     gf_ctx* const waiter = ctx->after_filter;
     ctx->after_filter = nullptr;
@@ -593,12 +637,43 @@ int launch_screen(gf_ctx* ctx, const FlankIndex& ix, const void* d_reads, const 
     switch (S.form) {
         case ScreenForm::pipe: rc = launch_filter_pipe(ctx, S, F); break;
         case ScreenForm::plain: rc = launch_filter_plain(ctx, S, F); break;
-        default: rc = launch_filter_pf4(ctx, ix, S, F, column_fits(S, ix, n_reads, read_len, d_probes, built_for) ? d_probes : nullptr); break;
+        default:
+            rc = launch_filter_pf4(ctx, ix, S, F, column_fits(S, ix.k, n_reads, read_len, d_probes, built_for) ? d_probes : nullptr,
+                                   parts_fit(S, ix.k, n_reads, read_len, d_parts, parts_for) ? d_parts : nullptr);
+            break;
     }
     if (rc) return rc;
     GF_HIP(ctx, hipGetLastError());
     if (waiter && (rc = wait_after_filter(ctx, waiter))) return rc;
     return launch_verify_passes(ctx, ix, S.pg, d_reads, d_nmask, n_reads, read_len, min_hits, d_out, cap, d_n_out);
+}
+
+// A library's resident parts: pass A alone into the caller's buffer (a set-up call: it waits for the stream once, to read how many pairs
+// found their part full — any, and the parts are not kept)
+int launch_parts_build(gf_ctx* ctx, const FlankIndex* ix, const void* d_reads, const void* d_probes, const gf_probe_geom* probes_for, size_t n_reads,
+                       int read_len, int k, void* d_parts, gf_screen_parts_geom* built_for) {
+    if (n_reads >= 0xFFFFFFFFull) return GF_E_INVAL;
+    const ScreenPlan S = fill_parts_geom(ctx, ix, n_reads, read_len, k, built_for);
+    if (n_reads == 0) built_for->use = 0;
+    if (!built_for->use) return GF_OK;
+    int rc;
+    if ((rc = ensure(ctx, ctx->counters, GF_COUNTER_BYTES))) return rc;
+    uint32_t* spills = (uint32_t*)ctx->counters.p + 5;   // ([0, 5): the screen's own)
+    GF_HIP(ctx, hipMemsetAsync(spills, 0, 4, ctx->stream));
+    FilterParams F = {};
+    F.reads = (const uint8_t*)d_reads;
+    F.n_reads = n_reads;
+    F.rb = S.rb;
+    F.stride2 = 2 * S.pg.stride;
+    F.first2 = 2 * S.pg.first;
+    F.np = S.pg.np;
+    if ((rc = launch_pass_a_build(ctx, S, F, column_fits(S, k, n_reads, read_len, d_probes, probes_for) ? d_probes : nullptr, d_parts, spills))) return rc;
+    GF_HIP(ctx, hipGetLastError());
+    uint32_t n_spilled = 0;
+    GF_HIP(ctx, hipMemcpyAsync(&n_spilled, spills, 4, hipMemcpyDeviceToHost, ctx->stream));
+    GF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (n_spilled) built_for->use = 0;
+    return GF_OK;
 }
 
 }  // namespace gf

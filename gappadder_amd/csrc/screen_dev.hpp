@@ -146,6 +146,9 @@ struct Part4Params {
     uint32_t* cand8x;             // per list entry: the ext word of the pair's 16-mer
     const uint32_t* probes;       // pass A's column form: the library's probe column, `plane` words per probe
     uint64_t plane;
+    // pass A alone, for a library's resident parts (launch_parts_build): no gaps, so a pair that finds its part full has nothing to be
+    // tested against — it is counted here and skipped, and the caller keeps no parts.  Null: a screen (the pair is tested on the spot).
+    uint32_t* spills;
 };
 constexpr uint32_t PF4_OBUF = 80;     // list entries buffered per wave of pass B (8 + 4 bytes each)
 // the pair's key in the grouped exact set, from group g on: found -> its ext word
@@ -235,13 +238,30 @@ struct ScreenPlan {
     uint64_t plane;          // words per plane of a probe column
     size_t slice_words;      // a staged 64-read tile + pad, in words
     size_t lds_a, lds_a_col; // pass A's LDS bytes: from the rows / from a column
-    // its workspace: `count` at 0, then the blocks at these byte offsets; zero_bytes from o_n_cand8 are cleared before pass A (the list counter and `seen`)
-    size_t o_n_cand8, o_seen, o_fills, o_cand8, o_cand8x, o_chunk_b, o_pairs, ws_bytes, zero_bytes;
+    // its workspace: `count` at 0, then the blocks at these byte offsets; zero_bytes from o_n_cand8 are cleared before pass A (the list counter and `seen`).
+    // The fill history and the pairs come last: a screen from a library's resident parts needs the workspace up to o_fills only.
+    size_t o_n_cand8, o_seen, o_fills, o_cand8, o_cand8x, o_chunk_b, o_pairs, ws_bytes, ws_bytes_resident, zero_bytes;
 };
 ScreenPlan plan_screen(const gf_ctx* ctx, const FlankIndex& ix, size_t n_reads, int read_len);   // n_reads < 2^32; no HIP call, nothing written
 
-// the filter of a planned screen from the partitioned form (screen_pf4.hip); d_probes: a column valid for this call, or null (the rows)
-int launch_filter_pf4(gf_ctx* ctx, const FlankIndex& ix, const ScreenPlan& S, const FilterParams& F, const void* d_probes);
+// A library's RESIDENT PARTS (gf_screen_parts_geom): pass A's output in one caller-owned buffer [count | fills | pairs], the pairs followed
+// by the 64 words pass A's idle lanes store to.  Nothing in it depends on the gaps.
+struct PartsLayout { size_t o_fills, o_pairs, bytes; };
+inline PartsLayout parts_layout(uint32_t n_writers, uint32_t cap, uint32_t gs) {
+    PartsLayout L;
+    L.o_fills = ((size_t)PF2_NB * n_writers * 4 + 255) & ~(size_t)255;
+    L.o_pairs = L.o_fills + (size_t)PF2_NB * n_writers * gs * 4;
+    L.bytes = L.o_pairs + (size_t)PF2_NB * n_writers * cap * 4 + 64 * 4;
+    return L;
+}
+// the plan whose pass A fills / whose passes B.. read a library's parts, and whether parts are kept at all (g->use); ix: as fill_probe_geom
+ScreenPlan fill_parts_geom(gf_ctx* ctx_or_null, const FlankIndex* ix_or_null, size_t n_reads, int read_len, int k, gf_screen_parts_geom* g);
+
+// the filter of a planned screen from the partitioned form (screen_pf4.hip); d_probes: a column valid for this call, or null (the rows);
+// d_parts: resident parts valid for this call (pass A is then not launched: passes B, resolve and list read them and write none of it), or null
+int launch_filter_pf4(gf_ctx* ctx, const FlankIndex& ix, const ScreenPlan& S, const FilterParams& F, const void* d_probes, const void* d_parts);
+// pass A of plan S alone into d_parts (parts_layout); F: the reads and the probe geometry, nothing of an index; spills: device counter
+int launch_pass_a_build(gf_ctx* ctx, const ScreenPlan& S, const FilterParams& F, const void* d_probes, void* d_parts, uint32_t* spills);
 // candidates (ctx->cand, counted in ctx->counters) -> hits (screen_verify.hip)
 int launch_verify_passes(gf_ctx* ctx, const FlankIndex& ix, const ProbeSpots& pg, const void* d_reads, const void* d_nmask, size_t n_reads,
                          int read_len, int min_hits, void* d_out, size_t cap, void* d_n_out);

@@ -6,6 +6,8 @@
 //   pass B   pf4_probe_kernel    a bucket's slice of the level-1 bitmap in LDS, the exact set for what passes
 //   resolve  pf4_resolve_kernel  pairs found in the exact set -> their reads (`seen` bits)
 //   list     pf4_list_kernel     `seen` -> the candidate list
+// Pass A's output depends on the reads alone: launch_pass_a_build runs it once into a library's resident parts, and a screen handed
+// parts that fit its plan starts at pass B (launch_filter_pf4).
 #include "screen_dev.hpp"
 
 namespace gf {
@@ -215,7 +217,8 @@ __global__ __launch_bounds__(64 * PF2_WAVES) void pf4_scatter_kernel(Part4Params
                     asm volatile("global_store_dword %0, %1, off" ::"v"(dst), "v"(e) : "memory");
                     ++stores_since;
                 }
-                if (spill) {   // a part that is full (degenerate inputs): tested on the spot
+                if (spill && Q.spills) atomicAdd(Q.spills, 1u);   // (the parts alone are built: counted, the caller keeps none)
+                else if (spill) {   // a part that is full (degenerate inputs): tested on the spot
                     const uint32_t h = key >> (32 - P.bm_log2);
                     const uint32_t wd = P.bitmap[h >> 5];
                     if ((wd >> (h & 31)) & (wd >> (key & 31)) & 1u) {
@@ -468,7 +471,11 @@ __device__ __forceinline__ void pf4_scatter_lines_body(const Part4Params& Q, uin
                     lsrc[PF2_NB + (at >> 5)] = at;
                 }
         }
-        if (spilled) {   // a part that is full (degenerate inputs): its pair is tested on the spot
+        if (spilled && Q.spills) {   // (the parts alone are built: counted, the caller keeps none)
+#pragma unroll
+            for (uint32_t x = 0; x < PF2_TILES * G; ++x)
+                if (((spilled >> x) & 1u) && rank[x / G][x % G] != EMPTY32) atomicAdd(Q.spills, 1u);
+        } else if (spilled) {   // a part that is full (degenerate inputs): its pair is tested on the spot
 #pragma unroll
             for (uint32_t x = 0; x < PF2_TILES * G; ++x)
                 if (((spilled >> x) & 1u) && rank[x / G][x % G] != EMPTY32) {
@@ -903,10 +910,44 @@ static const PassAKernel* pass_a_kernel(const ScreenPlan& S, bool col) {
     return nullptr;
 }
 
-int launch_filter_pf4(gf_ctx* ctx, const FlankIndex& ix, const ScreenPlan& S, const FilterParams& F, const void* d_probes) {
+static void launch_pass_a(gf_ctx* ctx, const ScreenPlan& S, const PassAKernel* pa, const Part4Params& Q) {
+    if (pa->column) hipLaunchKernelGGL(pa->column, dim3(Q.n_writers), dim3(64 * PF2_WAVES), S.lds_a_col, ctx->stream, Q);
+    else hipLaunchKernelGGL(pa->rows, dim3(Q.n_writers), dim3(64 * PF2_WAVES), S.lds_a, ctx->stream, Q, (uint32_t)S.slice_words);
+}
+
+// the parts of a buffer laid out by parts_layout, as pass A writes and the later passes read them
+static void point_at_parts(Part4Params& Q, const ScreenPlan& S, void* d_parts) {
+    const PartsLayout L = parts_layout(S.n_writers, S.cap, S.gs);
+    Q.count = (uint32_t*)d_parts;
+    Q.fills = (uint32_t*)((uint8_t*)d_parts + L.o_fills);
+    Q.pairs = (uint32_t*)((uint8_t*)d_parts + L.o_pairs);
+}
+
+int launch_pass_a_build(gf_ctx* ctx, const ScreenPlan& S, const FilterParams& F, const void* d_probes, void* d_parts, uint32_t* spills) {
+    if (S.cap >= (1u << 24) || !spills) return GF_E_INVAL;
+    Part4Params Q = {};   // (nothing of an index, no workspace: with `spills` set pass A touches the reads or the column and the parts alone)
+    Q.F = F;
+    Q.n_writers = S.n_writers;
+    Q.cap = S.cap;
+    point_at_parts(Q, S, d_parts);
+    Q.gs = S.gs;
+    Q.n_groups = S.n_groups;
+    Q.n_grp = S.n_grp;
+    Q.tiles_wg = S.tiles_wg;
+    Q.probes = (const uint32_t*)d_probes;
+    Q.plane = S.plane;
+    Q.spills = spills;
+    const PassAKernel* pa = pass_a_kernel(S, d_probes != nullptr);
+    if (!pa) return GF_E_UNSUPPORTED;
+    ctx->screen_kernels = pa->name;   // (the form the build took)
+    launch_pass_a(ctx, S, pa, Q);
+    return GF_OK;
+}
+
+int launch_filter_pf4(gf_ctx* ctx, const FlankIndex& ix, const ScreenPlan& S, const FilterParams& F, const void* d_probes, const void* d_parts) {
     if (S.cap >= (1u << 24)) return GF_E_INVAL;   // a position must fit 24 bits (2^32 reads stay far below)
     int rc;
-    if ((rc = ensure(ctx, ctx->part_ws, S.ws_bytes))) return rc;
+    if ((rc = ensure(ctx, ctx->part_ws, d_parts ? S.ws_bytes_resident : S.ws_bytes))) return rc;
     uint8_t* ws = (uint8_t*)ctx->part_ws.p;
     Part4Params Q;
     Q.F = F;
@@ -915,6 +956,10 @@ int launch_filter_pf4(gf_ctx* ctx, const FlankIndex& ix, const ScreenPlan& S, co
     Q.pairs = (uint32_t*)(ws + S.o_pairs);
     Q.count = (uint32_t*)ws;
     Q.fills = (uint32_t*)(ws + S.o_fills);
+    // a library's resident parts: pass B, resolve and list READ count, fills and pairs and write the workspace alone, so the buffer is
+    // the same after any number of screens
+    if (d_parts) point_at_parts(Q, S, const_cast<void*>(d_parts));
+    Q.spills = nullptr;
     Q.gs = S.gs;
     Q.n_groups = S.n_groups;
     Q.n_grp = S.n_grp;
@@ -930,12 +975,11 @@ int launch_filter_pf4(gf_ctx* ctx, const FlankIndex& ix, const ScreenPlan& S, co
     Q.probes = (const uint32_t*)d_probes;
     Q.plane = S.plane;
     GF_HIP(ctx, hipMemsetAsync(ws + S.o_n_cand8, 0, S.zero_bytes, ctx->stream));
-    const PassAKernel* pa = pass_a_kernel(S, d_probes != nullptr);
-    if (!pa) return GF_E_UNSUPPORTED;   // (the plan's forms all have their entry)
-    ctx->screen_kernels = std::string(pa->name) + ",pf4_probe_kernel,pf4_resolve_kernel,pf4_list_kernel";
+    const PassAKernel* pa = d_parts ? nullptr : pass_a_kernel(S, d_probes != nullptr);
+    if (!pa && !d_parts) return GF_E_UNSUPPORTED;   // (the plan's forms all have their entry)
+    ctx->screen_kernels = (pa ? std::string(pa->name) + "," : std::string()) + "pf4_probe_kernel,pf4_resolve_kernel,pf4_list_kernel";
     LaunchTimer tm(ctx, GF_KERNEL_SCREEN);
-    if (pa->column) hipLaunchKernelGGL(pa->column, dim3(Q.n_writers), dim3(64 * PF2_WAVES), S.lds_a_col, ctx->stream, Q);
-    else hipLaunchKernelGGL(pa->rows, dim3(Q.n_writers), dim3(64 * PF2_WAVES), S.lds_a, ctx->stream, Q, (uint32_t)S.slice_words);
+    if (pa) launch_pass_a(ctx, S, pa, Q);
     const size_t lds_b = (((size_t)1 << (ix.bm_log2 - PF2_NB_LOG2 - 5)) + 16 * (3 * PF4_OBUF + 2 * PF2_PEND)) * 4;
     hipLaunchKernelGGL(pf4_probe_kernel, dim3((unsigned)std::min<size_t>(PF2_NB, (size_t)ctx->n_cu)), dim3(1024), lds_b, ctx->stream, Q);
     const size_t lds_r = (size_t)4 * 8 * (((2 * (size_t)S.rb + 3) / 4) * 4 + 4) * 4;

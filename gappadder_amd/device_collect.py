@@ -696,10 +696,11 @@ class DeviceCollector:
                 alts.update(round_keywords(cfg, L, "adjudication", "adj", ("seed", "max_mismatch", "min_overlap", "context", "min_votes", "ratio"),
                                            ADJ.check_params, "adjudicate"))
         pipe = Pipeline(gf, len(gaps), L, kk, device=self.dev, anchor_mapq=self.anchor_mapq, clip_dist=self.clip_dist,
-                        k_screen=k_screen or None, keep_read_ids=True, probe_column=False,
+                        k_screen=k_screen or None, keep_read_ids=True, probe_column=False, screen_parts=False,
                         read_support=bool(cfg.get("fill_support")) and bool(kk), support_k=cfg.get("fill_support_k"), **polish, **pileup, **pairs, **span, **joins, **alts)
         # (no probe column on the file path: a file-born library is screened once, and until the packing kernels write the column while
-        # they hold the bases, building it is a pass of its own — 38 B read + 4 np written per read — that costs more than pass A saves)
+        # they hold the bases, building it is a pass of its own — 38 B read + 4 np written per read — that costs more than pass A saves;
+        # no resident parts either: they are one pass A to build and save one per screen, and there is one screen)
         pipe.assemble_in_step = False
         for lb in libs:
             pipe.add_library(lb)

@@ -73,7 +73,8 @@ class DeviceLibrary:
     over all ranks, `first_pair` = this rank's first pair (contiguous shards)."""
 
     def __init__(self, name, is_mean, is_sd, n_reads, d_reads, d_recs, n_recs=None, pull_mates=1, d_nmask=None, n_total=None,
-                 first_pair=0, tag_ctx=None, screen=True, d_rec_keys=None, d_probes=None, probe_geom=None, d_lin_keys=None, lin_layout=None):
+                 first_pair=0, tag_ctx=None, screen=True, d_rec_keys=None, d_probes=None, probe_geom=None, d_lin_keys=None, lin_layout=None,
+                 d_parts=None, parts_geom=None):
         self.name, self.is_mean, self.is_sd, self.pull_mates = name, int(is_mean), int(is_sd), int(pull_mates)
         self.n_reads, self.d_reads, self.d_recs, self.d_nmask = int(n_reads), d_reads, d_recs, d_nmask
         self.n_recs = int(n_reads if n_recs is None else n_recs)
@@ -88,6 +89,9 @@ class DeviceLibrary:
         # the reads' probe column and the geometry it was built for (gf_read_probes_dev, or the file path's packing kernels); None:
         # Pipeline.add_library builds it where it pays
         self.d_probes, self.probe_geom = d_probes, probe_geom
+        # the reads' resident parts — the output of the filter's first pass — and what they were built for (gf_screen_parts_build_dev);
+        # None: Pipeline.add_library builds them where parts are kept
+        self.d_parts, self.parts_geom = d_parts, parts_geom
         self.counts = {}
 
 
@@ -111,7 +115,7 @@ PICKS = {"exact": ("gf_pick_anchored2_dev", "gf_pick_anchored2_from_dev", "gf_pi
 class Pipeline:
     def __init__(self, gf, n_gaps, read_len, k_pairs, device=None, world=1, rank=0, backend="nccl", force_exchange=False,
                  min_count=2, min_contig=40, anchors=(30, 15), clip_dist=250, anchor_mapq=30, k_screen=None, keep_read_ids=False,
-                 key_column=True, linear_keys=True, probe_column=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False,
+                 key_column=True, linear_keys=True, probe_column=True, screen_parts=True, merge_in_step=False, merge_max_set=128, anchor_mode="exact", second_round=False,
                  recruit_rounds=1, extended_fill=False, ext_base_cap=None, rescue_round=False, read_support=False, support_k=None, polish=False,
                  polish_seed=16, polish_max_mismatch=4, polish_min_overlap=48, polish_min_votes=2, polish_indels=False, polish_max_indel=8,
                  pair_span=False, pair_seed=16,
@@ -136,6 +140,12 @@ class Pipeline:
         read, built once when a library is added (k = 51 on 150 bases: 12 of a read's 38 bytes, 10.8 GB for C4's 900 M reads) — and that
         pass streams THEM; only where 4 * np is at most half a packed read and the column fits (else nothing is built and the pass reads
         the rows).  A column built for another geometry (k, read length, read count) is rebuilt before it is used.
+        screen_parts: the screened libraries keep, beside the column, what the filter's first pass makes of it — every probe as a 4-byte
+        pair in its bucket's part, with the parts' fill history and counts (gf_screen_parts_geom; 12.2 GB for C4) — built once when a
+        library is added, from the column where there is one; the screen of every step then starts at its second pass.  None of it
+        depends on the gaps or the draft.  Only where a column would be kept too (gf_screen_parts_geom::use) and the parts fit; parts
+        built for another geometry or another plan (k, read count, writers) are rebuilt before they are used, and the column stays: it is
+        what the first pass streams whenever the parts are refused.
         anchor_mode: how every pick of the step anchors the flanks on the contigs — "exact" anchors (gf_pick_anchored2_dev) or "align",
         seed-and-extend of the whole flanks (gf_pick_aligned_dev; `anchors` are then the score thresholds), or "gapped", the same with a
         banded affine-gap extension that aligns through a draft indel next to the gap (gf_pick_gapped_dev); with "align" and "gapped" the
@@ -259,6 +269,7 @@ class Pipeline:
         self.key_column = bool(key_column)
         self.linear_keys = self.key_column and bool(linear_keys)
         self.probe_column = bool(probe_column)
+        self.screen_parts = bool(screen_parts)
         # merge_in_step: the contig-merge round (assemble_gaps.py:301-306 run_contigs_merge: dedup + ContigsMerger per gap) runs INSIDE the
         # step, on the device, for the gaps the first pick leaves open, followed by a second pick over the merged contigs — the reference
         # merges before it picks (:335-339); a gap the pick closes from its own contigs gains nothing from merging.  Merged contigs are
@@ -324,6 +335,8 @@ class Pipeline:
             self.gf.sync()
         if self.probe_column and lb.screen:
             self._probe_column(lb)
+        if self.screen_parts and lb.screen:
+            self._screen_parts(lb)
         self.libs.append(lb)
         return lb
 
@@ -374,6 +387,33 @@ class Pipeline:
         self.gf.sync()
         lb.d_probes, lb.probe_geom = d_probes, geom
 
+    def _screen_parts(self, lb):
+        """The library's resident parts for THIS pipeline's screen: kept when they were built for exactly what the screen would build now,
+        built (again) otherwise — from the column where the library has one; None where parts are not kept, do not fit the device, or a
+        part ran full (the filter then runs its first pass, from the column or the rows)."""
+        if not 16 <= self.k_screen <= min(64, self.L):
+            return
+        want = B.ScreenPartsGeom()
+        self._chk(self.lib.gf_screen_parts_geometry(self.h, lb.n_reads, self.L, self.k_screen, C.byref(want)), "gf_screen_parts_geometry")
+        if lb.d_parts is not None and lb.parts_geom is not None and lb.parts_geom.use and lb.parts_geom.key() == want.key():
+            return
+        lb.d_parts = lb.parts_geom = None
+        if not want.use or not lb.n_reads:
+            return
+        try:
+            d_parts = torch.empty(self.lib.gf_screen_parts_bytes(C.byref(want)) // 4, dtype=torch.int32, device=self.dev)
+        except torch.cuda.OutOfMemoryError:
+            return
+        torch.cuda.synchronize()
+        col = self.probe_column and lb.d_probes is not None
+        geom = B.ScreenPartsGeom()
+        self._chk(self.lib.gf_screen_parts_build_dev(self.h, lb.d_reads.data_ptr(), lb.d_probes.data_ptr() if col else None,
+                                                     C.byref(lb.probe_geom) if col else None, lb.n_reads, self.L, self.k_screen, d_parts.data_ptr(),
+                                                     C.byref(geom)), "gf_screen_parts_build_dev")
+        self.gf.sync()
+        if geom.use:
+            lb.d_parts, lb.parts_geom = d_parts, geom
+
     def _alloc_hit_buffers(self, lb, hit_cap):
         lb.hit_cap = int(hit_cap)
         lb.d_hits = self._u8(lb.hit_cap * 8)
@@ -394,9 +434,11 @@ class Pipeline:
                 self._chk(lib.gf_stream_wait_after_filter(lb.h2, h), "gf_stream_wait_after_filter")
         if lb.screen:
             col = self.probe_column and lb.d_probes is not None     # (the library checks the geometry again: a stale column is not used)
-            self._chk(lib.gf_screen_reads_probes_dev(h, lb.d_reads.data_ptr(), lb.d_nmask.data_ptr() if lb.d_nmask is not None else None,
-                                                     lb.d_probes.data_ptr() if col else None, C.byref(lb.probe_geom) if col else None, lb.n_reads,
-                                                     self.L, self.k_screen, 1, lb.d_hits.data_ptr(), lb.hit_cap, lb.cp), "gf_screen_reads_probes_dev")
+            parts = self.screen_parts and lb.d_parts is not None    # (likewise: parts of another plan are not used)
+            self._chk(lib.gf_screen_reads_parts_dev(h, lb.d_reads.data_ptr(), lb.d_nmask.data_ptr() if lb.d_nmask is not None else None,
+                                                    lb.d_probes.data_ptr() if col else None, C.byref(lb.probe_geom) if col else None,
+                                                    lb.d_parts.data_ptr() if parts else None, C.byref(lb.parts_geom) if parts else None, lb.n_reads,
+                                                    self.L, self.k_screen, 1, lb.d_hits.data_ptr(), lb.hit_cap, lb.cp), "gf_screen_reads_parts_dev")
         if tagger:
             self.tagger(lb)
 

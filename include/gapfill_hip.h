@@ -90,7 +90,8 @@ const char* gf_strerror(int code);
 const char* gf_last_error(gf_ctx* ctx);       /* text of the last HIP error seen by this ctx */
 /* the filter kernels the last gf_screen_reads[_dev] call launched, comma separated, as a profiler names them without namespace and
  * argument list (e.g. "pf4_scatter_lines_kernel<3u, false>,pf4_probe_kernel,pf4_resolve_kernel,pf4_list_kernel"): lets a caller
- * tie a committed rocprofv3 summary to the build that is running */
+ * tie a committed rocprofv3 summary to the build that is running.  A screen from a library's resident parts names no first-pass kernel
+ * ("pf4_probe_kernel,pf4_resolve_kernel,pf4_list_kernel"); after gf_screen_parts_build_dev: the first-pass kernel the build launched */
 const char* gf_screen_kernels(gf_ctx* ctx);
 int gf_set_stream(gf_ctx* ctx, void* hip_stream); /* adopt a caller's hipStream_t (NULL: back to the ctx's own) */
 int gf_sync(gf_ctx* ctx);
@@ -293,6 +294,37 @@ int gf_read_probes_dev(gf_ctx* ctx, const void* d_packed_reads, size_t n_reads, 
 int gf_screen_reads_probes_dev(gf_ctx* ctx, const void* d_packed_reads, const void* d_n_mask_or_null, const void* d_probes_or_null,
                                const gf_probe_geom* built_for, size_t n_reads, int read_len, int k, int min_hits, void* d_out, size_t cap,
                                void* d_n_out);
+/* The same screen over a library that keeps its RESIDENT PARTS: what the partitioned filter's first pass leaves — every probe of every
+ * read as a 4-byte pair in its bucket's part, the parts' fill history and their counts — depends on the reads, the probe geometry and
+ * the shape of the parts alone, never on the gaps, the draft or the index built from them.  A library that is screened step after step
+ * keeps it, and the screen starts at its second pass.
+ *   gf_screen_parts_geometry   the probe geometry (as gf_probe_geometry) and, from the same plan the screen makes, the numbers that shape
+ *                              the first pass's output; `use`: whether parts are kept — exactly where a probe column is (probe.use) and
+ *                              the screen takes the whole-line partitioned filter.  ctx may be NULL: the default options, 256 CUs.
+ *   gf_screen_parts_bytes      bytes of the one buffer [count | fills | pairs + the 64 words idle lanes of the first pass store to]
+ *   gf_screen_parts_build_dev  runs the first pass alone into d_parts — from the column when d_probes / probe_geom fit this geometry, else
+ *                              from the packed rows; no gaps are needed — and reports what it built for.  A set-up call: it waits for the
+ *                              stream.  `use` comes back 0 where no parts are kept (nothing was launched) or where a part ran full
+ *                              (degenerate reads: a screen tests such pairs on the spot, which needs the index): keep none then.
+ *   gf_screen_reads_parts_dev  gf_screen_reads_probes_dev; where `parts_for` equals what THIS call would build (read count, read length, k,
+ *                              probe geometry, writers, capacity, groups) the first pass is not launched and the later passes read d_parts
+ *                              (they write none of it: one buffer serves any number of screens, under any gaps) — otherwise today's path,
+ *                              column or rows.  gf_screen_kernels tells which.  Same hits either way. */
+typedef struct {
+    gf_probe_geom probe;
+    uint32_t n_writers, cap;          /* parts: [256 buckets][n_writers][cap] entries */
+    uint32_t gs, n_groups, n_grp;     /* fill history: [bucket][writer][gs] words, n_groups + 1 used; groups per tile iteration */
+    uint32_t tiles_wg;                /* 64-read tiles per writer and tile iteration */
+    uint32_t use;                     /* 1: keep the parts, a screen of this geometry starts at its second pass; 0: keep none */
+    uint32_t reserved;
+} gf_screen_parts_geom;
+int gf_screen_parts_geometry(gf_ctx* ctx, size_t n_reads, int read_len, int k, gf_screen_parts_geom* out);
+size_t gf_screen_parts_bytes(const gf_screen_parts_geom* geom);
+int gf_screen_parts_build_dev(gf_ctx* ctx, const void* d_packed_reads, const void* d_probes_or_null, const gf_probe_geom* probe_geom_or_null,
+                              size_t n_reads, int read_len, int k, void* d_parts /* gf_screen_parts_bytes */, gf_screen_parts_geom* built_for);
+int gf_screen_reads_parts_dev(gf_ctx* ctx, const void* d_packed_reads, const void* d_n_mask_or_null, const void* d_probes_or_null,
+                              const gf_probe_geom* probe_geom_or_null, const void* d_parts_or_null, const gf_screen_parts_geom* parts_for,
+                              size_t n_reads, int read_len, int k, int min_hits, void* d_out, size_t cap, void* d_n_out);
 /* Test aid (GF_E_UNSUPPORTED unless GF_DIAGNOSTICS is set in the environment): what the last screen on this context that took the
  * partitioned filter left in its workspace, as device pointers that stay valid until the next screen — the pairs of its first pass
  * ([256 buckets][n_writers][cap] entries, `count` of them written per part, in generation order), the fill history ([bucket][writer][gs]
